@@ -15,10 +15,19 @@ Multi-GPU (--gpus N, one process per GPU via torch.distributed.run): every
 rank encodes+decodes its own independent stripe (seed = rank), no data-path
 collective; value = all ranks' bytes / max-over-ranks time ("weak").
 
-Also reported: roofline of the dominant kernel (hipEvent-timed live in a
-profiled copy of the timed loop; PMC traffic from profiles/ if present) and
-the CPU baseline (the oracle's C restatement of the reference NoSimd engine,
-1 core, rank 0 at N=1 only, bounded sample).
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the
+metric needs: set up the stripe, untimed steps (SETTLE_STEPS for the GPU's
+clocks, then the W warm-up steps), N timed steps, the result line.  `--dump-outputs DIR` also writes what the last timed step computed
+(dump_outputs below), so that two builds can be compared output for output:
+the inputs are the same seeded stream in every run.
+
+With `--full`, also checked and reported: the correctness gate (recovery hash
+against the oracle fixture, the decode's restore), the roofline of the
+dominant kernel (hipEvent-timed live in a profiled copy of the timed loop;
+PMC traffic from profiles/ if present), the encode-only / decode-only rates,
+the side measurements under `extra` (`--no-extra` leaves them out) and the
+CPU baseline (the oracle's C restatement of the reference NoSimd engine,
+1 core, rank 0 at N=1 only, bounded sample; `--no-cpu-baseline`).
 """
 from __future__ import annotations
 
@@ -39,6 +48,7 @@ sys.path.insert(0, str(ROOT / "reed-solomon-16_amd"))
 METRIC = "encode+decode GiB/s (device-resident, 1024B shards); % of HBM roofline"
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
 GIB = 2.0 ** 30
+SETTLE_STEPS = 200  # plain run: untimed steps before the warm-up (~30 ms at the default stripe), see main()
 
 
 def parse():
@@ -52,9 +62,15 @@ def parse():
     p.add_argument("--slices", type=int, default=1, help="concurrent column slices of the device codec")
     p.add_argument("--split-decode", action="store_true",
                    help="issue the step's decode split (rs16_decode_prepare on a side stream during the encode)")
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="bound of the CPU-baseline sample")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extra", action="store_true", help="skip the 1000:1000 side measurements")
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the metric: correctness gate, rooflines, encode / decode rates, the "
+                        "extras and the CPU baseline (a plain run sets up, warms up, times the steps and prints)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's outputs (recovery and restored shards) as "
+                        "DIR/<name>.npy")
+    p.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: bound of the CPU-baseline sample")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    p.add_argument("--no-extra", action="store_true", help="--full without the side measurements")
     p.add_argument("--no-verify", action="store_true", help="diagnostic (ablation) builds only")
     p.add_argument("--traffic-json", default=str(ROOT / "profiles" / "pmc_traffic.json"))
     p.add_argument("--cpu-stub", action="store_true",
@@ -68,6 +84,47 @@ def free_port():
     port = s.getsockname()[1]
     s.close()
     return port
+
+
+DUMP_SAMPLE_VALUES = 4 << 20  # values per sampled array: 16 MiB of float32
+
+
+def dump_outputs(dirpath, shards):
+    """--dump-outputs: `shards` = {name: (rows, S) uint8 array}, the shard
+    buffers a caller of the timed path holds after its last step (the encode's
+    recovery shards, the decode's restored originals).  Per array:
+      DIR/<name>.npy          float32, the shard bytes of a fixed sample of
+                              rows (all of them if they fit DUMP_SAMPLE_VALUES;
+                              else the first, the last and a default_rng(0)
+                              choice, in row order) and of the first
+                              DUMP_SAMPLE_VALUES columns
+      DIR/<name>_rowsums.npy  float64 (rows, 2), of EVERY row: the sum of its
+                              bytes and the sum of byte x (column + 1), both
+                              exact in float64
+    so that a difference anywhere in an output shows in at least the sums."""
+    import numpy as np
+
+    out = Path(dirpath)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in shards.items():
+        rows, S = a.shape
+        cols = min(S, DUMP_SAMPLE_VALUES)
+        n = max(1, min(rows, DUMP_SAMPLE_VALUES // cols))
+        if n < rows:
+            pick = np.random.default_rng(0).choice(rows, n, replace=False)
+            pick[:2] = (0, rows - 1)
+            pick = np.unique(pick)
+        else:
+            pick = np.arange(rows)
+        np.save(out / f"{name}.npy", a[pick, :cols].astype(np.float32))
+        weights = np.arange(1, S + 1, dtype=np.float64)
+        sums = np.empty((rows, 2))
+        step = max(1, (8 << 20) // S)  # row blocks: the float64 copy stays small
+        for i in range(0, rows, step):
+            blk = a[i:i + step].astype(np.float64)
+            sums[i:i + step, 0] = blk.sum(axis=1)
+            sums[i:i + step, 1] = blk @ weights
+        np.save(out / f"{name}_rowsums.npy", sums)
 
 
 def pass_bytes(prog: str, k: int, m: int, S: int, orig_rcv=None, rec_rcv=None) -> float:
@@ -586,6 +643,8 @@ def stub_main(args, world, rank, local, dist, json_fd):
     timed(step, max(3, args.steps // 4), codec_rank)
     step_bytes = 2 * buf.size
     ranks = gather_ranks(dist, world, rank_identity(local, -1), per_rank, args.steps, step_bytes)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"stub": buf.reshape(1024, -1)})
     if rank == 0:
         out = {"metric": METRIC, "value": round(world * step_bytes * args.steps / dt / GIB, 3), "unit": "GiB/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -724,20 +783,23 @@ def main():
         rs16.decode_device(k, m, S, d_rest.ptr, d_of.ptr, d_rec.ptr, d_rf.ptr, k - loss, loss, engine=eng)
 
     # ---- correctness gate (the measured path must be the bit-exact one) ----
-    encode()
-    recovery = d_rec.download(shape=(m, S))
-    verified = "decode restores every original bit-exactly"
-    if seed == 0 and S == 1024:
-        fx = json.loads((ROOT / "tests" / "golden" / "kib_hashes.json").read_text())
-        want = {(c["k"], c["m"]): c["recovery_sha256"] for c in fx["cases"]}.get((k, m))
-        if want is not None:
-            got = hashlib.sha256(recovery.tobytes()).hexdigest()
-            assert args.no_verify or got == want, f"recovery hash {got} != oracle fixture {want}"
-            verified = "recovery SHA-256 == oracle fixture; " + verified
-    decode()
-    assert args.no_verify or np.array_equal(d_rest.download(shape=(k, S)), original), "decode did not restore"
-    if args.no_verify:
-        verified = "NOT VERIFIED (diagnostic build)"
+    # --full only: a plain run leaves the comparison to --dump-outputs
+    verified = "not checked (plain run: --full checks, --dump-outputs writes the outputs)"
+    if args.full:
+        encode()
+        recovery = d_rec.download(shape=(m, S))
+        verified = "decode restores every original bit-exactly"
+        if seed == 0 and S == 1024:
+            fx = json.loads((ROOT / "tests" / "golden" / "kib_hashes.json").read_text())
+            want = {(c["k"], c["m"]): c["recovery_sha256"] for c in fx["cases"]}.get((k, m))
+            if want is not None:
+                got = hashlib.sha256(recovery.tobytes()).hexdigest()
+                assert args.no_verify or got == want, f"recovery hash {got} != oracle fixture {want}"
+                verified = "recovery SHA-256 == oracle fixture; " + verified
+        decode()
+        assert args.no_verify or np.array_equal(d_rest.download(shape=(k, S)), original), "decode did not restore"
+        if args.no_verify:
+            verified = "NOT VERIFIED (diagnostic build)"
 
     timed, barrier = make_timed(eng.synchronize, dist, world)
 
@@ -747,7 +809,7 @@ def main():
     # 3.12) is computed on a side stream while the encode runs; measured slower
     # (the locator's workgroups take slots from the encode's first pass, and the
     # cross-stream wait costs more than the 9 us it hides), so it is an extra.
-    side = eng.create_stream()
+    side = eng.create_stream() if args.full or args.split_decode else None
 
     def step_serial():
         encode()
@@ -759,41 +821,86 @@ def main():
         rs16.decode_device_prepared(k, m, S, d_rest.ptr, d_rec.ptr, engine=eng)
 
     step = step_split if args.split_decode else step_serial
-    held = original.copy()
-    held[:loss] = 0
-    d_rest.upload(held)
-    step_split()
-    assert args.no_verify or np.array_equal(d_rest.download(shape=(k, S)), original), "split decode did not restore"
+    if args.full:
+        held = original.copy()
+        held[:loss] = 0
+        d_rest.upload(held)
+        step_split()
+        assert args.no_verify or np.array_equal(d_rest.download(shape=(k, S)), original), \
+            "split decode did not restore"
 
-    # ---- roofline: dominant kernel, hipEvent-timed on its launch stream ----
-    # An event-profiled copy of the K-step loop, run BEFORE the W warm-up
-    # steps and the timed loop, so that the timed loop runs unprofiled and
-    # in the state the profiled copy leaves the GPU in (a GPU coming out of
-    # idle runs steps ~10-25 of a cold start ~8 % slower while its clocks
-    # settle: extra.sustained, CHANGELOG.md round 4).  Its own first 40 steps warm
-    # the clocks and are not counted.  One column slice, so that every
-    # timed launch is one kernel running alone.
-    # The events are read (host work, GPU idle) only after the timed loop.
-    eng.set_slices(1)
-    eng.set_profiling(True)
-    for _ in range(40):
-        step()
-    eng.synchronize()
-    eng.profile()
-    eng.profile_reset()
-    timed(step, args.steps)
-    eng.set_profiling(False)
-    eng.set_slices(args.slices)
+        # ---- roofline: dominant kernel, hipEvent-timed on its launch stream ----
+        # An event-profiled copy of the K-step loop, run BEFORE the W warm-up
+        # steps and the timed loop, so that the timed loop runs unprofiled and
+        # in the state the profiled copy leaves the GPU in (a GPU coming out of
+        # idle runs steps ~10-25 of a cold start ~8 % slower while its clocks
+        # settle: extra.sustained, CHANGELOG.md round 4).  Its own first 40
+        # steps warm the clocks and are not counted.  One column slice, so
+        # that every timed launch is one kernel running alone.
+        # The events are read (host work, GPU idle) only after the timed loop.
+        eng.set_slices(1)
+        eng.set_profiling(True)
+        for _ in range(40):
+            step()
+        eng.synchronize()
+        eng.profile()
+        eng.profile_reset()
+        timed(step, args.steps)
+        eng.set_profiling(False)
+        eng.set_slices(args.slices)
+    else:
+        # A plain run has no profiled copy in front of it: SETTLE_STEPS untimed
+        # steps stand in for it, so that the W warm-up steps and the timed loop
+        # start from settled clocks here too (measured at 20 timed steps,
+        # 32768:32768 x 1 KiB: 5 / 25 / 65 / 105 / 205 untimed steps first give
+        # 770 / 795 / 853 / 880 / 913 GiB/s, the profiled copy 874).
+        for _ in range(SETTLE_STEPS):
+            step()
 
     for _ in range(args.warmup):
         step()
     per_rank_dt = []
     dt = timed(step, args.steps, per_rank_dt)
-    prof = eng.profile()
     step_bytes = 2 * (k + m) * S  # encode + decode, (original + recovery) bytes each
     value = world * step_bytes * args.steps / dt / GIB
     ranks = gather_ranks(dist, world, rank_identity(local, eng.device), per_rank_dt, args.steps, step_bytes)
     ms_per_step = dt / args.steps * 1e3
+    head = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u16",
+        "data": "synthetic (ChaCha8 seed=rank stream of the reference benches; inputs resident in HBM)",
+        "config": {"workload": f"{k}:{m} x {S} B encode + 100%-loss decode per GPU" +
+                   (" (BASELINE configs[3])" if (k, m, S) == (32768, 32768, 1024) else
+                    " (BASELINE configs[1] + [2])" if (k, m, S) == (1000, 1000, 1024) else ""),
+                   "original_count": k, "recovery_count": m, "shard_bytes": S,
+                   "parallelism": f"independent stripes x {world} (weak, no collective)",
+                   "column_slices": args.slices,
+                   "decode_issue": ("split: rs16_decode_prepare (eval_poly of the received pattern) on a side "
+                                    "stream while the encode runs, then rs16_decode_device_prepared"
+                                    if args.split_decode else "serial: rs16_decode_device after the encode")},
+        "full": args.full,
+    }
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's outputs, as its caller holds them (rank 0's stripe)
+        dump_outputs(args.dump_outputs, {"recovery": d_rec.download(shape=(m, S)),
+                                         "restored": d_rest.download(shape=(k, S))})
+    if not args.full:
+        if rank == 0:
+            head.update({"ranks": ranks, "verified": verified})
+            os.write(json_fd, (json.dumps(head) + "\n").encode())
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    prof = eng.profile()
 
     # Separate encode-only / decode-only rates (same data, same engine), and
     # the step issued the other way (split / serial decode).
@@ -1150,27 +1257,7 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": METRIC,
-            "value": round(value, 3),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u16",
-            "data": "synthetic (ChaCha8 seed=rank stream of the reference benches; inputs resident in HBM)",
-            "config": {"workload": f"{k}:{m} x {S} B encode + 100%-loss decode per GPU" +
-                       (" (BASELINE configs[3])" if (k, m, S) == (32768, 32768, 1024) else
-                        " (BASELINE configs[1] + [2])" if (k, m, S) == (1000, 1000, 1024) else ""),
-                       "original_count": k, "recovery_count": m, "shard_bytes": S,
-                       "parallelism": f"independent stripes x {world} (weak, no collective)",
-                       "column_slices": args.slices,
-                       "decode_issue": ("split: rs16_decode_prepare (eval_poly of the received pattern) on a side "
-                                        "stream while the encode runs, then rs16_decode_device_prepared"
-                                        if args.split_decode else "serial: rs16_decode_device after the encode")},
+            **head,
             "encode_gib_s": round(world * (k + m) * S * args.steps / dt_e / GIB, 3),
             "decode_gib_s": round(world * (k + m) * S * args.steps / dt_d / GIB, 3),
             "ranks": ranks,

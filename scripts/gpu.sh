@@ -8,7 +8,7 @@
 #
 # Steps:
 #   tests[=PYTEST_ARGS]   pytest -m gpu (default: the whole suite under tests/)
-#   bench[=ARGS]          python bench.py ARGS > bench.json (repeatable: bench_2.json, ...)
+#   bench[=ARGS]          python bench.py --full ARGS > bench.json (repeatable: bench_2.json, ...)
 #   bench-n2[=ARGS]       the N = 2 driver launch with both ranks on GPU 0 (RS16_BENCH_SHARE_GPU=1)
 #   stats[=ARGS]          rocprofv3 --kernel-trace --stats of bench.py ARGS (default: 20 steps, no extras)
 #   pmc=COUNTERS[@SCRIPT] one rocprofv3 --pmc pass (counters comma-separated; default workload
@@ -19,7 +19,7 @@
 #   stamps=PROGS[+K]      phase timeline of pass programs PROGS (comma list) at k = m = K (default
 #                         32768) with the stamps build (make -C reed-solomon-16_amd/csrc stamps:
 #                         reed-solomon-16_amd/build_stamps/librs16.so) -> stamps_N.json
-#   ab=DIRA,DIRB[+REPS[+ARGS]]  same-box A/B: bench.py --no-extra --no-cpu-baseline ARGS with
+#   ab=DIRA,DIRB[+REPS[+ARGS]]  same-box A/B: bench.py --full --no-extra --no-cpu-baseline ARGS with
 #                         RS16_LIB=reed-solomon-16_amd/DIRA/librs16.so, then DIRB, alternating, REPS (3) times
 #   slices                bench.py at 1 / 2 / 4 column slices, fresh process per run, 3 reps
 #                         (the profiles/r05_slices.txt measurement)
@@ -47,10 +47,10 @@ for step in "$@"; do
           ${arg:-tests/} > "$O/pytest_$n.log" 2>&1 || fail tests "$O/pytest_$n.log"
       tail -1 "$O/pytest_$n.log" ;;
     bench)
-      timeout -k 10 600 python bench.py $arg > "$O/bench_$n.json" 2> "$O/bench_$n.err" || fail bench "$O/bench_$n.err"
+      timeout -k 10 600 python bench.py --full $arg > "$O/bench_$n.json" 2> "$O/bench_$n.err" || fail bench "$O/bench_$n.err"
       python3 -c "import json,sys;d=json.load(open(sys.argv[1]));print('bench', d['value'], d['ms_per_step'], d.get('kernels_us'))" "$O/bench_$n.json" ;;
     bench-n2)
-      RS16_BENCH_SHARE_GPU=1 timeout -k 10 900 python bench.py --gpus 2 --no-cpu-baseline $arg > "$O/bench_n2_$n.json" \
+      RS16_BENCH_SHARE_GPU=1 timeout -k 10 900 python bench.py --full --gpus 2 --no-cpu-baseline $arg > "$O/bench_n2_$n.json" \
           2> "$O/bench_n2_$n.err" || fail bench-n2 "$O/bench_n2_$n.err"
       python3 -c "import json,sys;d=json.load(open(sys.argv[1]));print('n2', d['value'], d['ms_per_step'], [(r['rank'], r['ms_per_step']) for r in d['ranks']])" "$O/bench_n2_$n.json" ;;
     stats)
@@ -92,7 +92,7 @@ for step in "$@"; do
       [ "$reps" != "$rest" ] && bargs=${rest#*+}
       for rep in $(seq 1 ${reps:-3}); do
         for d in ${dirs//,/ }; do
-          RS16_LIB=reed-solomon-16_amd/$d/librs16.so timeout -k 10 200 python bench.py --no-extra --no-cpu-baseline \
+          RS16_LIB=reed-solomon-16_amd/$d/librs16.so timeout -k 10 200 python bench.py --full --no-extra --no-cpu-baseline \
               ${bargs//+/ } > "$O/ab_${d}_$rep.json" 2> "$O/ab.err" || fail ab "$O/ab.err"
           echo "$d rep=$rep $(python3 -c "import json,sys;d=json.load(open(sys.argv[1]));print(d['value'], d['ms_per_step'], d['kernels_us'])" "$O/ab_${d}_$rep.json")"
         done

@@ -9,7 +9,7 @@ O="$R/gpurun_out/prof_$TAG"
 mkdir -p "$O"
 cd "$R"
 fail() { echo "FAILED at $1"; tail -20 "$2" 2>/dev/null; exit 1; }
-timeout -k 10 400 python bench.py > "$O/bench.json" 2> "$O/bench.err" || fail bench "$O/bench.err"
+timeout -k 10 400 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" || fail bench "$O/bench.err"
 cat "$O/bench.json"
 cd /tmp && export TMPDIR=/tmp
 B="--steps 20 --warmup 3 --no-cpu-baseline --no-extra"
