@@ -487,10 +487,13 @@ enum {
                                       originals lost, all recovery received, k = m = 2^j >= 2048): evaluate
                                       the erasure polynomial and multiply anyway (default: every erasure
                                       log is 0, the multipliers are identities and are skipped) */
-    RS16_DIAG_NO_MID_DIRECT = 1024 /* the general decode's middle pass always as the 2^hi-point IFFT /
+    RS16_DIAG_NO_MID_DIRECT = 1024, /* the general decode's middle pass always as the 2^hi-point IFFT /
                                       derivative / FFT pass, also when the lost originals lie in at most
                                       4 of its output rows per column (default there: a direct product
                                       with the pass's matrix) */
+    RS16_DIAG_WIDE_TWIDDLES = 2048 /* the full 12-lookup multiply in every layer (default: the middle
+                                      passes multiply with 9 lookups in the layers whose twiddles all
+                                      lie in the GF(2^8) subfield) */
 };
 int rs16_engine_set_diagnostics(rs16_engine* eng, int flags);
 /* Deprecated (the round-4 process-wide form, kept for existing callers):
@@ -504,6 +507,19 @@ int rs16_set_diagnostics(int flags);
  * Engine::mul semantics (log_m 65535 == x1).  Lets CPU-only tests check the
  * table format against the reference multiply (NoSimd::mul). */
 void rs16_host_mul(const void* in, void* out, size_t bytes, uint16_t log_m);
+/* The same through the narrow multiply of the middle passes, which leaves
+ * out the lookups from an input's low byte to the output's high byte: equal
+ * to rs16_host_mul exactly when the multiplier is an element of the GF(2^8)
+ * subfield (as a field element, < 256). */
+void rs16_host_mul_narrow(const void* in, void* out, size_t bytes, uint16_t log_m);
+/* The FFT / IFFT twiddle of skew index `index` (0 .. 65534) as the engine's
+ * tables hold it: returns the field element (0 for the "no multiply"
+ * sentinel; ~0 for an index out of range), its log to *log_m (65535 = the
+ * sentinel) and its 20-dword v_perm multiply table to table20 (either may
+ * be NULL).  rs16_host_twiddle_narrow: 1 when the index rule the pass
+ * launches go by calls the twiddle a subfield element, else 0. */
+uint32_t rs16_host_twiddle(uint32_t index, uint32_t* log_m, uint32_t* table20);
+int rs16_host_twiddle_narrow(uint32_t index);
 
 /* Library/build identification, e.g. "rs16-mi355x gfx950". */
 const char* rs16_version(void);

@@ -83,6 +83,30 @@ extern "C" void rs16_host_mul(const void* in, void* out, size_t bytes, uint16_t 
     }
 }
 
+extern "C" void rs16_host_mul_narrow(const void* in, void* out, size_t bytes, uint16_t log_m) {
+    const uint32_t* t = &host_tables().mul_tab[(size_t)log_m * TAB_DWORDS];
+    const uint8_t* src = (const uint8_t*)in;
+    uint8_t* dst = (uint8_t*)out;
+    for (size_t q = 0; q < bytes / 8; q++) {
+        const size_t off = (q >> 3) * 64 + (q & 7) * 4;
+        uint32_t yl, yh, ol = 0, oh = 0;
+        memcpy(&yl, src + off, 4);
+        memcpy(&yh, src + off + 32, 4);
+        mul_xor_narrow(ol, oh, yl, yh, t);
+        memcpy(dst + off, &ol, 4);
+        memcpy(dst + off + 32, &oh, 4);
+    }
+}
+extern "C" uint32_t rs16_host_twiddle(uint32_t index, uint32_t* log_m, uint32_t* table20) {
+    const HostTables& t = host_tables();
+    if (index >= GF_MODULUS) return ~0u;
+    if (log_m) *log_m = t.skew[index];
+    if (table20) memcpy(table20, &t.skew_tab[(size_t)index * TAB_DWORDS], 20 * sizeof(uint32_t));
+    // (the sentinel's log 65535 is the log of the element 0: log[0] = 65535, while exp[65535] = exp[0])
+    return t.skew[index] == GF_MODULUS ? 0u : t.exp[t.skew[index]];
+}
+extern "C" int rs16_host_twiddle_narrow(uint32_t index) { return twiddle_narrow(index) ? 1 : 0; }
+
 extern "C" int rs16_engine_set_profiling(rs16_engine* e, int enable, rs16_error* err) {
     if (int rc = e->activate(err)) return rc;
     if (int rc = e->prof_collect(err)) return rc;
@@ -144,7 +168,7 @@ extern "C" int rs16_decode_check(rs16_engine* e, void* stream, rs16_error* err) 
 }
 static constexpr int DIAG_ALL = DIAG_FORCE_VOFF64 | DIAG_EVAL_TWO_KERNEL | DIAG_EVAL_FULL | DIAG_NO_COLUMN |
                                 DIAG_FORCE_COLUMN | DIAG_TILE_LAST | DIAG_NO_TILE_LAST | DIAG_FD_LDS |
-                                DIAG_COL_RADIX4 | DIAG_NO_IDENTITY | DIAG_NO_MID_DIRECT;
+                                DIAG_COL_RADIX4 | DIAG_NO_IDENTITY | DIAG_NO_MID_DIRECT | DIAG_WIDE_TWIDDLES;
 extern "C" int rs16_engine_set_diagnostics(rs16_engine* e, int flags) {
     const int old = e->diag;
     e->diag = flags & DIAG_ALL;

@@ -69,7 +69,18 @@ inline uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return a ^ b ^ c; }
 #endif
 
 // (xL, xH) ^= (yL, yH) * c  where t points at the table entry of c.
-RS16_HD void mul_xor(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const uint32_t* t) {
+//
+// NARROW: c lies in the GF(2^8) subfield.  The elements are Cantor-basis
+// coordinates (rs16_tables.cpp) and span(v_0 .. v_7) is that subfield, so c is
+// a subfield constant exactly when c < 256.  Multiplying by one maps the
+// subfield to itself: an input's low byte never reaches the output's high
+// byte, i.e. the hi-output pools of the groups L0-2, L3-5 and L6-7 -- dwords
+// 2, 3, 6, 7 and 17 of the table -- are all zero.  Their three lookups and
+// one of the six XORs are left out: 9 v_perm + 5 XOR against 12 + 6.  The
+// same 20-dword table serves both forms (the narrow one ignores five dwords).
+// Which twiddles are narrow: twiddle_narrow (rs16_internal.hpp).
+template <bool NARROW>
+RS16_HD void mul_xor_t(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const uint32_t* t) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(RS16_SHIFT32)
     // The selectors of both dwords from two 64-bit shifts of the (L, H) pair
     // instead of four 32-bit ones: the bits H shifts into L's top land where
@@ -96,14 +107,31 @@ RS16_HD void mul_xor(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const
     const uint32_t s4 = b & 0x07070707u;
     const uint32_t s5 = (b >> 3) & 0x03030303u;
 #endif
-    const uint32_t l0 = perm(t[1], t[0], s0), h0 = perm(t[3], t[2], s0);
-    const uint32_t l1 = perm(t[5], t[4], s1), h1 = perm(t[7], t[6], s1);
-    const uint32_t l3 = perm(t[9], t[8], s3), h3 = perm(t[11], t[10], s3);
-    const uint32_t l4 = perm(t[13], t[12], s4), h4 = perm(t[15], t[14], s4);
-    const uint32_t l2 = perm(t[16], t[16], s2), h2 = perm(t[17], t[17], s2);
-    const uint32_t l5 = perm(t[18], t[18], s5), h5 = perm(t[19], t[19], s5);
-    xL = xor3(xor3(xL, l0, l1), xor3(l2, l3, l4), l5);
-    xH = xor3(xor3(xH, h0, h1), xor3(h2, h3, h4), h5);
+    if constexpr (NARROW) {
+        const uint32_t l0 = perm(t[1], t[0], s0);
+        const uint32_t l1 = perm(t[5], t[4], s1);
+        const uint32_t l3 = perm(t[9], t[8], s3), h3 = perm(t[11], t[10], s3);
+        const uint32_t l4 = perm(t[13], t[12], s4), h4 = perm(t[15], t[14], s4);
+        const uint32_t l2 = perm(t[16], t[16], s2);
+        const uint32_t l5 = perm(t[18], t[18], s5), h5 = perm(t[19], t[19], s5);
+        xL = xor3(xor3(xL, l0, l1), xor3(l2, l3, l4), l5);
+        xH = xor3(xH, h3, h4) ^ h5;
+    } else {
+        const uint32_t l0 = perm(t[1], t[0], s0), h0 = perm(t[3], t[2], s0);
+        const uint32_t l1 = perm(t[5], t[4], s1), h1 = perm(t[7], t[6], s1);
+        const uint32_t l3 = perm(t[9], t[8], s3), h3 = perm(t[11], t[10], s3);
+        const uint32_t l4 = perm(t[13], t[12], s4), h4 = perm(t[15], t[14], s4);
+        const uint32_t l2 = perm(t[16], t[16], s2), h2 = perm(t[17], t[17], s2);
+        const uint32_t l5 = perm(t[18], t[18], s5), h5 = perm(t[19], t[19], s5);
+        xL = xor3(xor3(xL, l0, l1), xor3(l2, l3, l4), l5);
+        xH = xor3(xor3(xH, h0, h1), xor3(h2, h3, h4), h5);
+    }
+}
+RS16_HD void mul_xor(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const uint32_t* t) {
+    mul_xor_t<false>(xL, xH, yL, yH, t);
+}
+RS16_HD void mul_xor_narrow(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const uint32_t* t) {
+    mul_xor_t<true>(xL, xH, yL, yH, t);
 }
 
 // Ones'-complement add/sub on logs (reference add_mod/sub_mod,

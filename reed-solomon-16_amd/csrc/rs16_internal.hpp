@@ -56,6 +56,36 @@ constexpr size_t col_v_offset(uint32_t n) { return n - (1u << COL_LMIN); }
 constexpr size_t COL_V_DWORDS = col_v_offset(4u << COL_LMAX);
 const HostTables& host_tables();
 
+// Narrow twiddles.  The twiddle of skew index i (x = i + 1, b = the lowest set
+// bit of x) lies in span(v_0 .. v_{15-b}) of the Cantor basis; it is an
+// element of the GF(2^8) subfield span(v_0 .. v_7), i.e. < 256 as a field
+// element, exactly when x < 2^(b+8).  Its multiply then needs no lookup from
+// an input's low byte to the output's high byte (mul_xor_narrow, rs16_gf.hpp).
+// rs16_tables.cpp checks the rule against the tables once, when it builds them.
+RS16_HD bool twiddle_narrow(uint32_t i) {
+    const uint32_t x = i + 1;
+    return x < ((x & (0u - x)) << 8);
+}
+// The layers of one direction of a pass launch (tile bits [lo, lo + T), tiles
+// with b_high <= bh_max, skew delta `skew`): the first layer kb from which on
+// every twiddle the launch can form is narrow (T: none).  Layer kb's indices
+// are x - 1 with x = g + d + skew, d = 2^(lo+kb), g a multiple of 2d below
+// (bh_max + 1) 2^(lo+T) (TwiddleEntry, rs16_pass.hip).  The lowest set bit of
+// x is that of (d + skew) mod 2d for every g, or at least 2d when that is 0,
+// so the layer is narrow when its largest x is below 2^8 times that bit.
+inline int first_narrow_layer(uint32_t lo, int T, uint32_t skew, uint32_t bh_max) {
+    int k = T;
+    for (int kb = T - 1; kb >= 0; kb--) {
+        const uint64_t d = (uint64_t)1 << (lo + kb);
+        const uint64_t xmax = (((uint64_t)bh_max + 1) << (lo + T)) - d + skew;
+        const uint64_t low = (d + skew) & (2 * d - 1);
+        const uint64_t bit = low ? (low & (0 - low)) : 2 * d;
+        if (xmax >= (bit << 8)) break;
+        k = kb;
+    }
+    return k;
+}
+
 // ---------------------------------------------------------------------------
 // Pass kernels.  A "pass" applies a contiguous range of FFT/IFFT layers to
 // tiles of 2^T rows (T <= 8) x Q quads (Q = 32 for T > 4, else 64; a quad is
@@ -293,6 +323,7 @@ enum DiagFlags : int {
     DIAG_COL_RADIX4 = 256,    // column codec: the 4-rows-per-thread form for every transform (col_kernel)
     DIAG_NO_IDENTITY = 512,   // whole-half erasures: eval_poly and the per-row multipliers anyway (identity_logs)
     DIAG_NO_MID_DIRECT = 1024, // the general decode's middle pass always as DEC_MID (no mid_direct_kernel)
+    DIAG_WIDE_TWIDDLES = 2048, // the 12-lookup multiply in every layer (no narrow-twiddle pass variants)
 };
 
 constexpr size_t RS16_ZERO_BYTES = 65536;

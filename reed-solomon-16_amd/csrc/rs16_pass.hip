@@ -52,6 +52,12 @@
 //   the first group of each layout-B layer of the two-direction passes; those
 //   groups run the XOR half of the butterfly only (wave-uniform test).
 //
+//   Narrow twiddles: a twiddle that is an element of the GF(2^8) subfield
+//   multiplies with 9 of the 12 lookups (mul_xor_narrow, rs16_gf.hpp).  The
+//   two-direction middle passes exist in compile-time variants that do so
+//   from a given layer of each direction on (NarrowVar); launch_pass takes
+//   the variant the launch's twiddle indices allow (first_narrow_layer).
+//
 //   Batched stripes (PassArgs::stripe_tiles): one launch covers independent
 //   stripes of one geometry; a workgroup's tile index splits into (stripe,
 //   tile within the stripe) and the stripe displaces its array pointers.
@@ -551,7 +557,28 @@ template <int NR> __device__ __forceinline__ void pin_rows(uint32_t (&L)[NR], ui
 //   PR_ZERO IFFT: a group whose rows are all zero on input stays zero and is
 //           skipped.  zmask bit j = tile rows [16j, 16j+16) are all zero.
 enum { PR_NONE = 0, PR_OUT, PR_ZERO };
-template <int P, int T, bool LB, int KB0, int KB1, bool FFT, bool IN_TAB2, int PRUNE, int G, class FIN = NoFin>
+// Narrow-twiddle variants of the two-direction pass kernels (twiddle_narrow,
+// rs16_internal.hpp): from which layer kb of the pass on each direction
+// multiplies by subfield constants only.  A compile-time choice: the
+// unrolled layer code has no branch per group for it.
+//   0  none (the 12-lookup multiply everywhere)
+//   1  every layer of both directions (stripes of up to 2^14 rows; DEC_MID
+//      of the 65536-row general decode)
+//   2  all but the IFFT's layer 0 (the encoder's middle pass of a 2^15-row
+//      stripe: IFFT at skew 2^15, FFT at skew 0)
+//   3  all but the FFT's layer 0 (the identity decode's middle pass: the
+//      same with the directions swapped)
+constexpr int NARROW_VARIANTS = 4;
+template <int NV> struct NarrowVar {
+    static constexpr int NONE = 99;
+    static constexpr int IFFT_FROM = NV == 0 ? NONE : (NV == 2 ? 1 : 0);
+    static constexpr int FFT_FROM = NV == 0 ? NONE : (NV == 3 ? 1 : 0);
+};
+
+// NK: the direction's first narrow layer -- the layers kb >= NK multiply
+// with mul_xor_narrow (every twiddle of theirs in this launch is a subfield
+// constant: launch_pass picks the kernel variant from first_narrow_layer).
+template <int P, int T, int NK, bool LB, int KB0, int KB1, bool FFT, bool IN_TAB2, int PRUNE, int G, class FIN = NoFin>
 struct GroupLoop {
     static __device__ __forceinline__ void run(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR], const Thr& c,
                                                const PassArgs& a, const uint4* tab1, const uint4* tab2,
@@ -561,6 +588,7 @@ struct GroupLoop {
         constexpr int kb = S::kb_of(s);
         constexpr int rb = kb - S::SH;
         constexpr bool more = G + 1 < S::total();
+        constexpr bool NARROW = kb >= NK;
         uint32_t nxt[20];
         if constexpr (more)
             load_table_lds(nxt, group_table<T, LB, KB0, KB1, FFT, G + 1, IN_TAB2>(c, tab1, tab2));
@@ -592,13 +620,13 @@ struct GroupLoop {
             for (int j = 0; j < (1 << rb); j++) {
                 const int m = (gi << (rb + 1)) + j, m2 = m + (1 << rb);
                 if (FFT) {
-                    mul_xor(L[m], H[m], L[m2], H[m2], cur);
+                    mul_xor_t<NARROW>(L[m], H[m], L[m2], H[m2], cur);
                     L[m2] ^= L[m];
                     H[m2] ^= H[m];
                 } else {
                     L[m2] ^= L[m];
                     H[m2] ^= H[m];
-                    mul_xor(L[m], H[m], L[m2], H[m2], cur);
+                    mul_xor_t<NARROW>(L[m], H[m], L[m2], H[m2], cur);
                 }
             }
         } else if (need) {
@@ -620,7 +648,8 @@ struct GroupLoop {
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (S::DF && kb == 0) fin(L, H, gi << 1);  // rows 2 gi, 2 gi + 1 are final
         if constexpr (more)
-            GroupLoop<P, T, LB, KB0, KB1, FFT, IN_TAB2, PRUNE, G + 1, FIN>::run(L, H, c, a, tab1, tab2, nxt, zmask, fin);
+            GroupLoop<P, T, NK, LB, KB0, KB1, FFT, IN_TAB2, PRUNE, G + 1, FIN>::run(L, H, c, a, tab1, tab2, nxt, zmask,
+                                                                                     fin);
     }
 };
 
@@ -640,7 +669,8 @@ __device__ __forceinline__ const uint4* lds_vgpr(const uint4* p) {
 }
 
 // Apply the layers for k-bits [KB0, KB1) held in registers of layout LB.
-template <int P, int T, bool LB, int KB0, int KB1, bool FFT, bool IN_TAB2, int PRUNE = PR_NONE, class FIN = NoFin>
+template <int P, int T, int NK, bool LB, int KB0, int KB1, bool FFT, bool IN_TAB2, int PRUNE = PR_NONE,
+          class FIN = NoFin>
 __device__ __forceinline__ void layers(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR], const Thr& c,
                                        const PassArgs& a, const uint4* tab1, const uint4* tab2,
                                        uint32_t zmask = 0, const FIN& fin = FIN()) {
@@ -651,7 +681,7 @@ __device__ __forceinline__ void layers(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[
         }
         uint32_t t0[20];
         load_table_lds(t0, group_table<T, LB, KB0, KB1, FFT, 0, IN_TAB2>(c, tab1, tab2));
-        GroupLoop<P, T, LB, KB0, KB1, FFT, IN_TAB2, PRUNE, 0, FIN>::run(L, H, c, a, tab1, tab2, t0, zmask, fin);
+        GroupLoop<P, T, NK, LB, KB0, KB1, FFT, IN_TAB2, PRUNE, 0, FIN>::run(L, H, c, a, tab1, tab2, t0, zmask, fin);
     }
 }
 
@@ -1354,10 +1384,12 @@ template <int P, int T> struct EvenStore {
     }
 };
 
-template <int P, int T>
+template <int P, int T, int NV>
 __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, uint32_t tile, uint32_t slab,
                                              ItemRegs<P, T>& d, uint8_t* smem) {
     using PT = ProgTraits<P>;
+    constexpr int NKI = NarrowVar<NV>::IFFT_FROM, NKF = NarrowVar<NV>::FFT_FROM;
+    static_assert(NV == 0 || (PT::IFFT && PT::FFT && T > 4), "narrow variants: two-direction passes only");
     using SM = Smem<P, T>;
     using G = Geo<T>;
     constexpr int NR = G::NR;
@@ -1433,7 +1465,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
         // DEC_MID: a wave whose rows all are zero skips its layout-A layers
         bool skip_a = false;
         if constexpr (ZERO_SKIP) skip_a = __all(d.zrow == (1u << NR) - 1);
-        if (!skip_a) layers<P, T, false, 0, R, false, false>(L, H, c, a, tab1, tab2);
+        if (!skip_a) layers<P, T, NKI, false, 0, R, false, false>(L, H, c, a, tab1, tab2);
         RS16_STAMP(a, 3);
         prio<P, 1, T>();
         if constexpr (T > 4) {
@@ -1467,8 +1499,8 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
             } else {
                 // (SHARED: the layout-B tables t >= TSPLIT sit beside the image)
                 const uint4* tab1b = SM::SHARED ? (const uint4*)(smem + SM::TABB_OFF) - G::TSPLIT * 5 : tab1;
-                layers<P, T, true, R, (T > 4 ? T : R), false, false, (ZERO_SKIP ? PR_ZERO : PR_NONE)>(L, H, c, a, tab1b,
-                                                                                                    tab2, d.zmask);
+                layers<P, T, NKI, true, R, (T > 4 ? T : R), false, false, (ZERO_SKIP ? PR_ZERO : PR_NONE)>(
+                    L, H, c, a, tab1b, tab2, d.zmask);
             }
             in_b = true;
         }
@@ -1489,8 +1521,8 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
     // ---------------- FFT ----------------
     if constexpr (PT::FFT) {
         if constexpr (T > 4) {
-            layers<P, T, true, R, (T > 4 ? T : R), true, TWO, (P == DEC_MID ? PR_OUT : PR_NONE)>(L, H, c, a, tab1,
-                                                                                             tab2);
+            layers<P, T, NKF, true, R, (T > 4 ? T : R), true, TWO, (P == DEC_MID ? PR_OUT : PR_NONE)>(L, H, c, a, tab1,
+                                                                                                  tab2);
             if constexpr (SPLIT_FD) {
                 // the layout-A bits' derivative terms (fd_image) join the
                 // register rows that feed consumed rows
@@ -1556,10 +1588,10 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
         if constexpr (EARLY) {
             Thr cs = c;
             asm volatile("" : "+v"(cs.offL));
-            layers<P, T, false, 0, R, true, (TWO && !(SM::RESTAGE))>(L, H, c, a, tab1, tab2, 0,
-                                                                   EarlyStore<P, T>{a, cs, rvt, lostf});
+            layers<P, T, NKF, false, 0, R, true, (TWO && !(SM::RESTAGE))>(L, H, c, a, tab1, tab2, 0,
+                                                                        EarlyStore<P, T>{a, cs, rvt, lostf});
         } else if (need) {
-            layers<P, T, false, 0, R, true, (TWO && !(SM::RESTAGE))>(L, H, c, a, tab1, tab2);
+            layers<P, T, NKF, false, 0, R, true, (TWO && !(SM::RESTAGE))>(L, H, c, a, tab1, tab2);
         }
         RS16_STAMP(a, 9);
     }
@@ -1601,7 +1633,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
 
 // The pass: workgroup b processes item b of the launch (4 waves per SIMD,
 // except the one-pass decoders, whose larger register sets take 1).
-template <int P, int T>
+template <int P, int T, int NV = 0>
 __global__ void __launch_bounds__(Geo<T>::THREADS, ((P == DEC_SINGLE || P == DEC_HALF_SINGLE) ? 1 : 4))
     pass_kernel(PassArgs a) {
     using G = Geo<T>;
@@ -1709,7 +1741,7 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, ((P == DEC_SINGLE || P == DEC
     st.template finish<EARLY>(a, c, smem);
     rcn.count();
     RS16_STAMP(a, 2);
-    process_item<P, T>(a, c, tile, slab, cur, smem);
+    process_item<P, T, NV>(a, c, tile, slab, cur, smem);
     rcn.store(a, c);
 }
 
@@ -2057,8 +2089,34 @@ static const PassFn kPass[NUM_PROGS][9] = {
     RS16_ROW(DEC_HALF_LAST), RS16_ROW(DEC_HALF_SINGLE),
 };
 #undef RS16_ROW
+// The narrow variants [NV - 1][T - 5] of the two two-direction middle passes
+// (nullptr: none, the launch takes a variant that assumes less, or NV = 0).
+// DEC_MID runs at skew 0 in both directions, so it is narrow everywhere or
+// not at all; ENC_MID needs variants 2 / 3 only with 2^15-row stripes (T = 8).
+#define RS16_NROW(P, NV) {pass_kernel<P, 5, NV>, pass_kernel<P, 6, NV>, pass_kernel<P, 7, NV>, pass_kernel<P, 8, NV>}
+static const PassFn kEncMidNarrow[NARROW_VARIANTS - 1][4] = {
+    RS16_NROW(ENC_MID, 1),
+    {nullptr, nullptr, nullptr, pass_kernel<ENC_MID, 8, 2>},
+    {nullptr, nullptr, nullptr, pass_kernel<ENC_MID, 8, 3>},
+};
+static const PassFn kDecMidNarrow[4] = RS16_NROW(DEC_MID, 1);
+#undef RS16_NROW
+// The kernel of a launch: among the variants that exist for (prog, T), the
+// one that uses the narrow multiply in the most layers the launch allows
+// (ni / nf: first_narrow_layer of its IFFT / FFT direction).
+static PassFn pick_kernel(int prog, int T, int ni, int nf) {
+    if (T >= 5 && (prog == ENC_MID || prog == DEC_MID)) {
+        for (int nv = 1; nv < NARROW_VARIANTS; nv++) {
+            const int vi = nv == 2 ? 1 : 0, vf = nv == 3 ? 1 : 0;  // NarrowVar<nv>::IFFT_FROM / FFT_FROM
+            if (ni > vi || nf > vf) continue;
+            const PassFn f = prog == ENC_MID ? kEncMidNarrow[nv - 1][T - 5] : (nv == 1 ? kDecMidNarrow[T - 5] : nullptr);
+            if (f) return f;
+        }
+    }
+    return kPass[prog][T];
+}
 
-#define RS16_SM(P)                                                                                             \
+#define RS16_SM(P)                                                                                            \
     {Smem<P, 0>::BYTES, Smem<P, 1>::BYTES, Smem<P, 2>::BYTES, Smem<P, 3>::BYTES, Smem<P, 4>::BYTES,             \
      Smem<P, 5>::BYTES, Smem<P, 6>::BYTES, Smem<P, 7>::BYTES, Smem<P, 8>::BYTES}
 static const int kSmem[NUM_PROGS][9] = {
@@ -2094,14 +2152,23 @@ hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles
         a.voff32 = fits && aligned && !(a.diag & DIAG_FORCE_VOFF64) ? 1u : 0u;
         a.fd_lds = (a.diag & DIAG_FD_LDS) ? 1u : 0u;
     }
+    // Narrow twiddles: the launch's tiles are tile_base + [0, tiles of one
+    // stripe), b_high = tile >> lo (RS16_DIAG_WIDE_TWIDDLES: never)
+    int ni = T, nf = T;
+    if (!(a.diag & DIAG_WIDE_TWIDDLES)) {
+        const uint32_t bh_max = (a.tile_base + (a.stripe_tiles ? a.stripe_tiles : num_tiles) - 1) >> a.lo;
+        ni = first_narrow_layer(a.lo, T, a.skew_ifft, bh_max);
+        nf = first_narrow_layer(a.lo, T, a.skew_fft, bh_max);
+    }
+    const PassFn fn = pick_kernel(prog, T, ni, nf);
     const size_t lds = (size_t)kSmem[prog][T];
     if (lds > 65536) {
-        hipError_t e = hipFuncSetAttribute((const void*)kPass[prog][T], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
+        // (per kernel variant: each is a function of its own)
+        hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     dim3 grid(nwg), block(kThreads[T]);
-    hipLaunchKernelGGL(kPass[prog][T], grid, block, lds, s, a);
+    hipLaunchKernelGGL(fn, grid, block, lds, s, a);
     return hipGetLastError();
 }
 

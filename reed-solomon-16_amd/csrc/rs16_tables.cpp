@@ -127,6 +127,19 @@ void build(HostTables& t) {
     t.skew_tab.resize((size_t)GF_ORDER * TAB_DWORDS);
     for (uint32_t i = 0; i < GF_ORDER; i++)
         std::copy_n(&t.mul_tab[(size_t)t.skew_entry[i] * TAB_DWORDS], TAB_DWORDS, &t.skew_tab[(size_t)i * TAB_DWORDS]);
+    // The narrow pass variants leave out the lookups of the hi-output pools
+    // of the low-byte groups (mul_xor_narrow, rs16_gf.hpp) in the layers
+    // whose twiddle indices twiddle_narrow() accepts: those five dwords must
+    // be zero for exactly these indices.  Checked here, once, like the sentinel.
+    for (uint32_t i = 0; i < GF_MODULUS; i++) {
+        const uint32_t* e = &t.skew_tab[(size_t)i * TAB_DWORDS];
+        const bool zero = (e[2] | e[3] | e[6] | e[7] | e[17]) == 0;
+        if (zero != twiddle_narrow(i)) {
+            fprintf(stderr, "rs16: skew table entry %u is %s a subfield twiddle, against the index rule\n", i,
+                    zero ? "" : "not");
+            abort();
+        }
+    }
 
     // Column codec images: table g of layer kb (g = 2^L - 2^(L-kb) + j, group
     // j covering rows [j 2^(kb+1), (j+1) 2^(kb+1))) is the twiddle of skew

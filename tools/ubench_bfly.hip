@@ -86,6 +86,12 @@ __global__ void __launch_bounds__(256) k(unsigned* out, const unsigned* tab, uns
                 } else if (MODE == 3) {  // the same, instruction classes grouped
                     mul_xor64g(L[m], H[m], L[m2], H[m2], t);
                     L[m2] ^= L[m]; H[m2] ^= H[m];
+                } else if (MODE == 4) {  // FFT butterfly, subfield twiddle (9 lookups)
+                    mul_xor_narrow(L[m], H[m], L[m2], H[m2], t);
+                    L[m2] ^= L[m]; H[m2] ^= H[m];
+                } else if (MODE == 5) {  // IFFT butterfly, subfield twiddle
+                    L[m2] ^= L[m]; H[m2] ^= H[m];
+                    mul_xor_narrow(L[m], H[m], L[m2], H[m2], t);
                 } else {          // IFFT butterfly
                     L[m2] ^= L[m]; H[m2] ^= H[m];
                     mul_xor(L[m], H[m], L[m2], H[m2], t);
@@ -135,6 +141,10 @@ int main() {
         const double g2 = g_ghz;
         float ms3 = run<3>(d, tab, blocks);
         const double g3 = g_ghz;
+        float ms4 = run<4>(d, tab, blocks);
+        const double g4 = g_ghz;
+        float ms5 = run<5>(d, tab, blocks);
+        const double g5 = g_ghz;
         (void)ms1;
         printf("waves/SIMD %d: FFT %.3f ms @ %.2f GHz (%.1f cyc/wave-bfly/SIMD = %.2f per instr of 30)  IFFT %.3f ms @ %.2f GHz (%.1f)\n",
                wps, ms0, g0, ms0 * 1e-3 * g0 * 1e9 * 1024 / bf, ms0 * 1e-3 * g0 * 1e9 * 1024 / bf / 30, ms1b, g1,
@@ -143,6 +153,8 @@ int main() {
                ms2 * 1e-3 * g2 * 1e9 * 1024 / bf);
         printf("            FFT, 64-bit shifts, classes grouped %.3f ms @ %.2f GHz (%.1f cyc/wave-bfly/SIMD)\n", ms3, g3,
                ms3 * 1e-3 * g3 * 1e9 * 1024 / bf);
+        printf("            narrow (subfield twiddle, 9 lookups): FFT %.3f ms @ %.2f GHz (%.1f cyc/wave-bfly/SIMD)  IFFT %.3f ms @ %.2f GHz (%.1f)\n",
+               ms4, g4, ms4 * 1e-3 * g4 * 1e9 * 1024 / bf, ms5, g5, ms5 * 1e-3 * g5 * 1e9 * 1024 / bf);
     }
     return 0;
 }
