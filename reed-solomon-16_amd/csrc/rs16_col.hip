@@ -51,11 +51,6 @@
 #include "rs16_colops.hpp"
 #include "rs16_diag.hpp"
 
-// (timing A/B builds: 0 = the radix-2 decoder's eval with 16-term wave layers)
-#ifndef RS16_COL_EVAL_XP
-#define RS16_COL_EVAL_XP 1
-#endif
-
 namespace rs16 {
 
 namespace {
@@ -926,7 +921,9 @@ __global__ __launch_bounds__((1 << L) / 2) void col2_kernel(ColArgs a) {
     // ---- requests, as col_kernel: the decoder's flags and polynomial
     // inputs first, then the layer-0/1 tables into registers, the rows, the DMA
     [[maybe_unused]] uint8_t fr[2] = {0, 0};
-    [[maybe_unused]] ColEval<L, (DEC ? (GEN ? N : 2 * N) / NT : 1), NT, RS16_COL_EVAL_XP> ce;
+    // (XP: the eval's wave layers as lane layers; the 16-term wave layers of
+    // fwht_points measured slower at 16 waves, profiles/r05_col_gen_prune.txt)
+    [[maybe_unused]] ColEval<L, (DEC ? (GEN ? N : 2 * N) / NT : 1), NT, true> ce;
     if constexpr (DEC) {
 #pragma unroll
         for (int m = 0; m < 2; m++) {

@@ -1,6 +1,6 @@
 // rs16_colops.hpp -- in-wave radix-4 building blocks of the column codec
 // (rs16_col.hip) and of the one-wave-per-quad-column tile kernels
-// (rs16_pass.hip): a thread holds 4 rows of one quad column (the rows of a
+// (rs16_pass_small.hpp): a thread holds 4 rows of one quad column (the rows of a
 // block over two row bits B0, B1 inserted into its lane index), the two
 // layers of a block are butterflies between its registers, and the row bits
 // of registers and lanes trade places inside the wave between blocks.

@@ -199,18 +199,20 @@ int rs16_engine::prof_collect(rs16_error* err) {
     return RS16_OK;
 }
 
-int rs16_engine::pass(int prog, int T, const PassArgs& a, uint32_t tiles, hipStream_t s, rs16_error* err, int prof) {
+template <class F> int rs16_engine::profiled(int prof, hipStream_t s, rs16_error* err, F launch) {
     hipEvent_t ev;
-    if (prof < 0) prof = prog;
     if (int rc = prof_begin(s, &ev, err)) return rc;
-    if (stamp_buf && prof == stamp_prof) {
-        PassArgs b = a;
-        b.stamps = (uint64_t*)stamp_buf;
-        RS16_HIP(launch_pass(prog, T, b, tiles, s));
-    } else {
-        RS16_HIP(launch_pass(prog, T, a, tiles, s));
-    }
+    RS16_HIP(launch(stamp_buf && prof == stamp_prof ? (uint64_t*)stamp_buf : nullptr));
     return prof_end(prof, s, ev, err);
+}
+
+int rs16_engine::pass(int prog, int T, const PassArgs& a, uint32_t tiles, hipStream_t s, rs16_error* err, int prof) {
+    return profiled(prof < 0 ? prog : prof, s, err, [&](uint64_t* stamps) {
+        if (!stamps) return launch_pass(prog, T, a, tiles, s);
+        PassArgs b = a;
+        b.stamps = stamps;
+        return launch_pass(prog, T, b, tiles, s);
+    });
 }
 
 bool rs16_engine::col_ok(int L, size_t S, size_t nstripes, bool gen) const {
@@ -281,17 +283,10 @@ int rs16_engine::col(const ColArgs& args, int L, int mode, hipStream_t s, rs16_e
     a.img_fft = (const uint8_t*)(d_col_img + col_img_offset((uint32_t)L, a.skew_fft ? 1 : 0));
     if (mode == COL_DEC_EVAL) a.vtab = d_col_v + col_v_offset(2u << L);  // (2^(L+1) work rows)
     if (mode == COL_DEC_GEN) a.vtab = d_col_v + col_v_offset(1u << L);   // (2^L work rows)
-    hipEvent_t ev;
-    const int prof = dec ? PROF_COL_DEC : PROF_COL_ENC;
-    if (int rc = prof_begin(s, &ev, err)) return rc;
-    if (stamp_buf && stamp_prof == prof) {
-        ColArgs b = a;
-        b.stamps = (uint64_t*)stamp_buf;
-        RS16_HIP(launch_col(b, (uint32_t)L, mode, s));
-    } else {
-        RS16_HIP(launch_col(a, (uint32_t)L, mode, s));
-    }
-    return prof_end(prof, s, ev, err);
+    return profiled(dec ? PROF_COL_DEC : PROF_COL_ENC, s, err, [&](uint64_t* stamps) {
+        if (stamps) a.stamps = stamps;
+        return launch_col(a, (uint32_t)L, mode, s);
+    });
 }
 
 // The multi-chunk encodes of 128-row chunks in one launch (colm_kernel,
@@ -306,10 +301,8 @@ int rs16_engine::col_multi(size_t k, size_t m, size_t S, size_t S_user, const ui
     c.in_rows = (uint32_t)k;
     c.out_rows = (uint32_t)m;
     c.nch = nch;
-    hipEvent_t ev;
-    if (int rc = prof_begin(s, &ev, err)) return rc;
-    RS16_HIP(launch_col_multi(c, high, s));
-    return prof_end(PROF_COL_ENC, s, ev, err);
+    // (colm_kernel records no timeline: the stamps pointer is not passed on)
+    return profiled(PROF_COL_ENC, s, err, [&](uint64_t*) { return launch_col_multi(c, high, s); });
 }
 
 // Engine::fft over 2^L rows: L <= 8 in one pass; otherwise the high
@@ -800,12 +793,13 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
         const uint32_t* mt = nullptr;
         if (int rc = mid_tables(L, &mt, err)) return rc;
         batch(1u << lo, zs, 0, zs);  // (stripe displacements of the launch)
-        hipEvent_t pev;
-        if (int rc = prof_begin(s, &pev, err)) return rc;
-        if (stamp_buf && stamp_prof == PROF_DEC_MID_DIRECT) a.stamps = (uint64_t*)stamp_buf;
-        RS16_HIP(launch_mid_direct(a, mt, (uint32_t)hi, ns, s));
-        a.stamps = nullptr;
-        if (int rc = prof_end(PROF_DEC_MID_DIRECT, s, pev, err)) return rc;
+        if (int rc = profiled(PROF_DEC_MID_DIRECT, s, err, [&](uint64_t* stamps) {
+                a.stamps = stamps;
+                const hipError_t e = launch_mid_direct(a, mt, (uint32_t)hi, ns, s);
+                a.stamps = nullptr;
+                return e;
+            }))
+            return rc;
         a.mid_direct = MID_DIRECT_MAX;
     }
     RS16_PASS(DEC_MID, hi, a, batch(1u << lo, zs, 0, zs), s);
@@ -831,12 +825,13 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
         // reads that tile from lostrange; a launch that returns at once costs
         // per workgroup)
         const uint32_t tiles = batch(std::min(t1 - t0, a.tl_max), zs, zs, 0);
-        hipEvent_t ev;
-        if (int rc = prof_begin(s, &ev, err)) return rc;
-        if (stamp_buf && stamp_prof == PROF_DEC_TILE_LAST) a.stamps = (uint64_t*)stamp_buf;
-        RS16_HIP(launch_tile_last(a, tiles, s));
-        a.stamps = nullptr;
-        if (int rc = prof_end(PROF_DEC_TILE_LAST, s, ev, err)) return rc;
+        if (int rc = profiled(PROF_DEC_TILE_LAST, s, err, [&](uint64_t* stamps) {
+                a.stamps = stamps;
+                const hipError_t e = launch_tile_last(a, tiles, s);
+                a.stamps = nullptr;
+                return e;
+            }))
+            return rc;
         if (diag & DIAG_TILE_LAST) return RS16_OK;  // (every span is tile_last's)
     }
     RS16_PASS(DEC_LAST, lo, a, batch(t1 - t0, zs, zs, 0), s);

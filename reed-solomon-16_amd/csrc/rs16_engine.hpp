@@ -195,6 +195,10 @@ struct rs16_engine {
              int prof = -1);
     int prof_begin(hipStream_t s, hipEvent_t* ev, rs16_error* err);
     int prof_end(int id, hipStream_t s, hipEvent_t ev, rs16_error* err);
+    // One kernel launch under profiling id `prof`: launch(stamps) returns the
+    // launch's hipError_t; stamps = stamp_buf when `prof` is the stamped id,
+    // else nullptr (rs16_engine.cpp).
+    template <class F> int profiled(int prof, hipStream_t s, rs16_error* err, F launch);
     bool profiling = false;
     // diagnostic timelines (rs16_engine_set_stamps): passes under profiling
     // id stamp_prof get stamp_buf (RS16_STAMPS builds record into it)

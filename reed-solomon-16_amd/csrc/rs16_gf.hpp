@@ -81,12 +81,13 @@ inline uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return a ^ b ^ c; }
 // Which twiddles are narrow: twiddle_narrow (rs16_internal.hpp).
 template <bool NARROW>
 RS16_HD void mul_xor_t(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const uint32_t* t) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(RS16_SHIFT32)
+#if defined(__HIP_DEVICE_COMPILE__)
     // The selectors of both dwords from two 64-bit shifts of the (L, H) pair
-    // instead of four 32-bit ones: the bits H shifts into L's top land where
-    // the byte masks clear them.  (As plain C the compiler narrows the shifts
-    // back to 32 bits.)  tools/ubench_bfly: 117.7 -> 114.0 cycles per
-    // wave-butterfly at 4 waves per SIMD (profiles/r06_ubench_bfly64.txt).
+    // instead of four 32-bit ones (the host's form below): the bits H shifts
+    // into L's top land where the byte masks clear them.  (As plain C the
+    // compiler narrows the shifts back to 32 bits.)  tools/ubench_bfly: 117.7
+    // -> 114.0 cycles per wave-butterfly at 4 waves per SIMD
+    // (profiles/r06_ubench_bfly64.txt; whole passes: profiles/r06_shift64_ab.txt).
     const uint64_t y = ((uint64_t)yH << 32) | yL;
     uint64_t a, b;
     asm("v_lshrrev_b64 %0, 3, %1" : "=v"(a) : "v"(y));

@@ -70,7 +70,7 @@ RS16_HD bool twiddle_narrow(uint32_t i) {
 // with b_high <= bh_max, skew delta `skew`): the first layer kb from which on
 // every twiddle the launch can form is narrow (T: none).  Layer kb's indices
 // are x - 1 with x = g + d + skew, d = 2^(lo+kb), g a multiple of 2d below
-// (bh_max + 1) 2^(lo+T) (TwiddleEntry, rs16_pass.hip).  The lowest set bit of
+// (bh_max + 1) 2^(lo+T) (TwiddleEntry, rs16_pass.hpp).  The lowest set bit of
 // x is that of (d + skew) mod 2d for every g, or at least 2d when that is 0,
 // so the layer is narrow when its largest x is below 2^8 times that bit.
 inline int first_narrow_layer(uint32_t lo, int T, uint32_t skew, uint32_t bh_max) {
@@ -330,11 +330,13 @@ constexpr size_t RS16_ZERO_BYTES = 65536;
 
 // Launch `num_tiles` tiles (x nslab slabs) of program P with tile bits T.
 hipError_t launch_pass(int prog, int T, const PassArgs& a, uint32_t num_tiles, hipStream_t s);
-// DEC_LAST at T = 8 as one wave per quad column of a tile (rs16_pass.hip
-// tile_last_kernel): `num_tiles` tiles (x stripes, PassArgs::stripe_tiles)
-// from a.tile_base, rows at lo = 0.
+// DEC_LAST at T = 8 as one wave per quad column of a tile (rs16_pass_small.hpp
+// tile_last_kernel): `num_tiles` tiles (x stripes, PassArgs::stripe_tiles),
+// rows at lo = 0, counted from the stripe's first lost tile (read from
+// a.lostrange on the device; a.tl_max must not be 0 then), or from
+// a.tile_base when a.lostrange is null.
 hipError_t launch_tile_last(const PassArgs& a, uint32_t num_tiles, hipStream_t s);
-// The general decode's middle pass as a direct product (rs16_pass.hip
+// The general decode's middle pass as a direct product (rs16_pass_small.hpp
 // mid_direct_kernel): U rows [need_lo, need_hi) of every tile column j from
 // the live Z rows and mtab (rs16_engine::mid_tables: 2^hi x 2^hi v_perm
 // tables of mid_matrix_entries, 80 bytes each, row-major), for `ns`

@@ -324,7 +324,7 @@ __global__ void __launch_bounds__(64) fwht_hi_mulw_kernel(ErasureSpec e, const u
 // and 8-15; the two commute): H_lo(e) from the flags, then H_hi . LW . H_hi,
 // then the last H_lo.  With last_lo == false the last H_lo is left to the
 // consumer: the 65536-row decode passes (256-row tiles = one H_lo block each)
-// finish it per tile in LDS (rs16_pass.hip), saving a kernel.
+// finish it per tile in LDS (rs16_pass.hpp), saving a kernel.
 // One-kernel eval_poly for block-aligned segments (eval_fused_ok): workgroup
 // j computes column j of H_lo(e) for all 256 blocks itself -- thread t reads
 // block t's 256 flag bytes (16 x 16-byte loads, L2-resident after the first

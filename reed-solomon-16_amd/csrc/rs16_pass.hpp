@@ -1,8 +1,12 @@
-// rs16_pass.hip -- the HBM-pass kernels of the MI355X GF(2^16) Reed-Solomon
-// engine: the FFT/IFFT butterflies of the reference `Engine`
+// rs16_pass.hpp -- the HBM-pass kernel template of the MI355X GF(2^16)
+// Reed-Solomon engine: the FFT/IFFT butterflies of the reference `Engine`
 // (src/engine/engine_nosimd.rs:190-384, spec src/engine/engine_naive.rs:43-124)
 // fused with the Rate-level steps around them (src/rate/rate_high.rs:44-83,
 // 168-247; src/rate/rate_low.rs:168-247).
+//
+// Included only by the units that instantiate pass_kernel<P, T, NV>
+// (rs16_pass_enc.hip, rs16_pass_dec.hip); launch_pass (rs16_pass_launch.hip)
+// reaches the kernels through their PassKernel lookups.
 //
 // Structure of one pass
 // ---------------------
@@ -61,19 +65,12 @@
 //   Batched stripes (PassArgs::stripe_tiles): one launch covers independent
 //   stripes of one geometry; a workgroup's tile index splits into (stripe,
 //   tile within the stripe) and the stripe displaces its array pointers.
-#include "rs16_internal.hpp"
+#pragma once
+#include "rs16_pass_common.hpp"
 #include "rs16_fwht.hpp"
-#include "rs16_colops.hpp"
 #include "rs16_diag.hpp"
 
 namespace rs16 {
-
-typedef const __attribute__((address_space(4))) uint32_t* cu32p;
-
-// (timing A/B builds: -DRS16_NO_EARLY_B=1 keeps the IFFT-only passes' stores after the last block)
-#ifndef RS16_NO_EARLY_B
-#define RS16_NO_EARLY_B 0
-#endif
 
 enum LoadMode { LD_PLAIN = 0, LD_GATHER_ENC, LD_GATHER_DEC, LD_DEC_LAST };
 enum StoreMode { ST_PLAIN = 0, ST_RECOVERY, ST_RESTORE };
@@ -105,15 +102,6 @@ RS16_PROG(DEC_HALF_LAST, LD_PLAIN, false, false, true, ST_RESTORE)
 RS16_PROG(DEC_HALF_SINGLE, LD_GATHER_DEC, true, false, true, ST_RESTORE)
 #undef RS16_PROG
 
-// Quads per tile row of the T = 7 passes (the encoder's first / last
-// passes and the identity decode's): 64 -- 8-wave workgroups, two per CU,
-// 512 items for a 32768-row stripe, each twiddle table staged once per 64
-// quad columns -- against 32 (4-wave workgroups, four per CU, 1024 items):
-// same-box A/B x 8, 805-815 -> 797-838 GiB/s, mean +1.5 %, 6 of 8 pairs
-// faster (profiles/r06_t7_q64_ab.txt).  (-DRS16_T7_Q=32: the old geometry.)
-#ifndef RS16_T7_Q
-#define RS16_T7_Q 64
-#endif
 // Row bits in registers: 4 (16 rows per thread) from T = 6 on; 3 at T = 5
 // (the passes of the n <= 2048 codecs, which are latency-bound: 8 rows per
 // thread and 16 quads per tile row give twice the waves, each with half the
@@ -123,9 +111,16 @@ template <int T> struct Geo {
     static constexpr int R = T > 4 ? (T == 5 ? 3 : 4) : T;  // row bits held in registers
     static constexpr int NR = 1 << R;                     // rows per thread (a row set)
     static constexpr int SETS = 1 << (T - R);             // row sets per tile
+    // Quads per tile row of the T = 7 passes (the encoder's first / last
+    // passes and the identity decode's): 64 -- 8-wave workgroups, two per CU,
+    // 512 items for a 32768-row stripe, each twiddle table staged once per 64
+    // quad columns -- against 32 (4-wave workgroups, four per CU, 1024 items):
+    // same-box A/B x 8, 805-815 -> 797-838 GiB/s, mean +1.5 %, 6 of 8 pairs
+    // faster (profiles/r06_t7_q64_ab.txt).
+    static constexpr int T7_Q = 64;
     // quads per tile row: 32 (two 16-row sets per wave) from T = 6 on, 16
     // (four 8-row sets per wave) at T = 5, 64 (one row set) below
-    static constexpr int Q = T > 4 ? (R == 3 ? 16 : (T == 7 ? RS16_T7_Q : 32)) : 64;
+    static constexpr int Q = T > 4 ? (R == 3 ? 16 : (T == 7 ? T7_Q : 32)) : 64;
     static constexpr int HWS = 64 / Q;                    // row sets per wave
     static constexpr int W = SETS / HWS > 0 ? SETS / HWS : 1;  // waves per workgroup
     static constexpr int SHB = T - R;                     // layout B: k = s + (m << SHB)
@@ -141,22 +136,17 @@ template <int P, int T, int QL> struct SmemL;
 // LDS instruction with all lanes) when the program's whole layout still lets
 // two workgroups share a CU (<= 80 KiB: the T = 7 encode passes, 64-quad
 // rows); else two rounds of Q / 2 quads (the T = 8 passes, the decoders' T =
-// 7 passes with their multiplier tables).
-#ifndef RS16_ONE_ROUND_MAX
-#define RS16_ONE_ROUND_MAX (80 * 1024)
-#endif
-// The encoder's two-direction pass at T = 8 (ENC_MID, also the identity
-// decode's middle pass): its one-round image (64 KiB) shares its LDS with
-// the layout-A twiddle tables, which are dead during both layout switches
-// (-DRS16_MID_SHARED=0: two rounds, tables beside the image).
-#ifndef RS16_MID_SHARED
-#define RS16_MID_SHARED 1
-#endif
-#ifndef RS16_DEC_MID_SHARED
-#define RS16_DEC_MID_SHARED 1
-#endif
+// 7 passes with their multiplier tables).  (One round for the T = 7 encode
+// passes against two: profiles/r06_t7_one_round_ab.txt.)
+constexpr int ONE_ROUND_MAX = 80 * 1024;
+// The two-direction middle passes at T = 8 (ENC_MID, also the identity
+// decode's middle pass, and DEC_MID): their one-round image (64 KiB) shares
+// its LDS with the layout-A twiddle tables, which are dead during both layout
+// switches (SmemL::SHARED).  Two rounds with the tables beside the image
+// measured slower for both: profiles/r06_mid_shared_ab.txt,
+// profiles/r06_dec_mid_shared_ab.txt.
 template <int P, int T> struct Rnd {
-    static constexpr int NQR = T >= 7 && SmemL<P, T, Geo<T>::Q>::BYTES > RS16_ONE_ROUND_MAX ? 2 : 1;
+    static constexpr int NQR = T >= 7 && SmemL<P, T, Geo<T>::Q>::BYTES > ONE_ROUND_MAX ? 2 : 1;
     static constexpr int QL = Geo<T>::Q / NQR;
 };
 
@@ -172,17 +162,18 @@ template <int P, int T, int QL> struct SmemL {
     using PT = ProgTraits<P>;
     static constexpr bool TWO = PT::IFFT && PT::FFT;
     static constexpr int IMG_BYTES = T > 4 ? (1 << T) * QL * 8 : 0;
-    // SHARED (ENC_MID at T = 8, one round): [image 64 KiB, holding the
-    // layout-A tables of each direction outside the switches][IFFT layout-B
-    // tables][FFT layout-B tables]
-    static constexpr bool SHARED = RS16_MID_SHARED && (P == ENC_MID || (P == DEC_MID && RS16_DEC_MID_SHARED)) && T == 8 && QL == Geo<T>::Q;
+    // SHARED (ENC_MID and DEC_MID at T = 8, one round): [image 64 KiB,
+    // holding the layout-A tables of each direction outside the switches]
+    // [IFFT layout-B tables][FFT layout-B tables]
+    static constexpr bool SHARED = (P == ENC_MID || P == DEC_MID) && T == 8 && QL == Geo<T>::Q;
     static constexpr int ERT_BYTES = PT::LOAD == LD_GATHER_DEC ? (1 << T) * 80 : 0;
     static constexpr int ERT_OFF = IMG_BYTES;
     static constexpr int TABB_OFF = IMG_BYTES;  // (SHARED: the IFFT's layout-B tables)
     static constexpr int TAB1_BYTES = SHARED ? 0 : Geo<T>::NTAB * 80;
-    // Restage (one-item build, T > 4): tab2 holds only the second
-    // direction's layout-B tables; its layout-A tables are written over the
-    // first direction's in tab1 at the first layout switch.
+    // Restage (two-direction programs, T > 4): tab2 holds only the second
+    // direction's layout-B tables; its layout-A tables are requested before
+    // the first layout switch and written over the first direction's (dead
+    // by then) in tab1 between its barriers.
     static constexpr bool RESTAGE = TWO && T > 4;
     static constexpr int TAB2_BYTES = TWO ? (RESTAGE ? Geo<T>::NTAB - Geo<T>::TSPLIT : Geo<T>::NTAB) * 80 : 0;
     static constexpr int RVT_BYTES = PT::STORE == ST_RESTORE ? (1 << T) * 80 : 0;
@@ -205,8 +196,6 @@ struct Thr {
     uint32_t b_low, b_high, offL;
     bool active;
 };
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
 template <int T, bool LB> __device__ __forceinline__ uint32_t kidx(const Thr& c, int m) {
     return LB ? c.s + ((uint32_t)m << Geo<T>::SHB) : (c.s << Geo<T>::R) + (uint32_t)m;
@@ -250,23 +239,6 @@ __device__ __forceinline__ bool row_below(uint32_t ur, uint32_t lr, uint32_t lim
     return ur < lim && lr < lim - ur;
 }
 
-// The last pass's lost-original tiles (2^T rows each) span at most tl_max
-// tiles: tile_last_kernel is the last pass of the stripe (else DEC_LAST).
-template <int T> __device__ __forceinline__ bool tl_covers(const PassArgs& a) {
-    const uint32_t r0 = ((cu32p)a.lostrange)[0], r1 = ((cu32p)a.lostrange)[1];
-    return r0 < r1 && ((r1 - 1) >> T) - (r0 >> T) < a.tl_max;
-}
-
-// The consumed U rows [nlo, nhi) of the general decode's middle pass, when
-// at most MID_DIRECT_MAX (mid_direct_kernel: the direct product).
-__device__ __forceinline__ bool mid_need(const PassArgs& a, uint32_t& nlo, uint32_t& nhi) {
-    const uint32_t r0 = ((cu32p)a.lostrange)[0], r1 = ((cu32p)a.lostrange)[1];
-    if (r0 >= r1) return false;
-    nlo = max(a.need_lo, r0 >> a.lo);
-    nhi = min(a.need_hi, ((r1 - 1) >> a.lo) + 1);
-    return nhi > nlo && nhi - nlo <= MID_DIRECT_MAX;
-}
-
 // Priority schedule: a wave lowers its issue priority (s_setprio 3 -> 0) as
 // its item progresses, so that waves that are behind win the arbitration.
 // Hardware age order alone lets the oldest workgroup of a CU run ahead and
@@ -274,38 +246,22 @@ __device__ __forceinline__ bool mid_need(const PassArgs& a, uint32_t& nlo, uint3
 // spread of workgroup end times).  Measured (bench, 2 runs each): this
 // schedule 620 / 614 GiB/s; on the two-direction passes only 611 / 611; a
 // later schedule 607; none 595 / 594.
-// At point `at` of program P's item (0 staged, 1 first layout-A layers done,
+// At point `at` of an item (0 staged, 1 first layout-A layers done,
 // 2 first direction done, 3 layout-B FFT done, 4 last switch done, 5 stores).
 // (A static pair schedule -- slots 0-1 at priority 3 for the whole item,
 // slots 2-3 at 0 -- measured no better on the T = 7 passes and 3.5 us worse
 // on the T = 8 ones, same-box A/B x 3, round 4.  Round 6, two workgroups per
 // CU everywhere: without the schedule, or with a static bias for the younger
 // workgroup, ENC_MID runs 2-3 us slower: profiles/r06_prio_schedules_rejected.txt.)
-template <int P, int at, int T = 7> __device__ __forceinline__ void prio() {
+template <int at> __device__ __forceinline__ void prio() {
     constexpr int v[6] = {3, 2, -1, 1, -1, 0};
     if constexpr (v[at] >= 0) __builtin_amdgcn_s_setprio(v[at]);
 }
 
-
-// s_waitcnt immediate (gfx9 encoding) that waits for vmcnt <= n only
-// (expcnt and lgkmcnt at their maxima, i.e. not waited for).
-__host__ __device__ constexpr int vmcnt_wait(int n) { return (n & 15) | ((n >> 4) << 14) | (7 << 4) | (15 << 8); }
-
-// Row loads / stores at an address that includes the lane's offset.
-__device__ __forceinline__ void ld_ptr(const PassArgs& a, const gbyte* p, bool ok, uint32_t& L, uint32_t& H) {
-    (void)a;
-    L = H = 0;
-    if (ok) {
-        // (global address space from the SGPR base on: base + 32-bit lane
-        // offset selects the SGPR-base form of global_load)
-        const gu32* g = (const gu32*)p;
-        L = g[0];
-        H = g[8];
-    }
-}
-template <bool NT>
-__device__ __forceinline__ void st_ptr(const PassArgs& a, gbyte* p, bool ok, uint32_t L, uint32_t H) {
-    (void)a;
+// Row stores / loads at an address that includes the lane's offset (global
+// address space from the SGPR base on: base + 32-bit lane offset selects the
+// SGPR-base form of global_load / global_store).
+template <bool NT> __device__ __forceinline__ void st_ptr(gbyte* p, bool ok, uint32_t L, uint32_t H) {
     if (ok) {
         gu32* g = (gu32*)p;
         if constexpr (NT) {
@@ -341,17 +297,6 @@ template <> struct LaneOff<false> {
     __device__ __forceinline__ LaneOff(uint32_t lr, uint64_t S, uint32_t offL) : v((uint64_t)lr * S + offL) {}
     template <class B> __device__ __forceinline__ B* at(B* base) const { return base + v; }
 };
-
-__device__ __forceinline__ void load_table_lds(uint32_t (&t)[20], const uint4* p) {
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        const uint4 v = p[i];
-        t[4 * i] = v.x;
-        t[4 * i + 1] = v.y;
-        t[4 * i + 2] = v.z;
-        t[4 * i + 3] = v.w;
-    }
-}
 
 // ---------------------------------------------------------------------------
 // Table staging.  N tables of 5 x 16 B, table i taken from mul_tab entry
@@ -405,36 +350,15 @@ template <int T> struct TwiddleEntry {
     }
 };
 
-// Received?  Rows [0, a_count) are segment A, [chunk, chunk + b_count)
-// segment B; anything else is an absent (zero) row.
-__device__ __forceinline__ bool row_received(const PassArgs& a, uint32_t r) {
-    if (r < a.a_count) return !a.flags_a || a.flags_a[r];
-    if (r >= a.chunk && r - a.chunk < a.b_count) return !a.flags_b || a.flags_b[r - a.chunk];
-    return false;
-}
-// Lost original?  (the rows the decoder reveals)
-__device__ __forceinline__ bool row_lost_original(const PassArgs& a, uint32_t r) {
-    const uint32_t base = a.rest_seg_b ? a.chunk : 0;
-    const uint32_t cnt = a.rest_seg_b ? a.b_count : a.a_count;
-    const uint8_t* fl = a.rest_seg_b ? a.flags_b : a.flags_a;
-    return r >= base && r - base < cnt && fl && !fl[r - base];
-}
-
-// "MULTIPLY SHARDS" of rate_high.rs:203-228 / rate_low.rs:203-228: received
-// row r is multiplied by erasure log e[r]; absent rows by zero.
-// e[r]: from the tile's LDS copy when the pass finished eval_poly itself
-// (el = the tile's 2^T logs), else from HBM.
 // Decoder rows: pass row r is decode work row r + row_base_in (gather side)
 // or r + row_base_out (reveal side) -- non-zero in the half-transform decode.
-template <int T> struct GatherEntry {
-    const PassArgs& a;
-    const Thr& c;
-    const uint32_t* el;
-    __device__ __forceinline__ uint32_t operator()(int k) const {
-        const uint32_t r = row_rel<T>(c, a, (uint32_t)k) + a.row_base_in;
-        return row_received(a, r) ? (el ? el[k] : a.elog[r]) : ZERO_ENTRY;
-    }
-};
+// Rows [0, a_count) are segment A, [chunk, chunk + b_count) segment B, anything
+// else an absent (zero) row; which rows were received: the bitmap a.rbits.
+// The erasure log e[r] of a row comes from the tile's LDS copy when the pass
+// finished eval_poly itself (el = the tile's 2^T logs), else from HBM.
+// "MULTIPLY SHARDS" (rate_high.rs:203-228 / rate_low.rs:203-228: received row
+// r x e[r], absent rows x 0) is staged by TileStage::gather.
+//
 // REVEAL ERASURES (rate_high.rs:236-242 / rate_low.rs:236-242): lost
 // original row r -> work[r] * (GF_MODULUS - e[r]).
 template <int T> struct RevealEntry {
@@ -447,23 +371,6 @@ template <int T> struct RevealEntry {
     }
 };
 
-// The last 256-point FWHT of eval_poly (src/engine.rs:207-218; row bits 0-7,
-// add/sub mod 65535 as NoSimd::fwht_private, src/engine/engine_nosimd.rs:153-183)
-// over the 256-row block of a tile's rows in LDS; every thread of the
-// workgroup (NT of them) calls it.
-template <int NT> __device__ __forceinline__ void fwht256_tile(uint32_t* s) {
-#pragma unroll
-    for (uint32_t d = 1; d < 256; d <<= 1) {
-        __syncthreads();
-        for (uint32_t t = threadIdx.x; t < 128; t += NT) {
-            const uint32_t i = (t / d) * 2 * d + (t % d), j = i + d;
-            const uint32_t x = s[i], y = s[j];
-            s[i] = add_mod(x, y);
-            s[j] = sub_mod(x, y);
-        }
-    }
-    __syncthreads();
-}
 // Layers for k-bits [KB0, KB1) held in registers of layout LB, as a
 // compile-time sequence of twiddle groups (step s, index gi).
 // No per-group action (GroupLoop's default).
@@ -568,7 +475,7 @@ enum { PR_NONE = 0, PR_OUT, PR_ZERO };
 //      stripe: IFFT at skew 2^15, FFT at skew 0)
 //   3  all but the FFT's layer 0 (the identity decode's middle pass: the
 //      same with the directions swapped)
-constexpr int NARROW_VARIANTS = 4;
+// (NARROW_VARIANTS = 4 of them, rs16_pass_common.hpp)
 template <int NV> struct NarrowVar {
     static constexpr int NONE = 99;
     static constexpr int IFFT_FROM = NV == 0 ? NONE : (NV == 2 ? 1 : 0);
@@ -657,15 +564,11 @@ struct GroupLoop {
 // compile-time constants; left to the compiler, each ds_read gets its own
 // s_add + v_mov to build the address (150 VALU moves per ENC_MID item).
 // Through one opaque VGPR base the constant part folds into the ds_read
-// offset field instead.
+// offset field instead.  (Against the plain pointer: profiles/r06_lds_vbase_ab.txt.)
 __device__ __forceinline__ const uint4* lds_vgpr(const uint4* p) {
-#ifndef RS16_NO_LDS_VBASE
     uint32_t v = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint4*)p;
     asm volatile("" : "+v"(v));
     return (const uint4*)(const __attribute__((address_space(3))) uint4*)(uintptr_t)v;
-#else
-    return p;
-#endif
 }
 
 // Apply the layers for k-bits [KB0, KB1) held in registers of layout LB.
@@ -875,14 +778,6 @@ __device__ __forceinline__ void fd_image(uint32_t& dl, uint32_t& dh, const Thr& 
     }
 }
 
-// Two-direction programs of the one-item build (Smem::RESTAGE): the second
-// direction's layout-A tables are requested before the first layout switch
-// and written over the first direction's layout-A tables (dead by then) in
-// tab1 between its barriers.
-template <int P, int T> struct LateS2 {
-    static constexpr bool value = Smem<P, T>::RESTAGE;
-};
-
 // y = x + (in-tile formal derivative part) of the rows in registers, where
 // the LDS image is filled from (SL, SH) -- the rows themselves for the
 // (I + H) step of DEC_MID, z for DEC_LAST's y = u + L(z).  In rounds; with
@@ -936,7 +831,7 @@ __device__ __forceinline__ void set_item(Thr& c, const PassArgs& a, uint32_t ite
     c.offL = (Qg >> 3) * 64 + (Qg & 7) * 4;
 }
 
-// The one-item build's row loads of an item: row address = SGPR base of the
+// The row loads of an item: row address = SGPR base of the
 // wave's row (one scalar multiply-add per row) + the lane's offset.
 template <int P, int T, bool V32>
 __device__ __forceinline__ void load_rows(const PassArgs& a, const Thr& c, uint32_t tile, ItemRegs<P, T>& d) {
@@ -997,7 +892,7 @@ __device__ __forceinline__ void load_rows(const PassArgs& a, const Thr& c, uint3
             ld_sel(a, p, c.active & ((bits >> m) & 1u), c.offL, d.L[m], d.H[m]);
         }
     } else {  // LD_DEC_LAST: u in registers, z for y = u + L(z)
-        d.ztile = a.zflags && ((((cu32p)a.zflags)[tile >> 2] >> (8 * (tile & 3))) & 1u);
+        d.ztile = a.zflags && tile_is_zero(a, tile);
         const LaneOff<V32> lo(lr, a.S_in, c.offL);
 #pragma unroll
         for (int m = 0; m < NR; m++) {
@@ -1083,9 +978,7 @@ template <int P, int T> struct RevealStage {
             lost[i] = k < (1u << T) && row_lost_original(a, row_rel<T>(c, a, k) + a.row_base_out);
         }
     }
-    __device__ __forceinline__ void commit(const PassArgs& a, const Thr& c, uint8_t* smem) const {
-        (void)a;
-        (void)c;
+    __device__ __forceinline__ void commit(uint8_t* smem) const {
         uint32_t* lostf = (uint32_t*)(smem + SM::LOST_OFF);
 #pragma unroll
         for (int i = 0; i < (int)(sizeof lost / sizeof lost[0]); i++) {
@@ -1101,7 +994,7 @@ template <int P, int T> struct TileStage {
     using SM = Smem<P, T>;
     using G = Geo<T>;
     // second direction at the start: all of it, or only its layout-B tables
-    static constexpr int N2 = !SM::TWO ? 0 : (LateS2<P, T>::value ? G::NTAB - G::TSPLIT : G::NTAB);
+    static constexpr int N2 = !SM::TWO ? 0 : (SM::RESTAGE ? G::NTAB - G::TSPLIT : G::NTAB);
     static constexpr bool S2 = N2 > 0;
     // (SHARED: the first direction's layout-A tables into the image region,
     // its layout-B tables beside it)
@@ -1166,7 +1059,8 @@ template <int P, int T> struct TileStage {
             }
         }
         if constexpr (PT::LOAD == LD_GATHER_DEC) {
-            // "MULTIPLY SHARDS" tables (GatherEntry, with the received bit from rw)
+            // "MULTIPLY SHARDS" tables (received row r x e[r], absent rows x 0;
+            // the received bit from rw)
             static_assert(PER_E == Stager<T, (1 << T)>::PER, "one table chunk per (thread, i)");
             const u32x4* tab = (const u32x4*)a.mul_tab;
             // (two uniform paths: with the logs in LDS every table load issues
@@ -1194,7 +1088,7 @@ template <int P, int T> struct TileStage {
         if constexpr (PT::STORE == ST_RESTORE && !LateReveal<P, T>::value) {
             RevealStage<P, T> rs;
             rs.issue(a, c, el);
-            rs.commit(a, c, smem);
+            rs.commit(smem);
         }
         if constexpr (S2) s2.commit((uint4*)(smem + SM::TAB2_OFF));
         s1.commit((uint4*)(smem + SM::TAB1_OFF));
@@ -1239,10 +1133,7 @@ template <int P, int T> struct RcvCount {
     }
 };
 
-// Compute and store one item whose rows are in d (every thread of the
-// workgroup calls it for the same item).
-// The one-item build's store of row register m of an item (the counterpart
-// of load_rows): recovery / work rows as they are, lost originals revealed
+// The store of row register m of an item (the counterpart of load_rows): recovery / work rows as they are, lost originals revealed
 // (x (65535 - e), rate_high.rs:236-242) into the caller's original array.
 template <int P, int T, bool V32>
 __device__ __forceinline__ void store_row(const PassArgs& a, const Thr& cs, uint32_t L, uint32_t H, int m,
@@ -1256,11 +1147,11 @@ __device__ __forceinline__ void store_row(const PassArgs& a, const Thr& cs, uint
     if constexpr (PT::STORE == ST_PLAIN) {
         const LaneOff<V32> lo(lr, a.S_out, cs.offL);
         const uint32_t k = kidx<T, END_B>(cs, m);
-        st_ptr<NT>(a, lo.at(sgpr_ptr(a.out + (uint64_t)ur * a.S_out)),
+        st_ptr<NT>(lo.at(sgpr_ptr(a.out + (uint64_t)ur * a.S_out)),
                    cs.active & (P != DEC_MID || (k >= a.need_lo && k < a.need_hi)), L, H);
     } else if constexpr (PT::STORE == ST_RECOVERY) {
         const LaneOff<V32> lo(lr, a.S_out, cs.offL);
-        st_ptr<NT>(a, lo.at(sgpr_ptr(a.out + (uint64_t)ur * a.S_out)), cs.active & row_below(ur, lr, a.out_rows), L, H);
+        st_ptr<NT>(lo.at(sgpr_ptr(a.out + (uint64_t)ur * a.S_out)), cs.active & row_below(ur, lr, a.out_rows), L, H);
     } else {
         // lost original row r -> restored-originals row r + row_base_out - (segment start)
         const LaneOff<V32> lo(lr, a.S_rest, cs.offL);
@@ -1274,7 +1165,7 @@ __device__ __forceinline__ void store_row(const PassArgs& a, const Thr& cs, uint
             load_table_lds(tt, rvt + k * 5);
             uint32_t ol = 0, oh = 0;
             mul_xor(ol, oh, L, H, tt);
-            st_ptr<NT>(a, lo.at(sgpr_ptr(a.rest + ((int64_t)ur + shift) * (int64_t)a.S_rest)), true, ol, oh);
+            st_ptr<NT>(lo.at(sgpr_ptr(a.rest + ((int64_t)ur + shift) * (int64_t)a.S_rest)), true, ol, oh);
         }
     }
 }
@@ -1384,9 +1275,11 @@ template <int P, int T> struct EvenStore {
     }
 };
 
+// Compute and store one item whose rows are in d (every thread of the
+// workgroup calls it for the same item).
 template <int P, int T, int NV>
-__device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, uint32_t tile, uint32_t slab,
-                                             ItemRegs<P, T>& d, uint8_t* smem) {
+__device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, uint32_t tile, ItemRegs<P, T>& d,
+                                             uint8_t* smem) {
     using PT = ProgTraits<P>;
     constexpr int NKI = NarrowVar<NV>::IFFT_FROM, NKF = NarrowVar<NV>::FFT_FROM;
     static_assert(NV == 0 || (PT::IFFT && PT::FFT && T > 4), "narrow variants: two-direction passes only");
@@ -1398,12 +1291,13 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
     constexpr bool TWO = SM::TWO;
     // (DEC_MID runs with T >= 5 only; the 16-row-block pruning needs R = 4)
     constexpr bool ZERO_SKIP = P == DEC_MID && T > 4 && G::R == 4;
-    // stores inside the last FFT block (one-item build, 16 rows per lane, not
-    // the output-pruned DEC_MID; the reveal stores measured slower inside it)
+    // stores inside the last FFT block (16 rows per lane, not the
+    // output-pruned DEC_MID; the reveal stores measured slower inside it)
     constexpr bool EARLY = LayerSeq<T, false, 0, R, true>::DF && P != DEC_MID && PT::STORE != ST_RESTORE && PT::FFT &&
                            T > 4;
-    // the IFFT-only passes: early stores of the even rows (ifft_b_halves)
-    constexpr bool EARLY_B = PT::IFFT && !PT::FFT && PT::STORE == ST_PLAIN && T > 4 && G::R == 4 && !RS16_NO_EARLY_B;
+    // the IFFT-only passes: early stores of the even rows (ifft_b_halves;
+    // against all stores after the last block: profiles/r05_early_b_ab.txt)
+    constexpr bool EARLY_B = PT::IFFT && !PT::FFT && PT::STORE == ST_PLAIN && T > 4 && G::R == 4;
     uint2* lds = (uint2*)smem;
     const uint4* tab1 = (const uint4*)(smem + SM::TAB1_OFF);
     const uint4* tab2 = (const uint4*)(smem + SM::TAB2_OFF);
@@ -1437,7 +1331,9 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
     if constexpr (P == DEC_FIRST) {
         // A tile without received rows is zero after the erasure multiply
         // and through the IFFT: DEC_MID / DEC_LAST read it as zero, skip it.
-        if (a.zflags && ((((cu32p)a.zflags)[tile >> 2] >> (8 * (tile & 3))) & 1u)) {
+        // (pass_kernel has returned for such a tile already; the recheck
+        // stays because removing it changes the kernels' machine code)
+        if (a.zflags && tile_is_zero(a, tile)) {
             __builtin_amdgcn_s_waitcnt(vmcnt_wait(0));  // (see the end of this function)
             return;
         }
@@ -1467,9 +1363,10 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
         if constexpr (ZERO_SKIP) skip_a = __all(d.zrow == (1u << NR) - 1);
         if (!skip_a) layers<P, T, NKI, false, 0, R, false, false>(L, H, c, a, tab1, tab2);
         RS16_STAMP(a, 3);
-        prio<P, 1, T>();
+        prio<1>();
         if constexpr (T > 4) {
-            constexpr bool LS2 = LateS2<P, T>::value && !SM::SHARED;
+            // the second direction's layout-A tables (Smem::RESTAGE)
+            constexpr bool LS2 = SM::RESTAGE && !SM::SHARED;
             Stager<T, (LS2 ? G::TSPLIT : 0)> s3;
             if constexpr (LS2) s3.issue(a.skew_tab, TwiddleEntry<T>{a, c, 0, a.skew_fft});
             // (SHARED: the image overwrites the layout-A tables -- every wave
@@ -1505,7 +1402,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
             in_b = true;
         }
         RS16_STAMP(a, 5);
-        prio<P, 2, T>();
+        prio<2>();
     }
     // ---------------- formal derivative (tile bits) ----------------
     if constexpr (PT::FD) {
@@ -1536,7 +1433,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
                 }
             }
             RS16_STAMP(a, 7);
-            prio<P, 3, T>();
+            prio<3>();
             // reveal multipliers: requested before the last layout switch,
             // written to LDS between its barriers (read after the layers)
             RevealStage<P, (LateReveal<P, T>::value ? T : 0)> rs;
@@ -1553,7 +1450,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
                 else exchange<T, NQR, true>(L, H, c, lds);
             } else {
                 exchange<T, NQR, true>(L, H, c, lds, [&]() {
-                    if constexpr (LateReveal<P, T>::value) rs.commit(a, c, smem);
+                    if constexpr (LateReveal<P, T>::value) rs.commit(smem);
                 });
             }
             if constexpr (SM::SHARED) {
@@ -1567,23 +1464,22 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
                 __syncthreads();
             }
             RS16_STAMP(a, 8);
-            prio<P, 4, T>();
+            prio<4>();
             in_b = false;
         }
         bool need = true;
         if constexpr (P == DEC_MID) need = (c.s << R) < a.need_hi && ((c.s + 1) << R) > a.need_lo;
-#ifndef RS16_NO_RESTORE_SKIP
         if constexpr (PT::STORE == ST_RESTORE && T > 4) {
             // a row set without a lost original stores nothing: its
             // layout-A FFT layers are skipped (a wave whose two row sets
             // both have none skips them -- most waves of a decode that lost
-            // few, scattered originals)
+            // few, scattered originals; against running them always:
+            // profiles/r06_restore_skip_ab.txt)
             uint32_t any = 0;
 #pragma unroll
             for (int m = 0; m < NR; m++) any |= lostf[kidx<T, false>(c, m)];
             need = any != 0;
         }
-#endif
         // second direction's layout-A tables: restaged into tab1 (T > 4), else in tab2
         if constexpr (EARLY) {
             Thr cs = c;
@@ -1601,7 +1497,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
         return;
     }
 
-    prio<P, 5, T>();
+    prio<5>();
     // ---------------- store ----------------
     // The next item's loads were issued before this item's butterflies and
     // have landed by now: retire them before the stores, so that the stores
@@ -1657,21 +1553,7 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, ((P == DEC_SINGLE || P == DEC
         const uint32_t st = uni(tile / a.stripe_tiles);
         first_stripe = st == 0;
         tile -= st * a.stripe_tiles;
-        a.in += st * a.bs_in;
-        a.in2 += st * a.bs_in2;
-        a.out += st * a.bs_out;
-        a.seg_a += st * a.bs_seg;
-        a.seg_b += st * a.bs_seg_b;
-        a.rest += st * a.bs_rest;
-        // stripes with losses of their own: their flags and decode metadata
-        // (all strides 0 when the stripes share one erasure pattern)
-        if (a.flags_a) a.flags_a += st * a.bs_fa;
-        if (a.flags_b) a.flags_b += st * a.bs_fb;
-        if (a.elog) a.elog += st * a.bs_elog;
-        if (a.ework) a.ework += st * a.bs_elog;
-        if (a.rbits) a.rbits += st * a.bs_rbits;
-        if (a.zflags) a.zflags += st * a.bs_zflags;
-        if (a.lostrange) a.lostrange += st * a.bs_lost;
+        stripe_displace(a, st);
     }
     tile += a.tile_base;
     c.b_low = tile & ((1u << a.lo) - 1);
@@ -1681,7 +1563,7 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, ((P == DEC_SINGLE || P == DEC
     if constexpr (P == DEC_FIRST) {
         // a tile without received rows is skipped (process_item): return
         // before its table staging and row loads, so its slot frees at once
-        if (a.zflags && ((((cu32p)a.zflags)[tile >> 2] >> (8 * (tile & 3))) & 1u)) return;
+        if (a.zflags && tile_is_zero(a, tile)) return;
     }
     if constexpr (P == DEC_MID) {
         // mid_direct_kernel computed this stripe's consumed rows already
@@ -1692,14 +1574,15 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, ((P == DEC_SINGLE || P == DEC
         // A tile without a lost original stores nothing: return before any
         // load (the decode's lost rows are [lostrange[0], lostrange[1])).
         if (a.lostrange) {
+            // (lost_range written out: read through the helper, in any shape
+            // tried, this test compiles to other machine code)
             const uint32_t r0 = ((cu32p)a.lostrange)[0], r1 = ((cu32p)a.lostrange)[1];
             if (!((tile << T) < r1 && ((tile + 1) << T) > r0)) return;
             // (tile_last_kernel took this stripe's few tiles)
             if (a.tl_max && tl_covers<T>(a)) return;
         }
     }
-    // one item per workgroup (launch_pass sets per_wg = 1): straight-line code
-    // (a loop lets the compiler hoist per-row address terms out of it, which
+    // One item per workgroup, as straight-line code (a loop over items lets the compiler hoist per-row address terms out of it, which
     // costs more VGPRs than the 128 of four waves per SIMD).  The twiddle
     // tables are requested first, the tile's rows right behind them, so the
     // staging latency hides under the row loads.
@@ -1707,7 +1590,7 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, ((P == DEC_SINGLE || P == DEC
     // Load-issue order: the workgroup in slot 0 of its CU (HW_ID.tg_id) issues
     // its rows first, slot 1 next, ...  Same-box A/B: kernel times equal,
     // step time -2 % (643-645 -> 654-659 GiB/s, 3 pairs).  The progress-based
-    // schedule (prio<P, at>) takes over once the tables are staged.
+    // schedule (prio<at>) takes over once the tables are staged.
     if constexpr (T >= 7) {
         const uint32_t slot = (__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 16) & 15u;
         if (slot == 0) __builtin_amdgcn_s_setprio(3);
@@ -1730,446 +1613,41 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, ((P == DEC_SINGLE || P == DEC
         // Only the last pass's tiles that hold a lost original are consumed:
         // tile row k = rows [k << lo, (k + 1) << lo) (read with the rows in flight)
         if (a.lostrange) {
-            const uint32_t r0 = ((cu32p)a.lostrange)[0], r1 = ((cu32p)a.lostrange)[1];
+            uint32_t r0, r1;
+            lost_range(a, r0, r1);
             const bool any = r0 < r1;
             a.need_lo = max(a.need_lo, any ? r0 >> a.lo : 0u);
             a.need_hi = min(a.need_hi, any ? ((r1 - 1) >> a.lo) + 1 : 0u);
         }
     }
     RS16_STAMP(a, 1);
-    prio<P, 0, T>();
+    prio<0>();
     st.template finish<EARLY>(a, c, smem);
     rcn.count();
     RS16_STAMP(a, 2);
-    process_item<P, T, NV>(a, c, tile, slab, cur, smem);
+    process_item<P, T, NV>(a, c, tile, cur, smem);
     rcn.store(a, c);
 }
 
 // ---------------------------------------------------------------------------
-// The general decode's last pass (DEC_LAST: y = u + L(z) -> FFT of the tile's
-// 8 low row bits -> reveal x (65535 - e) -> store the lost originals,
-// rate_high.rs:232-242 / rate_low.rs:232-242) as one wave per quad column of
-// a 256-row tile instead of one 8-wave workgroup per (tile, 32-quad slab):
-// lane l holds 4 rows of its quad column, the FFT runs in 4 radix-4 blocks
-// in registers with in-wave row-bit exchanges (colops, as the column codec
-// at 256 rows), the in-tile formal-derivative terms come from registers and
-// lane shuffles (no LDS image, no barrier).  Four quad columns per
-// workgroup share the tile's 255 twiddle tables (staged by LDS-DMA once) and
-// the tile's erasure logs.  A decode that lost few originals needs this pass
-// for a handful of tiles only (lost-range pruning): there the 8-wave item's
-// latency (two waves per SIMD through 8 layers of 16 rows) was the whole
-// pass, 25 us for the reference bench's 1 % loss; here each wave carries a
-// quarter of the rows.
+// What an instantiation unit builds its PassKernel lookup from: taking a
+// kernel's address here is what instantiates it in that unit.
 // ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) tile_last_kernel(PassArgs a) {
-    using namespace colops;
-    constexpr int T = 8;
-    constexpr uint32_t NTAB = (1u << T) - 1;
-    __shared__ __attribute__((aligned(16))) uint8_t tabs[NTAB * 80];
-    __shared__ uint32_t elds[256];
-    const uint32_t t = threadIdx.x, lane = t & 63, w = uni(t >> 6);
-    const uint32_t nq4 = (a.qrow + 3) / 4;
-    uint32_t tile = blockIdx.x / nq4;
-    const uint32_t qg = blockIdx.x - tile * nq4;
-    if (a.stripe_tiles) {
-        const uint32_t st = uni(tile / a.stripe_tiles);
-        tile -= st * a.stripe_tiles;
-        a.in += st * a.bs_in;
-        a.in2 += st * a.bs_in2;
-        a.rest += st * a.bs_rest;
-        if (a.flags_a) a.flags_a += st * a.bs_fa;
-        if (a.flags_b) a.flags_b += st * a.bs_fb;
-        if (a.elog) a.elog += st * a.bs_elog;
-        if (a.ework) a.ework += st * a.bs_elog;
-        if (a.zflags) a.zflags += st * a.bs_zflags;
-        if (a.lostrange) a.lostrange += st * a.bs_lost;
-    }
-    if (a.lostrange) {
-        // The grid covers min(tiles, tl_max) tiles per stripe, counted from
-        // the first one with a lost original; lost originals over more than
-        // tl_max tiles are DEC_LAST's (its 8-wave items win there:
-        // scripts/probe_general.py, break-even 16-32 tiles), and a tile past
-        // the last lost original stores nothing.
-        const uint32_t r0 = ((cu32p)a.lostrange)[0], r1 = ((cu32p)a.lostrange)[1];
-        if (!tl_covers<T>(a)) return;
-        tile += r0 >> T;
-        if (tile > ((r1 - 1) >> T)) return;
-    } else {
-        tile += a.tile_base;
-    }
-    RS16_STAMP(a, 0);
-    const uint32_t q = qg * 4 + w;
-    const bool active = q < a.qrow;
-    const uint32_t offL = (q >> 3) * 64 + (q & 7) * 4;
-    const bool ztile = a.zflags && ((((cu32p)a.zflags)[tile >> 2] >> (8 * (tile & 3))) & 1u);
-    // ---- requests: z and u of the lane's rows in the first FFT block's
-    // layout (row bits 6, 7 in registers: row k = lane + 64 m), the tile's
-    // erasure-log block (wave 0, when eval_poly left its last H_lo to this
-    // pass), then the twiddle tables by LDS-DMA
-    uint32_t ZL[4], ZH[4], YL[4], YH[4];
-    const uint8_t* zpage = a.zero + (offL & 0x7FFFu);
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-        const uint64_t r = ((uint64_t)tile << T) + lane + 64u * m;
-        const uint32_t* pz = (const uint32_t*)(active && !ztile ? a.in + r * a.S_in + offL : zpage);
-        const uint32_t* pu = (const uint32_t*)(active ? a.in2 + r * a.S_in + offL : zpage);
-        ZL[m] = pz[0];
-        ZH[m] = pz[8];
-        YL[m] = pu[0];
-        YH[m] = pu[8];
-    }
-    const uint32_t row0 = (tile << T) + a.row_base_out;  // the tile's first decode work row
-    uint32_t ev[4] = {0, 0, 0, 0};
-    if (a.ework && w == 0) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) ev[j] = a.ework[(row0 & ~255u) + lane + 64u * j];
-    }
-#pragma unroll
-    for (uint32_t i = 0; i * 256 < NTAB * 5; i++) {
-        const uint32_t c = i * 256 + t;
-        if (c < NTAB * 5) {
-            // chunk c = part c % 5 of table tb = c / 5 (tile-group order: layer
-            // kb at groups [2^T - 2^(T-kb), ...), group j = row >> (kb + 1))
-            const uint32_t tb = c / 5, part = c - tb * 5;
-            const uint32_t kb = (uint32_t)(T - 32 + __clz(NTAB - tb));
-            const uint32_t j = tb - ((1u << T) - (1u << (T - kb)));
-            const uint32_t idx = (tile << T) + (j << (kb + 1)) + (1u << kb) + a.skew_fft - 1;
-            __builtin_amdgcn_global_load_lds((colops::glb_vp)(a.skew_tab + (size_t)idx * TAB_DWORDS + part * 4),
-                                             (colops::lds_vp)(tabs + (i * 256 + 64 * w) * 16), 16, 0, 0);
-        }
-    }
-    RS16_STAMP(a, 1);
-    __builtin_amdgcn_s_waitcnt(0);
-    if (a.ework && w == 0) {
-        fwht256_wave(ev);  // the last 256-point FWHT of eval_poly (src/engine.rs:207-218)
-#pragma unroll
-        for (int j = 0; j < 4; j++) elds[lane + 64 * j] = ev[j];
-    }
-    __syncthreads();  // tables and logs in LDS
-    RS16_STAMP(a, 2);
-    // ---- reveal multipliers of the lane's output rows (the last block's
-    // layout: row k = 4 lane + m), requested now, used after the FFT
-    uint32_t rt[4][20];
-    bool lost[4];
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-        const uint32_t r = row0 + 4 * lane + m;
-        lost[m] = active && row_lost_original(a, r);
-        const uint32_t e = a.ework ? elds[(4 * lane + m + row0) & 255u] : (lost[m] ? a.elog[r] : 0u);
-        glb_table(rt[m], a.mul_tab, lost[m] ? GF_MODULUS - e : ZERO_ENTRY);
-    }
-    // ---- y = u + L(z): the formal derivative's terms of the tile's row bits
-    // (src/engine.rs:233-238 in closed form): y[k] ^= z[k | 2^b] for every
-    // bit b < 8 that is 0 in k -- bits 6, 7 are register bits, 0-5 lane bits
-    if (!ztile) {
-#pragma unroll
-        for (int m = 0; m < 4; m++) {
-            if (!(m & 1)) YL[m] ^= ZL[m | 1], YH[m] ^= ZH[m | 1];
-            if (!(m & 2)) YL[m] ^= ZL[m | 2], YH[m] ^= ZH[m | 2];
-        }
-#define RS16_FDL(B)                                                                   \
-        {                                                                             \
-            const bool take = !(lane & (1u << (B)));                                  \
-            _Pragma("unroll") for (int m = 0; m < 4; m++) {                           \
-                const uint32_t pl = (uint32_t)xshfl<(1 << (B))>((int)ZL[m]);          \
-                const uint32_t ph = (uint32_t)xshfl<(1 << (B))>((int)ZH[m]);          \
-                YL[m] ^= take ? pl : 0u;                                              \
-                YH[m] ^= take ? ph : 0u;                                              \
-            }                                                                         \
-        }
-        RS16_FDL(0) RS16_FDL(1) RS16_FDL(2) RS16_FDL(3) RS16_FDL(4) RS16_FDL(5)
-#undef RS16_FDL
-    }
-    // ---- FFT of the tile's 8 row bits, high layers first: blocks (6, 7),
-    // (4, 5), (2, 3), (0, 1)
-    auto tabs_of = [&](BlockTabs& bt, auto b0c, auto b1c) {
-        constexpr int B0 = decltype(b0c)::value, B1 = decltype(b1c)::value;
-        const uint32_t r0 = brow<B0, B1>(lane, 0), r2 = brow<B0, B1>(lane, 2);
-        auto off = [](int kb, uint32_t r) { return (((1u << T) - (1u << (T - kb))) + (r >> (kb + 1))) * 80u; };
-        lds_table(bt.w0, tabs, off(B0, r0));
-        lds_table(bt.w2, tabs, off(B0, r2));
-        lds_table(bt.w1, tabs, off(B1, r0));
-    };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
-    using I4 = std::integral_constant<int, 4>;
-    using I5 = std::integral_constant<int, 5>;
-    using I6 = std::integral_constant<int, 6>;
-    using I7 = std::integral_constant<int, 7>;
-    RS16_STAMP(a, 3);
-    BlockTabs ta, tb;
-    tabs_of(ta, I6(), I7());
-    tabs_of(tb, I4(), I5());
-    compute<true, true, true>(YL, YH, ta);
-    wave_exchange<4, 5>(YL, YH);
-    tabs_of(ta, I2(), I3());
-    compute<true, true, true>(YL, YH, tb);
-    wave_exchange<2, 3>(YL, YH);
-    tabs_of(tb, I0(), I1());
-    compute<true, true, true>(YL, YH, ta);
-    wave_exchange<0, 1>(YL, YH);
-    compute<true, true, true>(YL, YH, tb);
-    RS16_STAMP(a, 9);
-    // ---- reveal (x (65535 - e)) and store the lost originals in place
-    // (restored-originals row = work row - the originals' segment start)
-    const int64_t shift = (int64_t)a.row_base_out - (a.rest_seg_b ? (int64_t)a.chunk : 0);
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-        if (!lost[m]) continue;
-        uint32_t ol = 0, oh = 0;
-        mul_xor(ol, oh, YL[m], YH[m], rt[m]);
-        const int64_t rr = (int64_t)(tile << T) + 4 * lane + m + shift;
-        uint32_t* p = (uint32_t*)(a.rest + rr * (int64_t)a.S_rest + offL);
-        // (plain stores: 32768:32768 1 %-loss decode 103.1 -> 101.5 us against
-        // non-temporal ones, same-box A/B x 3)
-        p[0] = ol;
-        p[8] = oh;
-    }
-    RS16_STAMP(a, 10);
-    RS16_STAMP_END(a);
+template <int P, int T, int NV = 0> PassKernel pass_entry() {
+    return {pass_kernel<P, T, NV>, Smem<P, T>::BYTES, Geo<T>::THREADS, Geo<T>::Q};
 }
-
-hipError_t launch_tile_last(const PassArgs& a, uint32_t num_tiles, hipStream_t s) {
-    if (num_tiles == 0 || a.qrow == 0) return hipSuccess;
-    const uint32_t nwg = num_tiles * ((a.qrow + 3) / 4);
-    hipLaunchKernelGGL(tile_last_kernel, dim3(nwg), dim3(256), 0, s, a);
-    return hipGetLastError();
+// the 12-lookup kernels of program P at T = 0 .. 8
+template <int P> PassKernel pass_row(int T) {
+    static const PassKernel row[9] = {pass_entry<P, 0>(), pass_entry<P, 1>(), pass_entry<P, 2>(),
+                                      pass_entry<P, 3>(), pass_entry<P, 4>(), pass_entry<P, 5>(),
+                                      pass_entry<P, 6>(), pass_entry<P, 7>(), pass_entry<P, 8>()};
+    return row[T];
 }
-
-// ---------------------------------------------------------------------------
-// The general decode's middle pass as a direct product.  DEC_MID is the same
-// linear map u = FFT_hi (I + H) IFFT_hi z on every tile column j (rows
-// t << lo | j; its twiddles do not involve j), a 2^hi x 2^hi matrix M over
-// GF(2^16) (mid_matrix_entries, rs16_tables.cpp).  When the lost originals
-// lie in few last-pass tiles, DEC_LAST consumes only the U rows t in
-// [nlo, nhi) -- nhi - nlo <= MID_DIRECT_MAX -- and each is a sum over the
-// live z rows (DEC_FIRST tiles with a received row, zflags):
-//   u[o << lo | j] = sum over live t of M[o][t] z[t << lo | j]
-// -- (nhi - nlo) x (live rows) multiplies per column instead of DEC_MID's
-// 2^hi-point IFFT, derivative and output-pruned FFT (at the reference
-// bench's 1 % loss: 2 x 129 against ~1300 butterflies, and one dispatch
-// round instead of two).  Workgroup = (column j, 64-quad slab, stripe);
-// its 8 waves take the rows t = w mod 8 (the zero tiles cluster, so
-// interleaved), all of a wave's rows requested at once, and multiply them by
-// the tables of rows [nlo, nhi) of M in LDS (one LDS-DMA copy of the
-// contiguous v_perm tables), then XOR their partial sums through LDS; wave o
-// stores row nlo + o.  A stripe whose consumed rows exceed
-// MID_DIRECT_MAX returns here and DEC_MID computes it (PassArgs::mid_direct).
-// ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(512) mid_direct_kernel(PassArgs a, const uint32_t* mtab, uint32_t hi) {
-    constexpr uint32_t W = 8, RPW = 256 / W;  // waves; rows per wave at 2^hi = 256
-    extern __shared__ __attribute__((aligned(16))) uint8_t mlds[];
-    // blockIdx.x = column j x slabs + 64-quad slab (one index: the stamps' workgroup id)
-    const uint32_t nslab = (a.qrow + 63) / 64;
-    const uint32_t j = blockIdx.x / nslab, slab = blockIdx.x - j * nslab;
-    const uint32_t t0 = threadIdx.x, lane = t0 & 63, w = uni(t0 >> 6);
-    if (blockIdx.z) {  // stripe z (PassArgs::stripe_tiles convention: displacements per stripe)
-        const uint32_t st = blockIdx.z;
-        a.in += st * a.bs_in;
-        a.out += st * a.bs_out;
-        if (a.zflags) a.zflags += st * a.bs_zflags;
-        a.lostrange += st * a.bs_lost;
-    }
-    uint32_t nlo, nhi;
-    if (!mid_need(a, nlo, nhi)) return;
-    const uint32_t N = 1u << hi, nout = nhi - nlo, rpw = N / W;
-    RS16_STAMP(a, 0);
-    const uint32_t Qg = slab * 64 + lane;
-    const bool active = Qg < a.qrow;
-    const uint32_t offL = (Qg >> 3) * 64 + (Qg & 7) * 4;
-    const uint8_t* zpage = a.zero + (offL & 0x7FFFu);
-    // The wave's rows t = w + 8 u (a dead row -- DEC_FIRST tile without a
-    // received row -- reads the zero page) and the tables of rows [nlo, nhi)
-    // of M (LDS-DMA, L2-resident after the first workgroups).
-    // (lane u reads row u's zero-tile flag: one load and a ballot)
-    const bool lv_lane = lane < rpw && !(a.zflags && a.zflags[w + W * lane]);
-    const uint64_t live = __ballot(lv_lane);
-    const uint8_t* rbase = a.in + ((uint64_t)w << a.lo | j) * a.S_in;
-    const uint64_t rstride = ((uint64_t)W << a.lo) * a.S_in;
-    // Rows in batches of RPB: batch b + 1 is requested once batch b has
-    // landed, before batch b's multiplies.  (All rows requested at once land
-    // together at the end of the chip-wide load phase and the VALU idles
-    // through it: 14.8 us per workgroup, half of it loads,
-    // `profiles/r05_mid_direct.txt`.)
-    constexpr uint32_t RPB = 8, NB = RPW / RPB;
-    uint32_t zl[2][RPB], zh[2][RPB];
-    auto fetch = [&](uint32_t b, uint32_t (&l)[RPB], uint32_t (&h)[RPB]) {
-#pragma unroll
-        for (uint32_t v = 0; v < RPB; v++) {
-            const uint32_t u = b * RPB + v;
-            const uint32_t* p = (const uint32_t*)(active && ((live >> u) & 1u) ? rbase + u * rstride + offL : zpage);
-            l[v] = p[0];
-            h[v] = p[8];
-        }
-    };
-    fetch(0, zl[0], zh[0]);
-    uint4* tabs = (uint4*)mlds;
-    colops::dma_copy_rt<W * 64>((const uint8_t*)(mtab + (size_t)nlo * N * 20), mlds, nout * N * 80);
-    __builtin_amdgcn_s_waitcnt(0);
-    __syncthreads();  // tables in LDS
-    RS16_STAMP(a, 1);
-    uint32_t acc[MID_DIRECT_MAX][2] = {};
-    auto multiply = [&](uint32_t b, const uint32_t (&l)[RPB], const uint32_t (&h)[RPB]) {
-#pragma unroll
-        for (uint32_t v = 0; v < RPB; v++) {
-            const uint32_t u = b * RPB + v;
-            if (!((live >> u) & 1u)) continue;  // (uniform)
-            const uint32_t t = w + W * u;
-#pragma unroll
-            for (uint32_t o = 0; o < MID_DIRECT_MAX; o++) {
-                if (o >= nout) break;
-                uint32_t tt[20];
-                load_table_lds(tt, tabs + (o * N + t) * 5);
-                mul_xor(acc[o][0], acc[o][1], l[v], h[v], tt);
-            }
-        }
-    };
-#pragma unroll
-    for (uint32_t b = 0; b < NB; b++) {
-        if (b * RPB >= rpw) break;  // (uniform: 2^hi < 256)
-        if (b + 1 < NB && (b + 1) * RPB < rpw) fetch(b + 1, zl[(b + 1) & 1], zh[(b + 1) & 1]);
-        multiply(b, zl[b & 1], zh[b & 1]);
-        __builtin_amdgcn_s_waitcnt(vmcnt_wait(0));
-    }
-    RS16_STAMP(a, 2);
-    // XOR the waves' partial sums: row o by wave o
-    __syncthreads();  // (the tables are no longer read: the partials reuse their LDS)
-    uint2* part = (uint2*)mlds;
-#pragma unroll
-    for (uint32_t o = 0; o < MID_DIRECT_MAX; o++)
-        if (o < nout) part[(w * MID_DIRECT_MAX + o) * 64 + lane] = make_uint2(acc[o][0], acc[o][1]);
-    __syncthreads();
-    if (w < nout) {
-        uint32_t xl = 0, xh = 0;
-#pragma unroll
-        for (uint32_t v = 0; v < W; v++) {
-            const uint2 q = part[(v * MID_DIRECT_MAX + w) * 64 + lane];
-            xl ^= q.x;
-            xh ^= q.y;
-        }
-        if (active) {
-            uint32_t* p = (uint32_t*)(a.out + ((uint64_t)(nlo + w) << a.lo | j) * a.S_out + offL);
-            p[0] = xl;
-            p[8] = xh;
-        }
-    }
-    RS16_STAMP_END(a);
-}
-
-hipError_t launch_mid_direct(const PassArgs& a, const uint32_t* mtab, uint32_t hi, uint32_t ns, hipStream_t s) {
-    if (a.qrow == 0 || ns == 0) return hipSuccess;
-    const uint32_t N = 1u << hi;
-    // tables of up to MID_DIRECT_MAX rows (bounded by the host's consumed range)
-    const uint32_t rows = std::min(MID_DIRECT_MAX, a.need_hi > a.need_lo ? a.need_hi - a.need_lo : 0u);
-    if (rows == 0 || hi > 8 || hi < 3) return rows == 0 ? hipSuccess : hipErrorInvalidValue;
-    const size_t lds = std::max((size_t)rows * N * 80, (size_t)8 * MID_DIRECT_MAX * 64 * 8);
-    if (lds > 65536) {  // (as launch_pass: set on every call, i.e. on the current device)
-        hipError_t e = hipFuncSetAttribute((const void*)mid_direct_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(mid_direct_kernel, dim3((1u << a.lo) * ((a.qrow + 63) / 64), 1, ns), dim3(512), lds, s, a, mtab,
-                       hi);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Dispatch table [prog][T].
-// ---------------------------------------------------------------------------
-typedef void (*PassFn)(PassArgs);
-
-#define RS16_ROW(P)                                                                                            \
-    {pass_kernel<P, 0>, pass_kernel<P, 1>, pass_kernel<P, 2>, pass_kernel<P, 3>, pass_kernel<P, 4>,             \
-     pass_kernel<P, 5>, pass_kernel<P, 6>, pass_kernel<P, 7>, pass_kernel<P, 8>}
-static const PassFn kPass[NUM_PROGS][9] = {
-    RS16_ROW(GEN_FFT),    RS16_ROW(GEN_IFFT),  RS16_ROW(ENC_FIRST), RS16_ROW(ENC_MID),  RS16_ROW(ENC_LAST),
-    RS16_ROW(ENC_SINGLE), RS16_ROW(DEC_FIRST), RS16_ROW(DEC_MID),   RS16_ROW(DEC_LAST), RS16_ROW(DEC_SINGLE),
-    RS16_ROW(DEC_HALF_LAST), RS16_ROW(DEC_HALF_SINGLE),
-};
-#undef RS16_ROW
-// The narrow variants [NV - 1][T - 5] of the two two-direction middle passes
-// (nullptr: none, the launch takes a variant that assumes less, or NV = 0).
-// DEC_MID runs at skew 0 in both directions, so it is narrow everywhere or
-// not at all; ENC_MID needs variants 2 / 3 only with 2^15-row stripes (T = 8).
-#define RS16_NROW(P, NV) {pass_kernel<P, 5, NV>, pass_kernel<P, 6, NV>, pass_kernel<P, 7, NV>, pass_kernel<P, 8, NV>}
-static const PassFn kEncMidNarrow[NARROW_VARIANTS - 1][4] = {
-    RS16_NROW(ENC_MID, 1),
-    {nullptr, nullptr, nullptr, pass_kernel<ENC_MID, 8, 2>},
-    {nullptr, nullptr, nullptr, pass_kernel<ENC_MID, 8, 3>},
-};
-static const PassFn kDecMidNarrow[4] = RS16_NROW(DEC_MID, 1);
-#undef RS16_NROW
-// The kernel of a launch: among the variants that exist for (prog, T), the
-// one that uses the narrow multiply in the most layers the launch allows
-// (ni / nf: first_narrow_layer of its IFFT / FFT direction).
-static PassFn pick_kernel(int prog, int T, int ni, int nf) {
-    if (T >= 5 && (prog == ENC_MID || prog == DEC_MID)) {
-        for (int nv = 1; nv < NARROW_VARIANTS; nv++) {
-            const int vi = nv == 2 ? 1 : 0, vf = nv == 3 ? 1 : 0;  // NarrowVar<nv>::IFFT_FROM / FFT_FROM
-            if (ni > vi || nf > vf) continue;
-            const PassFn f = prog == ENC_MID ? kEncMidNarrow[nv - 1][T - 5] : (nv == 1 ? kDecMidNarrow[T - 5] : nullptr);
-            if (f) return f;
-        }
-    }
-    return kPass[prog][T];
-}
-
-#define RS16_SM(P)                                                                                            \
-    {Smem<P, 0>::BYTES, Smem<P, 1>::BYTES, Smem<P, 2>::BYTES, Smem<P, 3>::BYTES, Smem<P, 4>::BYTES,             \
-     Smem<P, 5>::BYTES, Smem<P, 6>::BYTES, Smem<P, 7>::BYTES, Smem<P, 8>::BYTES}
-static const int kSmem[NUM_PROGS][9] = {
-    RS16_SM(GEN_FFT),    RS16_SM(GEN_IFFT),  RS16_SM(ENC_FIRST), RS16_SM(ENC_MID),  RS16_SM(ENC_LAST),
-    RS16_SM(ENC_SINGLE), RS16_SM(DEC_FIRST), RS16_SM(DEC_MID),   RS16_SM(DEC_LAST), RS16_SM(DEC_SINGLE),
-    RS16_SM(DEC_HALF_LAST), RS16_SM(DEC_HALF_SINGLE),
-};
-#undef RS16_SM
-
-#define RS16_TH(P)                                                                                             \
-    {Geo<0>::THREADS, Geo<1>::THREADS, Geo<2>::THREADS, Geo<3>::THREADS, Geo<4>::THREADS, Geo<5>::THREADS,       \
-     Geo<6>::THREADS, Geo<7>::THREADS, Geo<8>::THREADS}
-static const int kThreads[9] = RS16_TH(0);
-static const int kQuads[9] = {Geo<0>::Q, Geo<1>::Q, Geo<2>::Q, Geo<3>::Q, Geo<4>::Q,
-                              Geo<5>::Q, Geo<6>::Q, Geo<7>::Q, Geo<8>::Q};
-#undef RS16_TH
-
-hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles, hipStream_t s) {
-    if (prog < 0 || prog >= NUM_PROGS || T < 0 || T > 8) return hipErrorInvalidValue;
-    if (num_tiles == 0 || args.qrow == 0) return hipSuccess;
-    PassArgs a = args;
-    a.nslab = (a.qrow + kQuads[T] - 1) / kQuads[T];
-    a.ntiles = num_tiles;
-    const uint32_t nwg = num_tiles * a.nslab;  // one workgroup per (tile, slab) item
-    if (a.need_hi == 0) a.need_hi = 1u << T;  // no pruning
-    {
-        const uint64_t hws = kQuads[T] >= 64 ? 1 : 64 / kQuads[T];
-        const uint64_t smax = std::max(std::max(a.S_in, a.S_out), std::max(a.S_seg, a.S_rest));
-        const uint64_t span = (uint64_t)1 << (T + a.lo);  // rows of one tile's aligned block
-        const bool fits = (hws - 1) * ((uint64_t)16 << a.lo) * smax + 1024 < ((uint64_t)1 << 32);
-        const bool aligned = a.chunk % span == 0 && a.row_base_in % span == 0;
-        // (RS16_DIAG_FORCE_VOFF64: always the 64-bit lane offsets)
-        a.voff32 = fits && aligned && !(a.diag & DIAG_FORCE_VOFF64) ? 1u : 0u;
-        a.fd_lds = (a.diag & DIAG_FD_LDS) ? 1u : 0u;
-    }
-    // Narrow twiddles: the launch's tiles are tile_base + [0, tiles of one
-    // stripe), b_high = tile >> lo (RS16_DIAG_WIDE_TWIDDLES: never)
-    int ni = T, nf = T;
-    if (!(a.diag & DIAG_WIDE_TWIDDLES)) {
-        const uint32_t bh_max = (a.tile_base + (a.stripe_tiles ? a.stripe_tiles : num_tiles) - 1) >> a.lo;
-        ni = first_narrow_layer(a.lo, T, a.skew_ifft, bh_max);
-        nf = first_narrow_layer(a.lo, T, a.skew_fft, bh_max);
-    }
-    const PassFn fn = pick_kernel(prog, T, ni, nf);
-    const size_t lds = (size_t)kSmem[prog][T];
-    if (lds > 65536) {
-        // (per kernel variant: each is a function of its own)
-        hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    dim3 grid(nwg), block(kThreads[T]);
-    hipLaunchKernelGGL(fn, grid, block, lds, s, a);
-    return hipGetLastError();
+// narrow variant NV of program P at T = 5 .. 8 (no such kernel below)
+template <int P, int NV> PassKernel narrow_row(int T) {
+    static const PassKernel row[4] = {pass_entry<P, 5, NV>(), pass_entry<P, 6, NV>(), pass_entry<P, 7, NV>(),
+                                      pass_entry<P, 8, NV>()};
+    return T >= 5 ? row[T - 5] : PassKernel{};
 }
 
 }  // namespace rs16

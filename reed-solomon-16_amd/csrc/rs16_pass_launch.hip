@@ -1,0 +1,80 @@
+// rs16_pass_launch.hip -- launch_pass: which pass kernel a launch takes and
+// how it is launched.  The kernels themselves are instantiated in
+// rs16_pass_enc.hip and rs16_pass_dec.hip (template: rs16_pass.hpp); this
+// unit sees them through the PassKernel lookups only.
+#include <algorithm>
+
+#include "rs16_pass_common.hpp"
+
+namespace rs16 {
+
+// The kernel of (prog, T, nv) (fn nullptr: no such variant): one table,
+// filled at the first launch from whichever unit instantiates the program.
+struct KernelTable {
+    PassKernel k[NUM_PROGS][9][NARROW_VARIANTS];
+    KernelTable() {
+        for (int prog = 0; prog < NUM_PROGS; prog++)
+            for (int T = 0; T <= 8; T++)
+                for (int nv = 0; nv < NARROW_VARIANTS; nv++) {
+                    const PassKernel e = pass_kernels_enc(prog, T, nv);
+                    k[prog][T][nv] = e.fn ? e : pass_kernels_dec(prog, T, nv);
+                }
+    }
+};
+static const PassKernel& find_kernel(int prog, int T, int nv) {
+    static const KernelTable table;
+    return table.k[prog][T][nv];
+}
+
+// The kernel of a launch: among the variants that exist for (prog, T), the
+// one that uses the narrow multiply in the most layers the launch allows
+// (ni / nf: first_narrow_layer of its IFFT / FFT direction).
+static const PassKernel& pick_kernel(int prog, int T, int ni, int nf) {
+    for (int nv = 1; nv < NARROW_VARIANTS; nv++) {
+        const int vi = nv == 2 ? 1 : 0, vf = nv == 3 ? 1 : 0;  // NarrowVar<nv>::IFFT_FROM / FFT_FROM
+        if (ni > vi || nf > vf) continue;
+        const PassKernel& k = find_kernel(prog, T, nv);
+        if (k.fn) return k;
+    }
+    return find_kernel(prog, T, 0);
+}
+
+hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles, hipStream_t s) {
+    if (prog < 0 || prog >= NUM_PROGS || T < 0 || T > 8) return hipErrorInvalidValue;
+    if (num_tiles == 0 || args.qrow == 0) return hipSuccess;
+    PassArgs a = args;
+    // Narrow twiddles: the launch's tiles are tile_base + [0, tiles of one
+    // stripe), b_high = tile >> lo (RS16_DIAG_WIDE_TWIDDLES: never)
+    int ni = T, nf = T;
+    if (!(a.diag & DIAG_WIDE_TWIDDLES)) {
+        const uint32_t bh_max = (a.tile_base + (a.stripe_tiles ? a.stripe_tiles : num_tiles) - 1) >> a.lo;
+        ni = first_narrow_layer(a.lo, T, a.skew_ifft, bh_max);
+        nf = first_narrow_layer(a.lo, T, a.skew_fft, bh_max);
+    }
+    const PassKernel& k = pick_kernel(prog, T, ni, nf);
+    a.nslab = (a.qrow + k.quads - 1) / k.quads;
+    a.ntiles = num_tiles;
+    const uint32_t nwg = num_tiles * a.nslab;  // one workgroup per (tile, slab) item
+    if (a.need_hi == 0) a.need_hi = 1u << T;  // no pruning
+    {
+        const uint64_t hws = k.quads >= 64 ? 1 : 64 / k.quads;
+        const uint64_t smax = std::max(std::max(a.S_in, a.S_out), std::max(a.S_seg, a.S_rest));
+        const uint64_t span = (uint64_t)1 << (T + a.lo);  // rows of one tile's aligned block
+        const bool fits = (hws - 1) * ((uint64_t)16 << a.lo) * smax + 1024 < ((uint64_t)1 << 32);
+        const bool aligned = a.chunk % span == 0 && a.row_base_in % span == 0;
+        // (RS16_DIAG_FORCE_VOFF64: always the 64-bit lane offsets)
+        a.voff32 = fits && aligned && !(a.diag & DIAG_FORCE_VOFF64) ? 1u : 0u;
+        a.fd_lds = (a.diag & DIAG_FD_LDS) ? 1u : 0u;
+    }
+    const size_t lds = (size_t)k.lds;
+    if (lds > 65536) {
+        // (per kernel variant: each is a function of its own)
+        hipError_t e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    dim3 grid(nwg), block(k.threads);
+    hipLaunchKernelGGL(k.fn, grid, block, lds, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace rs16

@@ -89,7 +89,7 @@ void build(HostTables& t) {
 
     // The pass kernels skip the multiply of uniform groups whose twiddle is
     // the sentinel and recognise those by index: the sentinel entries are
-    // exactly the indices 2^i - 1 (rs16_pass.hip, GroupLoop).  A table that
+    // exactly the indices 2^i - 1 (rs16_pass.hpp, GroupLoop).  A table that
     // broke this would give wrong results, so it is checked here, once.
     for (uint32_t i = 0; i < GF_MODULUS; i++)
         if ((t.skew[i] == GF_MODULUS) != ((i & (i + 1)) == 0)) {

@@ -5,7 +5,7 @@ Runs the bench's step (32768:32768 x 1 KiB encode + 100 %-loss decode) with
 the stamps of one pass program at a time and prints, per pass: the spread
 of workgroup start / end times (s_memrealtime, 100 MHz) and the median
 duration of each phase of a workgroup (s_memtime cycles at the workgroup's
-own clock).  Phases (rs16_pass.hip stamp()): 0 start, 1 loads issued,
+own clock).  Phases (rs16_pass.hpp RS16_STAMP): 0 start, 1 loads issued,
 2 tables staged, 3 first layout-A layers, 4 layout switch, 5 first
 direction done, 6 formal derivative, 7 layout-B FFT layers, 8 layout
 switch, 9 last layers, 10 stores issued, 11 stores done; EVAL_POLY (the

@@ -142,7 +142,7 @@ def loss_masks(k, m, pattern):
 ])
 def test_decode_zero_tiles(eng, k, m, sb, pattern):
     # DEC_FIRST tiles without a received row are skipped and read back as
-    # zero by DEC_MID / DEC_LAST (rs16_pass.hip); restoration must be exact.
+    # zero by DEC_MID / DEC_LAST (rs16_pass.hpp); restoration must be exact.
     original = generate_original(k, sb, 11)
     recovery = dev_encode(eng, original, m)
     assert np.array_equal(recovery, O.encode(k, m, original))
@@ -311,7 +311,7 @@ def test_decode_last_pass_paths(eng, k, m, sb, pattern, path):
 ])
 def test_decode_split_formal_derivative(eng, k, m, sb, diag, lost, fd):
     # DEC_MID's in-tile formal derivative split by row bits (fd_regs /
-    # fd_image, rs16_pass.hip) when the consumed tile rows lie in two
+    # fd_image, rs16_pass.hpp) when the consumed tile rows lie in two
     # layout-B register rows, else through the LDS image; DIAG_FD_LDS forces
     # the LDS form everywhere.  Both restore the lost originals bit-exactly.
     original = generate_original(k, sb, 19)

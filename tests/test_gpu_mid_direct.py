@@ -1,4 +1,4 @@
-"""The general decode's middle pass as a direct product (rs16_pass.hip
+"""The general decode's middle pass as a direct product (rs16_pass_small.hpp
 mid_direct_kernel): when the lost originals lie in at most
 MID_DIRECT_MAX = 4 of the middle pass's output rows per column, those rows
 are computed as sums over the live z rows with the pass's matrix

@@ -1,4 +1,4 @@
-"""The narrow-twiddle variants of the middle passes (rs16_pass.hip NarrowVar;
+"""The narrow-twiddle variants of the middle passes (rs16_pass.hpp NarrowVar;
 launch_pass picks one per launch from first_narrow_layer) against the
 12-lookup multiply everywhere (RS16_DIAG_WIDE_TWIDDLES) and the oracle.
 
