@@ -345,6 +345,74 @@ int rs16_decode_device_prepared(rs16_engine* eng, size_t original_count, size_t 
                                 size_t shard_bytes, void* d_original, const void* d_recovery, void* stream,
                                 rs16_error* err);
 
+/* ---- Partial-stripe writes: delta update of the recovery shards ----------
+ * Overwriting a few original shards of a stripe that is already encoded.
+ * The encode is GF(2^16)-linear per element position (src/algorithm.md:18-32),
+ *   recovery_j = sum_i M[j][i] * original_i,
+ * so after originals indices[0 .. n) changed from old_e to new_e
+ *   recovery_j ^= sum_e M[j][indices[e]] * (old_e ^ new_e).
+ * That needs only the n deltas and the recovery shards: the other originals
+ * need not be in HBM, and one read-modify-write sweep over the recovery rows
+ * replaces the three passes of rs16_encode_device.  No reference counterpart
+ * (the reference re-encodes: src/lib.rs:242-279).
+ *
+ * A plan holds the n columns of M for one (rate, original_count,
+ * recovery_count, indices).  `rate` must be the rate the stripe was encoded
+ * with: the two rates are different codes with different M.
+ * RS16_RATE_DEFAULT means what it means everywhere else in the library, the
+ * choice of rs16_use_high_rate -- the rate of rs16_encode_device.  At most
+ * RS16_UPDATE_MAX_SHARDS = 32 originals per plan: the plan gets its columns
+ * from ONE encode of a 64-byte stripe (the engine's own encode of that rate,
+ * so they are exact on every rate path), and a 64-byte block carries 32
+ * independent elements -- element e is the field element 1 in shard
+ * indices[e] and 0 elsewhere, and recovery row j returns M[j][indices[e]] in
+ * element e.  More changed originals: XOR is associative, so apply several
+ * plans one after another (each to its own deltas); likewise several updates
+ * through one plan compose to the encode of the final stripe.
+ *
+ * rs16_update_plan_new is synchronous (one small encode on the engine's
+ * stream, its result copied to the host, an m x n index array uploaded).
+ * Errors, checked in this order: UnsupportedShardCount as rs16_validate gives
+ * for `rate`; n == 0 or n > 32: InvalidArgument; an index >= original_count:
+ * InvalidOriginalShardIndex (v0 original_count, v1 index); a repeated index:
+ * DuplicateOriginalShardIndex.  Like an encoder, a plan is detached by
+ * rs16_engine_free: later calls on it fail with RS16_INVALID_ARGUMENT and
+ * rs16_update_plan_free then frees only host memory.  Updates enqueued on a
+ * caller's stream must have finished before the plan or its engine is freed.
+ *
+ * rs16_update_device is asynchronous on `stream` and works in place:
+ * d_delta = the n shards old ^ new in the order of `indices`, contiguous,
+ * read only; d_recovery = recovery shards [recovery_pos, recovery_pos +
+ * recovery_n), contiguous (a node that stores only some recovery shards
+ * updates only those); recovery_n == 0 does nothing.  shard_bytes 0 or no
+ * multiple of 64: InvalidShardSize; a range beyond recovery_count:
+ * InvalidArgument.  It uses no engine scratch and no decode state: it may run
+ * on any stream beside the engine's other work, and it neither disturbs
+ * rs16_decode_check nor a pending rs16_decode_prepare.
+ *
+ * When to prefer it (MI355X, DESIGN.md 3.15, profiles/r08_update.txt): the
+ * update's cost grows with n, rs16_encode_device's does not.  Measured at
+ * 32768:32768 x 1 KiB: the encode 69 us, the update 12 / 18 / 33 / 63 us at
+ * n = 1 / 4 / 8 / 16; it stops beating the encode at n = 17 (16-18 at 64 and
+ * 192-byte shards) and costs twice the encode at n = 32.  So the cap of 32 is
+ * above the crossover: with the whole stripe in HBM, re-encode from about 16
+ * changed shards on; the update still wins beyond that when the other
+ * originals would first have to be fetched.  At 1000:1000 x 1 KiB (8 us
+ * encode) the update is 4-5 us up to n = 16 and level with the encode at 32.
+ * rs16_update_plan_new costs 1 ms at 32768:32768 and 0.07 ms at 1000:1000
+ * (host time, synchronous): keep plans for shards that are rewritten often. */
+enum { RS16_UPDATE_MAX_SHARDS = 32 };   /* one 64-byte block carries 32 independent elements */
+typedef struct rs16_update_plan rs16_update_plan;
+rs16_update_plan* rs16_update_plan_new(rs16_engine* eng, int rate, size_t original_count, size_t recovery_count,
+                                       const size_t* indices, size_t n, rs16_error* err);
+void rs16_update_plan_free(rs16_update_plan* plan);
+size_t rs16_update_plan_count(const rs16_update_plan* plan);
+/* Diagnostics / tests: out[j * n + e] = M[j][indices[e]] as a field element
+ * (recovery_count x n values). */
+int rs16_update_plan_coefficients(rs16_update_plan* plan, uint16_t* out, rs16_error* err);
+int rs16_update_device(rs16_update_plan* plan, size_t shard_bytes, const void* d_delta, void* d_recovery,
+                       size_t recovery_pos, size_t recovery_n, void* stream, rs16_error* err);
+
 /* ---- Host-resident stripes, pipelined (full duplex) -----------------------
  * nstripes independent stripes in host memory (stripe i's originals at
  * h_original + i original_stride, its recovery at h_recovery + i

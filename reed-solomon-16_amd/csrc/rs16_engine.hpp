@@ -68,6 +68,7 @@ DecodeGeom decode_geom(bool high, size_t k, size_t m);
 
 struct rs16_encoder;
 struct rs16_decoder;
+struct rs16_update_plan;
 
 struct rs16_engine {
     int device = 0;
@@ -188,6 +189,7 @@ struct rs16_engine {
     // rs16_{en,de}coder_free only frees its host memory.
     std::vector<rs16_encoder*> encoders;
     std::vector<rs16_decoder*> decoders;
+    std::vector<rs16_update_plan*> update_plans;  // detached the same way (rs16_update_plan_free)
 
     // Pass launch (with optional hipEvent timing on the launch stream under
     // profiling id `prof` (rs16::ProfId; -1 = the program's own id).

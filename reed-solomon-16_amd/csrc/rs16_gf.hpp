@@ -79,8 +79,15 @@ inline uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return a ^ b ^ c; }
 // one of the six XORs are left out: 9 v_perm + 5 XOR against 12 + 6.  The
 // same 20-dword table serves both forms (the narrow one ignores five dwords).
 // Which twiddles are narrow: twiddle_narrow (rs16_internal.hpp).
-template <bool NARROW>
-RS16_HD void mul_xor_t(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const uint32_t* t) {
+//
+// The two halves of a product are separate functions, so that a kernel which
+// multiplies one y by many constants extracts y's six selectors once
+// (mul_selectors) and pays only the lookups per constant (mul_xor_sel):
+// rs16_update.hip.
+struct MulSel {
+    uint32_t s0, s1, s2, s3, s4, s5;
+};
+RS16_HD MulSel mul_selectors(uint32_t yL, uint32_t yH) {
 #if defined(__HIP_DEVICE_COMPILE__)
     // The selectors of both dwords from two 64-bit shifts of the (L, H) pair
     // instead of four 32-bit ones (the host's form below): the bits H shifts
@@ -108,6 +115,11 @@ RS16_HD void mul_xor_t(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, con
     const uint32_t s4 = b & 0x07070707u;
     const uint32_t s5 = (b >> 3) & 0x03030303u;
 #endif
+    return MulSel{s0, s1, s2, s3, s4, s5};
+}
+template <bool NARROW>
+RS16_HD void mul_xor_sel(uint32_t& xL, uint32_t& xH, const MulSel& y, const uint32_t* t) {
+    const uint32_t s0 = y.s0, s1 = y.s1, s2 = y.s2, s3 = y.s3, s4 = y.s4, s5 = y.s5;
     if constexpr (NARROW) {
         const uint32_t l0 = perm(t[1], t[0], s0);
         const uint32_t l1 = perm(t[5], t[4], s1);
@@ -127,6 +139,10 @@ RS16_HD void mul_xor_t(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, con
         xL = xor3(xor3(xL, l0, l1), xor3(l2, l3, l4), l5);
         xH = xor3(xor3(xH, h0, h1), xor3(h2, h3, h4), h5);
     }
+}
+template <bool NARROW>
+RS16_HD void mul_xor_t(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const uint32_t* t) {
+    mul_xor_sel<NARROW>(xL, xH, mul_selectors(yL, yH), t);
 }
 RS16_HD void mul_xor(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const uint32_t* t) {
     mul_xor_t<false>(xL, xH, yL, yH, t);

@@ -357,6 +357,21 @@ hipError_t launch_xor_chunks(uint8_t* w, size_t chunk_bytes, uint32_t nch, hipSt
 hipError_t launch_copy_chunks(uint8_t* w, size_t chunk_bytes, uint32_t nch, hipStream_t s);
 hipError_t launch_formal_derivative(uint8_t* out, const uint8_t* in, size_t shard_count, size_t S, hipStream_t s);
 
+// Delta update of recovery shards (rs16_update.hip): rec[r] ^= sum over
+// e < n of delta[e] * (table of entry idx[(row0 + r) n + e]) for r < rows.
+constexpr uint32_t UPDATE_MAX_SHARDS = 32;  // one 64-byte block carries 32 independent elements
+struct UpdateArgs {
+    uint8_t* rec;            // recovery rows [row0, row0 + rows), in place
+    const uint8_t* delta;    // n rows old ^ new, in the order of the plan's indices
+    const uint32_t* idx;     // the plan's recovery_count x n mul-table entries (ZERO_ENTRY: coefficient 0)
+    const uint32_t* mul_tab;
+    uint64_t S;              // row stride = row width (bytes)
+    uint32_t qrow;           // quads per row = S / 8
+    uint32_t row0, rows;
+    uint32_t quads_per_lane, nslab, rows_per_wave;  // set by launch_update
+};
+hipError_t launch_update(UpdateArgs a, uint32_t n, hipStream_t s);
+
 // FWHT / eval_poly.  `work` is a u32[65536] scratch.
 struct ErasureSpec {           // builds the erasure vector of rate_{high,low}.rs decode
     const uint8_t* flags_a;    // received flags of segment A

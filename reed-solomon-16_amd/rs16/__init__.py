@@ -31,6 +31,7 @@ __all__ = [
     "DIAG_FORCE_VOFF64", "DIAG_EVAL_TWO_KERNEL", "DIAG_EVAL_FULL", "DIAG_NO_COLUMN", "DIAG_FORCE_COLUMN",
     "DIAG_TILE_LAST", "DIAG_NO_TILE_LAST", "DIAG_FD_LDS", "DIAG_COL_RADIX4", "DIAG_NO_IDENTITY", "DIAG_NO_MID_DIRECT", "DIAG_WIDE_TWIDDLES", "encode_host", "decode_host",
     "encode_host_batch", "decode_host_batch", "decode_prepare", "decode_device_prepared",
+    "UpdatePlan", "update_recovery_device", "UPDATE_MAX_SHARDS",
     "encode_host_multi", "decode_host_multi", "Comm", "column_slice", "scatter_columns", "gather_columns",
 ]
 
@@ -717,6 +718,90 @@ def decode_device_prepared(original_count, recovery_count, shard_bytes, d_origin
            err)
     if check:
         _check(lib().rs16_decode_check(eng.h, stream, C.byref(err)), err)
+
+
+UPDATE_MAX_SHARDS = 32  # RS16_UPDATE_MAX_SHARDS
+
+
+class UpdatePlan:
+    """rs16_update_plan: the columns of the encode matrix of up to 32 original
+    shards `indices` of an original_count : recovery_count stripe encoded at
+    `rate` ("default" = the rate encode_device picks).  apply() adds the
+    change of those originals to recovery shards in place, from the deltas
+    old ^ new alone (include/rs16.h "Partial-stripe writes")."""
+
+    def __init__(self, original_count, recovery_count, indices, rate="default", engine: Optional[Engine] = None):
+        self.engine = engine or default_engine()
+        self._err = RS16Error()
+        indices = [int(i) for i in indices]
+        arr = (C.c_size_t * max(len(indices), 1))(*indices)
+        self.h = lib().rs16_update_plan_new(self.engine.h, _RATES[rate], original_count, recovery_count, arr,
+                                            len(indices), C.byref(self._err))
+        if not self.h:
+            raise Error._from_c(self._err)
+        self.original_count, self.recovery_count, self.indices = original_count, recovery_count, indices
+
+    def __len__(self) -> int:
+        return lib().rs16_update_plan_count(self.h)
+
+    def coefficients(self) -> np.ndarray:
+        """(recovery_count, n) uint16: [j, e] = M[j][indices[e]] as a field element."""
+        out = np.empty((self.recovery_count, len(self.indices)), np.uint16)
+        _check(lib().rs16_update_plan_coefficients(self.h, out.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                   C.byref(self._err)), self._err)
+        return out
+
+    def apply(self, shard_bytes, d_delta, d_recovery, recovery_pos=0, recovery_n=None, stream=None):
+        """d_recovery (recovery shards [recovery_pos, recovery_pos + recovery_n),
+        default: all from recovery_pos on) ^= M * d_delta (the n shards old ^
+        new in the order of `indices`).  Asynchronous on `stream`."""
+        if recovery_n is None:
+            recovery_n = max(self.recovery_count - recovery_pos, 0)
+        _check(lib().rs16_update_device(self.h, shard_bytes, Engine._ptr(d_delta), Engine._ptr(d_recovery),
+                                        recovery_pos, recovery_n, stream, C.byref(self._err)), self._err)
+
+    def close(self):
+        # Safe after the engine is gone: rs16_engine_free detaches its plans,
+        # and freeing a detached one only frees host memory.
+        if getattr(self, "h", None):
+            lib().rs16_update_plan_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def update_recovery_device(original_count, recovery_count, shard_bytes, indices, d_delta, d_recovery,
+                           rate="default", recovery_pos=0, recovery_n=None, stream=None,
+                           engine: Optional[Engine] = None):
+    """Delta update for any number of changed originals: `indices` in chunks of
+    at most 32, one plan each, applied one after another (XOR is associative).
+    d_delta: the len(indices) shards old ^ new in the order of `indices`.
+    Builds its plans on every call; callers that rewrite the same shards keep
+    an UpdatePlan."""
+    indices = [int(i) for i in indices]
+    if not indices:
+        raise Error("InvalidArgument")
+    seen = set()
+    for i in indices:  # (a plan sees only its own chunk)
+        if i in seen:
+            raise Error("DuplicateOriginalShardIndex", index=i)
+        seen.add(i)
+    base =Engine._ptr(d_delta)
+    plans = [UpdatePlan(original_count, recovery_count, indices[a:a + UPDATE_MAX_SHARDS], rate, engine)
+             for a in range(0, len(indices), UPDATE_MAX_SHARDS)]
+    try:
+        for c, plan in enumerate(plans):
+            plan.apply(shard_bytes, base + c * UPDATE_MAX_SHARDS * shard_bytes, d_recovery, recovery_pos, recovery_n,
+                       stream)
+        # the plans' index arrays must outlive the launches that read them
+        plans[0].engine.synchronize(stream)
+    finally:
+        for plan in plans:
+            plan.close()
 
 
 def _host_ptr(x) -> int:

@@ -112,7 +112,12 @@ SIGNATURES = {
     "rs16_encode_host_multi": (_i, [_p, _i, _sz, _sz, _sz, _p, _p, _e]),
     "rs16_decode_prepare": (_i, [_p, _sz, _sz, _sz, _p, _p, _sz, _sz, _p, _e]),
     "rs16_decode_device_prepared": (_i, [_p, _sz, _sz, _sz, _p, _p, _p, _e]),
-    "rs16_encode_host_batch": (_i, [_p, _sz, _sz, _sz, _sz, _p, _sz, _p, _sz, _e]),
+    "rs16_update_plan_new": (_p, [_p, _i, _sz, _sz, C.POINTER(_sz), _sz, _e]),
+    "rs16_update_plan_free": (None, [_p]),
+    "rs16_update_plan_count": (_sz, [_p]),
+    "rs16_update_plan_coefficients": (_i, [_p, C.POINTER(C.c_uint16), _e]),
+    "rs16_update_device": (_i, [_p, _sz, _p, _p, _sz, _sz, _p, _e]),
+    "rs16_encode_host_batch":(_i, [_p, _sz, _sz, _sz, _sz, _p, _sz, _p, _sz, _e]),
     "rs16_decode_host_batch": (_i, [_p, _sz, _sz, _sz, _sz, _p, _sz, _p, _sz, _p, _sz, _p, _sz, _e]),
     "rs16_decode_host_multi": (_i, [_p, _i, _sz, _sz, _sz, _p, _p, _p, _p, _e]),
     "rs16_stream_create": (_p, [_p, _e]),
