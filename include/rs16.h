@@ -588,6 +588,12 @@ void rs16_host_mul_narrow(const void* in, void* out, size_t bytes, uint16_t log_
  * launches go by calls the twiddle a subfield element, else 0. */
 uint32_t rs16_host_twiddle(uint32_t index, uint32_t* log_m, uint32_t* table20);
 int rs16_host_twiddle_narrow(uint32_t index);
+/* The pass launches divide workgroup indices by launch constants (slabs per
+ * row, tiles per stripe) with a host-computed multiply-high constant instead
+ * of a division.  This checks that form on the host: the number of n = n0 +
+ * i * step, i < count (stopping at 2^32), whose quotient by `divisor` (>= 1)
+ * differs from n / divisor. */
+uint64_t rs16_host_fast_div_check(uint32_t divisor, uint32_t n0, uint32_t count, uint32_t step);
 
 /* Library/build identification, e.g. "rs16-mi355x gfx950". */
 const char* rs16_version(void);

@@ -106,6 +106,13 @@ extern "C" uint32_t rs16_host_twiddle(uint32_t index, uint32_t* log_m, uint32_t*
     return t.skew[index] == GF_MODULUS ? 0u : t.exp[t.skew[index]];
 }
 extern "C" int rs16_host_twiddle_narrow(uint32_t index) { return twiddle_narrow(index) ? 1 : 0; }
+extern "C" uint64_t rs16_host_fast_div_check(uint32_t divisor, uint32_t n0, uint32_t count, uint32_t step) {
+    const FastDiv f = fast_div_of(divisor);
+    uint64_t bad = 0;
+    for (uint64_t i = 0, n = n0; i < count && n < ((uint64_t)1 << 32); i++, n += step)
+        bad += fast_div((uint32_t)n, f.mul, f.one) != (uint32_t)n / divisor;
+    return bad;
+}
 
 extern "C" int rs16_engine_set_profiling(rs16_engine* e, int enable, rs16_error* err) {
     if (int rc = e->activate(err)) return rc;

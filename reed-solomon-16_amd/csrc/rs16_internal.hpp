@@ -235,7 +235,40 @@ struct PassArgs {
     // the device and returns at once when the other one covers the stripe
     // (0: DEC_LAST alone, no tile_last_kernel launch)
     uint32_t tl_max;
+    // Launch constants of the full-item fast path (set by launch_pass).
+    // rs_in / rs_seg / rs_out: bytes between the rows of consecutive row
+    // registers of a thread, in the layout the kernel loads (in, seg_a) and
+    // stores (out) in: S << lo in layout A, S << (lo + SHB) in layout B.  A
+    // wave whose rows all are read / written forms one base address per array
+    // and steps it by these.
+    uint64_t rs_in, rs_seg, rs_out;
+    // Every lane of every item holds a quad of the row (qrow a multiple of the
+    // kernel's Q), lane offsets fit 32 bits (voff32) and plain loads read row
+    // r of `in` (no in_rows_mask): the launch-wide half of the fast path's
+    // test; the other half, the wave's rows against the row limit, is per wave.
+    uint32_t full_lanes;
+    // item / nslab and tile / stripe_tiles without a division (FastDiv)
+    uint32_t nslab_one, stripe_one;
+    uint64_t nslab_mul, stripe_mul;
 };
+
+// n / d for any 32-bit n without a division or a branch: the high 64 bits of
+// n x mul, plus n & one.  d = 1: mul = 0, one = ~0.  d = 2^s: mul = 2^(64-s),
+// exact.  Else mul = floor(2^64 / d) + 1 = (2^64 + e) / d with 0 < e < d, so
+// n mul / 2^64 = n / d + n e / (d 2^64), and n e < 2^64 keeps the excess below
+// 1 / d, the distance from n / d to the next integer: exact for every n < 2^32.
+struct FastDiv {
+    uint64_t mul;
+    uint32_t one;
+};
+inline FastDiv fast_div_of(uint32_t d) {
+    if (d <= 1) return {0, ~0u};  // (d = 0: never divided by)
+    return {~(uint64_t)0 / d + 1, 0};  // (d = 2^s divides 2^64: floor((2^64 - 1) / d) + 1 = 2^(64-s))
+}
+RS16_HD uint32_t fast_div(uint32_t n, uint64_t mul, uint32_t one) {
+    const uint64_t lo = ((uint64_t)n * (uint32_t)mul) >> 32;
+    return (uint32_t)(((uint64_t)n * (uint32_t)(mul >> 32) + lo) >> 32) + (n & one);
+}
 
 // One-launch codec for 2^9 / 2^10-row transforms (rs16_col.hip): one
 // workgroup per quad column (x stripe) runs the whole encode or

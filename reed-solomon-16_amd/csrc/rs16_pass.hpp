@@ -299,6 +299,87 @@ template <> struct LaneOff<false> {
 };
 
 // ---------------------------------------------------------------------------
+// Full-item fast path.  The general row addressing above decides per row and
+// per lane: a 64-bit product row x stride, a compare against the row limit,
+// a select of the zero page (which turns the address into a VGPR pair) or an
+// exec branch around the store.  In a launch whose lanes all hold a quad
+// (PassArgs::full_lanes) a wave whose rows all lie below the row limit needs
+// none of that: one base address per array (one product), the rows of
+// consecutive row registers a launch-constant stride apart (PassArgs::rs_in,
+// rs_seg, rs_out), every load and store in SGPR base + 32-bit lane offset
+// form.  One wave-uniform test per item picks the path; partial tiles and
+// slabs, absent rows, in_rows_mask and 64-bit lane offsets take the general
+// one.  The plain and encoder-gather loads and the plain and recovery stores
+// have it (T > 4: the passes of stripes above 2048 rows); DEC_MID's zero rows
+// and pruned stores, the decoder's gathers and the reveal stores do not.
+// ---------------------------------------------------------------------------
+template <int P, int T> struct FastRows {
+    using PT = ProgTraits<P>;
+    static constexpr bool LOAD = T > 4 && P != DEC_MID && (PT::LOAD == LD_PLAIN || PT::LOAD == LD_GATHER_ENC);
+    static constexpr bool STORE = T > 4 && P != DEC_MID && (PT::STORE == ST_PLAIN || PT::STORE == ST_RECOVERY);
+};
+// one past the last row of the wave (rows grow with the tile row k)
+template <int T, bool LB> __device__ __forceinline__ uint32_t wave_rows_end(const WaveRows<T, LB>& wr) {
+    using G = Geo<T>;
+    constexpr uint32_t kmax = LB ? (G::HWS - 1) + ((uint32_t)(G::NR - 1) << G::SHB) : ((uint32_t)G::HWS << G::R) - 1;
+    return wr.base + (kmax << wr.lo) + 1;
+}
+template <int P, int T>
+__device__ __forceinline__ bool load_rows_fast(const PassArgs& a, const Thr& c, uint32_t (&L)[Geo<T>::NR],
+                                               uint32_t (&H)[Geo<T>::NR]) {
+    constexpr bool START_B = !ProgTraits<P>::IFFT;
+    constexpr bool GATHER = ProgTraits<P>::LOAD == LD_GATHER_ENC;
+    const WaveRows<T, START_B> wr(c, a);
+    if (!a.full_lanes || (GATHER && wave_rows_end<T, START_B>(wr) > a.a_count)) return false;
+    const uint64_t S = GATHER ? a.S_seg : a.S_in, rs = GATHER ? a.rs_seg : a.rs_in;
+    const uint32_t voff = lane_rows<T, START_B>(c, a) * (uint32_t)S + c.offL;
+    uint64_t p = (uint64_t)(GATHER ? a.seg_a : a.in) + (uint64_t)wr.base * S;
+#pragma unroll
+    for (int m = 0; m < Geo<T>::NR; m++) {
+        const gu32* g = (const gu32*)(sgpr_ptr((const uint8_t*)p) + voff);
+        L[m] = g[0];
+        H[m] = g[8];
+        p += rs;
+    }
+    // (a block of its own: without the marker the compiler sinks the loads of
+    // this and the general paths into one shared block behind them, which
+    // takes its addresses as 64-bit VGPR pairs from whichever path ran)
+    asm volatile("; full-item rows requested");
+    return true;
+}
+// The stores' side: row register m at base + m x rs_out (launch_pass: the
+// offsets of all row registers fit 32 bits when full_lanes is set), in any
+// order -- the early stores come from inside the last layer block.
+template <int P, int T> struct FastStore {
+    static constexpr bool END_B = !ProgTraits<P>::FFT && T > 4;
+    const PassArgs& a;
+    const Thr& cs;
+    bool on;
+    uint64_t p;
+    __device__ __forceinline__ FastStore(const PassArgs& a_, const Thr& cs_) : a(a_), cs(cs_), on(false), p(0) {
+        if constexpr (FastRows<P, T>::STORE) {
+            const WaveRows<T, END_B> wr(cs, a);
+            on = a.full_lanes &&
+                 (ProgTraits<P>::STORE != ST_RECOVERY || wave_rows_end<T, END_B>(wr) <= a.out_rows);
+            p = (uint64_t)a.out + (uint64_t)wr.base * a.S_out;
+        }
+    }
+    __device__ __forceinline__ void row(int m, uint32_t L, uint32_t H) const {
+        // (the lane offset from cs.offL at each store, as the general path
+        // forms it: kept across the early stores' layer block it costs a VGPR)
+        const uint32_t voff = lane_rows<T, END_B>(cs, a) * (uint32_t)a.S_out + cs.offL;
+        gu32* g = (gu32*)(sgpr_ptr((const uint8_t*)(p + (uint32_t)m * (uint32_t)a.rs_out)) + voff);
+        if constexpr (ProgTraits<P>::ST_NT) {
+            __builtin_nontemporal_store(L, g);
+            __builtin_nontemporal_store(H, g + 8);
+        } else {
+            g[0] = L;
+            g[8] = H;
+        }
+    }
+};
+
+// ---------------------------------------------------------------------------
 // Table staging.  N tables of 5 x 16 B, table i taken from mul_tab entry
 // entry(i), spread over the workgroup's threads.  Split into issue (global
 // loads into registers, issued next to the tile's own loads so that their
@@ -818,14 +899,14 @@ __device__ __forceinline__ void set_item(Thr& c, const PassArgs& a, uint32_t ite
     // is a multiple of 8 all slabs of a tile run on one XCD (they share the
     // tile's twiddle tables in its L2) and consecutive tiles go to different
     // XCDs (tiles of uneven work spread evenly).
-    if ((a.ntiles & 7) == 0) {
-        const uint32_t i = item >> 3;
-        slab = i % a.nslab;
-        tile = (i / a.nslab) * 8 + (item & 7);
-    } else {
-        tile = item / a.nslab;
-        slab = item - tile * a.nslab;
-    }
+    // (Both forms in one branch-free sequence, the quotient by the launch
+    // constant nslab without a division (fast_div): a branch here would split
+    // the kernel-argument loads into a round before it and one behind it.)
+    const bool x8 = (a.ntiles & 7) == 0;
+    const uint32_t i = x8 ? item >> 3 : item;
+    const uint32_t q = fast_div(i, a.nslab_mul, a.nslab_one);
+    slab = i - q * a.nslab;
+    tile = x8 ? q * 8 + (item & 7) : q;
     const uint32_t Qg = slab * Q + c.qt;
     c.active = Qg < a.qrow;
     c.offL = (Qg >> 3) * 64 + (Qg & 7) * 4;
@@ -945,6 +1026,9 @@ __device__ __forceinline__ void load_item(const PassArgs& a, const Thr& c, uint3
             for (int j = 0; j < G::SETS; j++)
                 if ((zf[4 * j] & zf[4 * j + 1] & zf[4 * j + 2] & zf[4 * j + 3]) == 0x01010101u) d.zmask |= 1u << j;
         }
+    }
+    if constexpr (FastRows<P, T>::LOAD) {
+        if (load_rows_fast<P, T>(a, c, d.L, d.H)) return;
     }
     if (a.voff32) load_rows<P, T, true>(a, c, tile, d);
     else load_rows<P, T, false>(a, c, tile, d);
@@ -1115,7 +1199,13 @@ template <int P, int T> struct RcvCount {
         if constexpr (ON) {
             r0 = uni(row_rel<T>(c, a, 0) + 64u * c.w);
             go = first && a.rcount && c.w < NCH && (r0 & 63u) == 0;
-            if (go) f = !a.cnt_flags || a.cnt_flags[r0 + c.lane];
+            // (the raw byte: it is first looked at in count(), behind the
+            // row loads -- a test here would wait for it before they issue,
+            // and against a constant 1 the compiler moves count()'s test up
+            // to the load, hence the opaque one)
+            f = 1;
+            asm("" : "+v"(f));
+            if (go && a.cnt_flags) f = a.cnt_flags[r0 + c.lane];
         }
     }
     __device__ __forceinline__ void count() {
@@ -1184,9 +1274,13 @@ template <int P, int T> struct EarlyStore {
     const Thr& cs;
     const uint4* rvt;
     const uint32_t* lostf;
+    const FastStore<P, T> fs;
     __device__ __forceinline__ void operator()(const uint32_t (&L)[Geo<T>::NR], const uint32_t (&H)[Geo<T>::NR],
                                                int m) const {
-        if (a.voff32) {
+        if (fs.on) {
+            fs.row(m, L[m], H[m]);
+            fs.row(m + 1, L[m + 1], H[m + 1]);
+        } else if (a.voff32) {
             store_row<P, T, true>(a, cs, L[m], H[m], m, rvt, lostf);
             store_row<P, T, true>(a, cs, L[m + 1], H[m + 1], m + 1, rvt, lostf);
         } else {
@@ -1266,7 +1360,13 @@ __device__ __forceinline__ void ifft_b_halves(uint32_t (&L)[Geo<T>::NR], uint32_
 template <int P, int T> struct EvenStore {
     const PassArgs& a;
     const Thr& cs;
+    const FastStore<P, T> fs;
     __device__ __forceinline__ void operator()(const uint32_t (&L)[Geo<T>::NR], const uint32_t (&H)[Geo<T>::NR]) const {
+        if (fs.on) {
+#pragma unroll
+            for (int m = 0; m < Geo<T>::NR; m += 2) fs.row(m, L[m], H[m]);
+            return;
+        }
 #pragma unroll
         for (int m = 0; m < Geo<T>::NR; m += 2) {
             if (a.voff32) store_row<P, T, true>(a, cs, L[m], H[m], m, nullptr, nullptr);
@@ -1392,7 +1492,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
             if constexpr (EARLY_B) {
                 Thr cs = c;
                 asm volatile("" : "+v"(cs.offL));
-                ifft_b_halves<T>(L, H, tab1, EvenStore<P, T>{a, cs});
+                ifft_b_halves<T>(L, H, tab1, EvenStore<P, T>{a, cs, FastStore<P, T>(a, cs)});
             } else {
                 // (SHARED: the layout-B tables t >= TSPLIT sit beside the image)
                 const uint4* tab1b = SM::SHARED ? (const uint4*)(smem + SM::TABB_OFF) - G::TSPLIT * 5 : tab1;
@@ -1485,7 +1585,8 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
             Thr cs = c;
             asm volatile("" : "+v"(cs.offL));
             layers<P, T, NKF, false, 0, R, true, (TWO && !(SM::RESTAGE))>(L, H, c, a, tab1, tab2, 0,
-                                                                        EarlyStore<P, T>{a, cs, rvt, lostf});
+                                                                        EarlyStore<P, T>{a, cs, rvt, lostf,
+                                                                                         FastStore<P, T>(a, cs)});
         } else if (need) {
             layers<P, T, NKF, false, 0, R, true, (TWO && !(SM::RESTAGE))>(L, H, c, a, tab1, tab2);
         }
@@ -1512,8 +1613,12 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
     cs.b_high = uni(cs.b_high);
     asm volatile("" : "+s"(cs.b_low), "+s"(cs.b_high));
     asm volatile("" : "+v"(cs.offL));
-    if constexpr (EARLY_B) {
-        // (the even rows went out inside the last block)
+    const FastStore<P, T> fs(a, cs);
+    if (fs.on) {
+        // (EARLY_B: the even rows went out inside the last block)
+#pragma unroll
+        for (int m = EARLY_B ? 1 : 0; m < NR; m += EARLY_B ? 2 : 1) fs.row(m, L[m], H[m]);
+    } else if constexpr (EARLY_B) {
 #pragma unroll
         for (int m = 1; m < NR; m += 2) {
             if (a.voff32) store_row<P, T, true>(a, cs, L[m], H[m], m, rvt, lostf);
@@ -1550,7 +1655,7 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, ((P == DEC_SINGLE || P == DEC
     bool first_stripe = true;
     if (a.stripe_tiles) {
         // batched stripes: the stripe's arrays, the tile within the stripe
-        const uint32_t st = uni(tile / a.stripe_tiles);
+        const uint32_t st = uni(fast_div(tile, a.stripe_mul, a.stripe_one));
         first_stripe = st == 0;
         tile -= st * a.stripe_tiles;
         stripe_displace(a, st);
@@ -1634,7 +1739,9 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, ((P == DEC_SINGLE || P == DEC
 // kernel's address here is what instantiates it in that unit.
 // ---------------------------------------------------------------------------
 template <int P, int T, int NV = 0> PassKernel pass_entry() {
-    return {pass_kernel<P, T, NV>, Smem<P, T>::BYTES, Geo<T>::THREADS, Geo<T>::Q};
+    using PT = ProgTraits<P>;
+    return {pass_kernel<P, T, NV>, Smem<P, T>::BYTES, Geo<T>::THREADS, Geo<T>::Q,
+            !PT::IFFT ? Geo<T>::SHB : 0, (!PT::FFT && T > 4) ? Geo<T>::SHB : 0};
 }
 // the 12-lookup kernels of program P at T = 0 .. 8
 template <int P> PassKernel pass_row(int T) {

@@ -18,6 +18,9 @@ struct PassKernel {
     int lds;       // dynamic LDS bytes (Smem<P, T>::BYTES)
     int threads;   // Geo<T>::THREADS
     int quads;     // Geo<T>::Q, quads per tile row
+    // layout of the rows at the loads / at the stores: 0 = A (consecutive row
+    // registers are 1 << lo rows apart), else B (1 << (lo + SHB)): SHB
+    int load_shb, store_shb;
 };
 // Narrow-twiddle variants of the two-direction middle passes (NarrowVar,
 // rs16_pass.hpp): nv = 0 is the 12-lookup kernel that every (prog, T) has.

@@ -66,6 +66,16 @@ hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles
         a.voff32 = fits && aligned && !(a.diag & DIAG_FORCE_VOFF64) ? 1u : 0u;
         a.fd_lds = (a.diag & DIAG_FD_LDS) ? 1u : 0u;
     }
+    // The full-item fast path's launch constants (PassArgs::rs_in).
+    a.rs_in = a.S_in << (a.lo + k.load_shb);
+    a.rs_seg = a.S_seg << (a.lo + k.load_shb);
+    a.rs_out = a.S_out << (a.lo + k.store_shb);
+    // (16 row registers at most: the stores' offsets m x rs_out fit 32 bits)
+    const bool full = a.voff32 && a.qrow % k.quads == 0 && a.in_rows_mask == 0 && a.rs_out < ((uint64_t)1 << 28);
+    a.full_lanes = full ? 1u : 0u;
+    const FastDiv dn = fast_div_of(a.nslab), ds = fast_div_of(a.stripe_tiles);
+    a.nslab_mul = dn.mul, a.nslab_one = dn.one;
+    a.stripe_mul = ds.mul, a.stripe_one = ds.one;
     const size_t lds = (size_t)k.lds;
     if (lds > 65536) {
         // (per kernel variant: each is a function of its own)

@@ -29,6 +29,7 @@ SIGNATURES = {
     "rs16_host_mul_narrow": (None, [_p, _p, _sz, C.c_uint16]),
     "rs16_host_twiddle": (C.c_uint32, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rs16_host_twiddle_narrow": (C.c_int, [C.c_uint32]),
+    "rs16_host_fast_div_check": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "rs16_engine_set_profiling": (_i, [_p, _i, _e]),
     "rs16_engine_profile_read": (_i, [_p, _i, C.POINTER(C.c_double), C.POINTER(C.c_uint64), _e]),
     "rs16_engine_profile_reset": (None, [_p]),
