@@ -39,7 +39,16 @@ __device__ __forceinline__ void diag_stamp(const Args& a, int i) {
         __builtin_amdgcn_s_waitcnt(0);      \
         ::rs16::diag_stamp((args), 11);     \
     } while (0)
+// phase i reached once the rows m and m2 of the wave's first butterfly are in
+// its registers (the wave-staged passes: slot 6, which only the decoder's
+// formal derivative uses otherwise)
+#define RS16_STAMP_ROWS(args, i, L, H, m, m2)                                            \
+    do {                                                                                 \
+        asm volatile("" : "+v"((L)[m]), "+v"((H)[m]), "+v"((L)[m2]), "+v"((H)[m2]));      \
+        ::rs16::diag_stamp((args), (i));                                                 \
+    } while (0)
 #else
 #define RS16_STAMP(args, i) ((void)0)
+#define RS16_STAMP_ROWS(args, i, L, H, m, m2) ((void)0)
 #define RS16_STAMP_END(args) ((void)0)
 #endif

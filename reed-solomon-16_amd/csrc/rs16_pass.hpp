@@ -324,16 +324,23 @@ template <int T, bool LB> __device__ __forceinline__ uint32_t wave_rows_end(cons
     constexpr uint32_t kmax = LB ? (G::HWS - 1) + ((uint32_t)(G::NR - 1) << G::SHB) : ((uint32_t)G::HWS << G::R) - 1;
     return wr.base + (kmax << wr.lo) + 1;
 }
-template <int P, int T>
-__device__ __forceinline__ bool load_rows_fast(const PassArgs& a, const Thr& c, uint32_t (&L)[Geo<T>::NR],
-                                               uint32_t (&H)[Geo<T>::NR]) {
+// The row requests of the full-item form: row register m of the wave at base
+// + m x row stride, every load SGPR base + 32-bit lane offset.  `rows` false
+// (wave-uniform): 2 NR dwords of the zero page instead (row stride 0, the
+// lane's offset within the page as in ld_sel).  CLAMP: a lane without a quad
+// (partial last slab) requests the first quad of its slab -- a lane is a quad
+// column, nothing of it reaches another lane, and its stores are masked.
+template <int P, int T, bool CLAMP>
+__device__ __forceinline__ void request_rows(const PassArgs& a, const Thr& c, bool rows, uint32_t (&L)[Geo<T>::NR],
+                                             uint32_t (&H)[Geo<T>::NR]) {
     constexpr bool START_B = !ProgTraits<P>::IFFT;
     constexpr bool GATHER = ProgTraits<P>::LOAD == LD_GATHER_ENC;
     const WaveRows<T, START_B> wr(c, a);
-    if (!a.full_lanes || (GATHER && wave_rows_end<T, START_B>(wr) > a.a_count)) return false;
-    const uint64_t S = GATHER ? a.S_seg : a.S_in, rs = GATHER ? a.rs_seg : a.rs_in;
-    const uint32_t voff = lane_rows<T, START_B>(c, a) * (uint32_t)S + c.offL;
-    uint64_t p = (uint64_t)(GATHER ? a.seg_a : a.in) + (uint64_t)wr.base * S;
+    const uint64_t S = GATHER ? a.S_seg : a.S_in, rs = rows ? (GATHER ? a.rs_seg : a.rs_in) : 0;
+    // (offL = (Qg >> 3) * 64 + (Qg & 7) * 4 of the lane's quad Qg = slab * Q + qt, Q a multiple of 8)
+    const uint32_t offL = CLAMP && !c.active ? ((c.offL >> 6) - (c.qt >> 3)) * 64 : c.offL;
+    const uint32_t voff = rows ? lane_rows<T, START_B>(c, a) * (uint32_t)S + offL : (c.offL & 0x7FFFu);
+    uint64_t p = rows ? (uint64_t)(GATHER ? a.seg_a : a.in) + (uint64_t)wr.base * S : (uint64_t)a.zero;
 #pragma unroll
     for (int m = 0; m < Geo<T>::NR; m++) {
         const gu32* g = (const gu32*)(sgpr_ptr((const uint8_t*)p) + voff);
@@ -345,7 +352,46 @@ __device__ __forceinline__ bool load_rows_fast(const PassArgs& a, const Thr& c, 
     // this and the general paths into one shared block behind them, which
     // takes its addresses as 64-bit VGPR pairs from whichever path ran)
     asm volatile("; full-item rows requested");
+}
+template <int P, int T>
+__device__ __forceinline__ bool load_rows_fast(const PassArgs& a, const Thr& c, uint32_t (&L)[Geo<T>::NR],
+                                               uint32_t (&H)[Geo<T>::NR]) {
+    constexpr bool START_B = !ProgTraits<P>::IFFT;
+    constexpr bool GATHER = ProgTraits<P>::LOAD == LD_GATHER_ENC;
+    const WaveRows<T, START_B> wr(c, a);
+    if (!a.full_lanes || (GATHER && wave_rows_end<T, START_B>(wr) > a.a_count)) return false;
+    // (request_rows<P, T, false>(a, c, true, L, H) written out: through the
+    // call, 20 kernels outside the wave-staged ones compile to other code)
+    const uint64_t S = GATHER ? a.S_seg : a.S_in, rs = GATHER ? a.rs_seg : a.rs_in;
+    const uint32_t voff = lane_rows<T, START_B>(c, a) * (uint32_t)S + c.offL;
+    uint64_t p = (uint64_t)(GATHER ? a.seg_a : a.in) + (uint64_t)wr.base * S;
+#pragma unroll
+    for (int m = 0; m < Geo<T>::NR; m++) {
+        const gu32* g = (const gu32*)(sgpr_ptr((const uint8_t*)p) + voff);
+        L[m] = g[0];
+        H[m] = g[8];
+        p += rs;
+    }
+    asm volatile("; full-item rows requested");  // (a block of its own, see request_rows)
     return true;
+}
+// How a wave of a wave-staged pass (pass_kernel) gets its rows.  Those passes
+// issue request_rows on every path, so the form covers what it can: DIRECT,
+// the rows themselves -- any launch with 32-bit lane offsets and no row mask,
+// partial slabs included (CLAMP), when the wave's rows lie below the gather's
+// row limit; ZERO, a gather wave wholly at or above the limit: the zero page,
+// which is its data; GENERAL, the rest (a wave that straddles the limit,
+// 64-bit lane offsets, in_rows_mask): the zero page, then load_rows on top.
+enum RowsMode { ROWS_DIRECT = 0, ROWS_ZERO, ROWS_GENERAL };
+template <int P, int T>
+__device__ __forceinline__ uint32_t wave_rows_mode(const PassArgs& a, const Thr& c) {
+    constexpr bool START_B = !ProgTraits<P>::IFFT;
+    constexpr bool GATHER = ProgTraits<P>::LOAD == LD_GATHER_ENC;
+    const WaveRows<T, START_B> wr(c, a);
+    const bool below = !GATHER || wave_rows_end<T, START_B>(wr) <= a.a_count;
+    const bool above = GATHER && wr.base >= a.a_count;  // (the wave's lowest row)
+    const bool direct = (a.voff32 != 0) & (a.in_rows_mask == 0) & below;
+    return direct ? ROWS_DIRECT : (above ? ROWS_ZERO : ROWS_GENERAL);
 }
 // The stores' side: row register m at base + m x rs_out (launch_pass: the
 // offsets of all row registers fit 32 bits when full_lanes is set), in any
@@ -409,6 +455,52 @@ template <int T, int N> struct Stager {
         }
     }
 };
+
+// Wave-private staging (the encoder-family passes at T >= 7, the cut of the
+// slot-priority code in pass_kernel): no workgroup barrier stands between a
+// wave's row loads and its first layers.  The tables of the first layer block
+// are requested and committed by the wave that reads them -- in layout A the
+// 2^R - 1 tables of each of its own row sets (group_table: t = offset(kb) +
+// (s << (R-1-kb)) + gi), in layout B (ENC_LAST) the block's shared tables,
+// which every wave writes with the same values -- and ordered by
+// wave_lds_publish().  Every other table is committed by the thread that
+// requested it without a barrier of its own: its first reader stands behind
+// the barriers of the first layout switch.
+template <int P, int T> struct WaveStaged {
+    static constexpr bool value = (P == ENC_FIRST || P == ENC_MID || P == ENC_LAST) && T >= 7;
+};
+// N tables per wave, spread over its 64 lanes: table i = entry(i) of `tabs`,
+// committed to table slot slot(i) of dst.
+template <int N> struct WaveStager {
+    static constexpr int PER = (N * 5 + 63) / 64;
+    u32x4 v[PER > 0 ? PER : 1];
+    template <class F> __device__ __forceinline__ void issue(const uint32_t* tabs, uint32_t lane, F entry) {
+        const u32x4* tab = (const u32x4*)tabs;
+#pragma unroll
+        for (int i = 0; i < PER; i++) {
+            const int idx = (int)lane + i * 64;
+            if (idx < N * 5) v[i] = tab[(size_t)entry(idx / 5) * (TAB_DWORDS / 4) + idx % 5];
+        }
+    }
+    template <class F> __device__ __forceinline__ void commit(uint4* dst, uint32_t lane, F slot) const {
+        u32x4* d = (u32x4*)dst;
+#pragma unroll
+        for (int i = 0; i < PER; i++) {
+            const int idx = (int)lane + i * 64;
+            if (idx < N * 5) d[slot(idx / 5) * 5 + idx % 5] = v[i];
+        }
+    }
+};
+// What a wave's lanes wrote to LDS is visible to the wave's other lanes: the
+// LDS executes a wave's instructions in order, the wait retires the writes,
+// and the wave-scope fences keep the compiler from moving a lane's table
+// reads above its writes (to it they are other addresses).
+__device__ __forceinline__ void wave_lds_publish() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0) only
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // Twiddle of tile group t (t in [0, 2^T - 1)) as an index of skew_tab (the
 // v_perm table of every skew entry, so staging is one load deep): layer kb with
@@ -1040,7 +1132,8 @@ __device__ __forceinline__ void load_item(const PassArgs& a, const Thr& c, uint3
 // FWHT of eval_poly when the caller left it undone, ework).  In two steps:
 // issue() sends the twiddle-table loads (one level deep, from skew_tab), so
 // the caller can issue the tile's data loads behind them; finish() stages the
-// per-row multipliers, writes everything to LDS and ends with a barrier.  The
+// per-row multipliers, writes everything to LDS and ends with a barrier (the
+// wave-staged passes: with wave_lds_publish(), see WaveStaged).  The
 // caller must have a barrier between the previous key's last use of these
 // LDS regions and finish().
 // Reveal multipliers (65535 - e of the lost originals) and lost-row flags of
@@ -1082,11 +1175,38 @@ template <int P, int T> struct TileStage {
     static constexpr bool S2 = N2 > 0;
     // (SHARED: the first direction's layout-A tables into the image region,
     // its layout-B tables beside it)
-    static constexpr int N1 = SM::SHARED ? G::TSPLIT : G::NTAB;
-    static constexpr int N1B = SM::SHARED ? G::NTAB - G::TSPLIT : 0;
+    // Wave-private staging (WaveStaged): WS_A, the first block runs in layout
+    // A -- the wave stages its row sets' layout-A tables (sw), the workgroup
+    // the first direction's layout-B ones (s1b); WS_B, it runs in layout B
+    // (ENC_LAST) -- every wave stages the layout-B tables (sw, into the shared
+    // slots: a copy per wave would add 4.5 KiB of LDS to a layout that has
+    // 6 KiB left under ONE_ROUND_MAX, for values that are the same anyway), the
+    // workgroup the layout-A ones (s1).
+    static constexpr bool WS = WaveStaged<P, T>::value;
+    static constexpr bool WS_A = WS && PT::IFFT, WS_B = WS && !PT::IFFT;
+    static_assert(!WS || (T > 4 && G::R == 4 && PT::LOAD != LD_GATHER_DEC && PT::STORE != ST_RESTORE),
+                  "wave-private staging: 16-row sets, twiddle tables only");
+    static constexpr int N1 = WS_A ? 0 : (SM::SHARED || WS_B ? G::TSPLIT : G::NTAB);
+    static constexpr int N1B = SM::SHARED || WS_A ? G::NTAB - G::TSPLIT : 0;
+    static constexpr int NW = WS_A ? G::HWS * (G::NR - 1) : (WS_B ? G::NTAB - G::TSPLIT : 0);
     Stager<T, N1> s1;
     Stager<T, N1B> s1b;
     Stager<T, N2> s2;
+    WaveStager<NW> sw;
+    // tile group id of the wave's table i
+    static __device__ __forceinline__ uint32_t wave_group(const Thr& c, int i) {
+        if constexpr (WS_A) {
+            // table i15 of row set hs: layer kb = R - 1 - floor(log2(2^R - 1 - i15))
+            constexpr int NA = G::NR - 1, R = G::R;
+            const int hs = i / NA, i15 = i - hs * NA;
+            const int kb = R - 32 + __clz((uint32_t)(NA - i15));
+            const uint32_t gi = (uint32_t)(i15 - ((1 << R) - (1 << (R - kb))));
+            const uint32_t s = c.w * G::HWS + (uint32_t)hs;
+            return (uint32_t)((1 << T) - (1 << (T - kb))) + (s << (R - 1 - kb)) + gi;
+        } else {
+            return (uint32_t)(G::TSPLIT + i);
+        }
+    }
 
     uint32_t ev[4];  // wave 0: the tile's 256-row block of eval_poly's work (ework)
     // decoder gather: the received-bitmap words of this thread's erasure-table
@@ -1118,6 +1238,11 @@ template <int P, int T> struct TileStage {
                 const uint32_t k = min(idx / 5, (1u << T) - 1);
                 rw[i] = a.rbits[(row_rel<T>(c, a, k) + a.row_base_in) >> 5];
             }
+        }
+        // (the wave's own tables first: its first layers wait for them alone)
+        if constexpr (WS) {
+            const TwiddleEntry<T> tw{a, c, 0, PT::IFFT ? a.skew_ifft : a.skew_fft};
+            sw.issue(a.skew_tab, c.lane, [&](int i) { return tw((int)wave_group(c, i)); });
         }
         s1.issue(a.skew_tab, TwiddleEntry<T>{a, c, 0, PT::IFFT ? a.skew_ifft : a.skew_fft});
         if constexpr (N1B > 0) s1b.issue(a.skew_tab, TwiddleEntry<T>{a, c, G::TSPLIT, a.skew_ifft});
@@ -1174,6 +1299,18 @@ template <int P, int T> struct TileStage {
             rs.issue(a, c, el);
             rs.commit(smem);
         }
+        if constexpr (WS) {
+            // The wave's own tables, then the tables of the later blocks (all
+            // requested ahead of the rows: one vmcnt wait that leaves every
+            // row load in flight).  The latter are first read behind the
+            // barriers of the first layout switch, so this ends without one.
+            sw.commit((uint4*)(smem + SM::TAB1_OFF), c.lane, [&](int i) { return wave_group(c, i); });
+            if constexpr (S2) s2.commit((uint4*)(smem + SM::TAB2_OFF));
+            s1.commit((uint4*)(smem + SM::TAB1_OFF));
+            s1b.commit((uint4*)(smem + (SM::SHARED ? SM::TABB_OFF : SM::TAB1_OFF + G::TSPLIT * 80)));
+            wave_lds_publish();
+            return;
+        }
         if constexpr (S2) s2.commit((uint4*)(smem + SM::TAB2_OFF));
         s1.commit((uint4*)(smem + SM::TAB1_OFF));
         if constexpr (N1B > 0) s1b.commit((uint4*)(smem + SM::TABB_OFF));
@@ -1186,9 +1323,9 @@ template <int P, int T> struct TileStage {
 // slab's workgroup counts chunk j of its tile (a tile below 64 rows: the
 // chunk's first tile counts it).  Behind uniform branches: the flag bytes
 // are the workgroup's first loads (so the compiler's waits for the later
-// loads do not change), the ballots run after the staging barrier (the bytes
-// are older than the tables it waited for) and the counts, in SGPRs, are
-// stored after the item.
+// loads do not change), the ballots run after the tables are staged (the
+// bytes are older than the table loads that the staging waited for, with or
+// without its barrier) and the counts, in SGPRs, are stored after the item.
 template <int P, int T> struct RcvCount {
     static constexpr bool ON = P == ENC_FIRST || P == ENC_LAST;
     static constexpr uint32_t NCH = (1u << T) >= 64 ? (1u << T) / 64 : 1;
@@ -1461,6 +1598,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
         // DEC_MID: a wave whose rows all are zero skips its layout-A layers
         bool skip_a = false;
         if constexpr (ZERO_SKIP) skip_a = __all(d.zrow == (1u << NR) - 1);
+        if constexpr (WaveStaged<P, T>::value) RS16_STAMP_ROWS(a, 6, L, H, 0, 1);
         if (!skip_a) layers<P, T, NKI, false, 0, R, false, false>(L, H, c, a, tab1, tab2);
         RS16_STAMP(a, 3);
         prio<1>();
@@ -1518,6 +1656,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
     // ---------------- FFT ----------------
     if constexpr (PT::FFT) {
         if constexpr (T > 4) {
+            if constexpr (WaveStaged<P, T>::value && !PT::IFFT) RS16_STAMP_ROWS(a, 6, L, H, 0, NR / 2);
             layers<P, T, NKF, true, R, (T > 4 ? T : R), true, TWO, (P == DEC_MID ? PR_OUT : PR_NONE)>(L, H, c, a, tab1,
                                                                                                   tab2);
             if constexpr (SPLIT_FD) {
@@ -1713,7 +1852,35 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, ((P == DEC_SINGLE || P == DEC
     constexpr bool EARLY = ProgTraits<P>::LOAD == LD_GATHER_DEC;
     if constexpr (EARLY) st.gather(a, c, smem);
     ItemRegs<P, T> cur;
-    load_item<P, T>(a, c, tile, cur);
+    if constexpr (WaveStaged<P, T>::value) {
+        // The full-item loads on every path, the general ones on top of them
+        // where the wave needs those.  The compiled form of "if (full) fast
+        // loads else general loads" is two guarded blocks in a row, and with
+        // them comes an edge around both (never taken) on which no row load
+        // was issued at all: the wait for the staged tables, which counts the
+        // loads behind them on the poorest path to it, was vmcnt(0) -- a wave
+        // waited for its last row before it committed its tables.  With one
+        // guarded block the poorest path is the full item's own: the wait
+        // leaves its 2 NR row loads in flight, and each row is waited for at
+        // its first use.  The price is on the GENERAL waves (wave_rows_mode:
+        // a wave across the gather's row limit, 64-bit lane offsets, a row
+        // mask): they request 2 NR dwords of the zero page first, and the
+        // guarded block, which reuses those registers for its addresses,
+        // waits for them to return before it requests the rows -- one more
+        // round trip to the cache.  Partial slabs are not among them.
+        static_assert(FastRows<P, T>::LOAD, "the encoder-family passes have the full-item loads");
+        cur.zrow = cur.zmask = 0;
+        cur.ztile = false;
+        const uint32_t mode = uni(wave_rows_mode<P, T>(a, c));
+        request_rows<P, T, true>(a, c, mode == ROWS_DIRECT, cur.L, cur.H);
+        if (mode == ROWS_GENERAL) {
+            if (a.voff32) load_rows<P, T, true>(a, c, tile, cur);
+            else load_rows<P, T, false>(a, c, tile, cur);
+            asm volatile("; general rows requested");
+        }
+    } else {
+        load_item<P, T>(a, c, tile, cur);
+    }
     if constexpr (P == DEC_MID) {
         // Only the last pass's tiles that hold a lost original are consumed:
         // tile row k = rows [k << lo, (k + 1) << lo) (read with the rows in flight)

@@ -7,8 +7,9 @@ of workgroup start / end times (s_memrealtime, 100 MHz) and the median
 duration of each phase of a workgroup (s_memtime cycles at the workgroup's
 own clock).  Phases (rs16_pass.hpp RS16_STAMP): 0 start, 1 loads issued,
 2 tables staged, 3 first layout-A layers, 4 layout switch, 5 first
-direction done, 6 formal derivative, 7 layout-B FFT layers, 8 layout
-switch, 9 last layers, 10 stores issued, 11 stores done; EVAL_POLY (the
+direction done, 6 formal derivative (the wave-staged encoder passes: wave
+0's first butterfly, reported as "start->first butterfly"), 7 layout-B FFT
+layers, 8 layout switch, 9 last layers, 10 stores issued, 11 stores done; EVAL_POLY (the
 n <= 2048 eval kernel, rs16_misc.hip): 0 start, 1 flags in, 2 sums done,
 10 store issued, 11 store done.  Programs: RS16_STAMP_PROGS (comma list);
 size: argv[1] (k = m); loss pattern: RS16_STAMPS_LOSS, RS16_STAMPS_SCATTER
@@ -29,6 +30,8 @@ from rs16.device import DeviceArray  # noqa: E402
 from rs16.util import generate_original  # noqa: E402
 
 PH = ["start", "loads", "staged", "A-layers", "switch1", "dir1", "fd", "B-fft", "switch2", "last", "stores", "drain"]
+# programs whose slot 6 is "first butterfly" (RS16_STAMP_ROWS), not "fd"
+FIRST_BFLY = ("ENC_FIRST", "ENC_MID", "ENC_LAST", "DEC_HALF_FIRST", "DEC_HALF_MID", "DEC_HALF_LAST")
 # the column codec (rs16_col.hip cstamp)
 PH_COL = ["start", "issued", "staged", "iblk0", "iblk2", "ifft", "fblk0", "fblk2", "fxchg3", "fft", "stores", "drain"]
 
@@ -95,6 +98,12 @@ def main():
         ghz = (st[:, 11] - st[:, 0]) / np.maximum((st[:, 15] - st[:, 14]) * 10.0, 1)  # cycles per ns
         rec = [p for p in range(12) if (st[:, p] != 0).all()]
         phases = {}
+        # the wave-staged passes (encoder family, T >= 7) stamp slot 6 when the
+        # rows of wave 0's first butterfly are in its registers: a column of
+        # its own, not a link of the phase chain
+        if name in FIRST_BFLY and 6 in rec:
+            rec.remove(6)
+            phases["start->first butterfly"] = round(float(np.median((st[:, 6] - st[:, 0]) / ghz / 1000.0)), 2)
         for a, b in zip(rec, rec[1:]):
             dur = (st[:, b] - st[:, a]) / ghz / 1000.0  # us
             ph = PH_COL if name.startswith("COL") else PH
