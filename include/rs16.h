@@ -133,7 +133,8 @@ int rs16_engine_formal_derivative(rs16_engine* eng, void* data, size_t shard_cou
 typedef enum rs16_rate { RS16_RATE_DEFAULT = 0, RS16_RATE_HIGH = 1, RS16_RATE_LOW = 2 } rs16_rate;
 /* Rate::supports / ReedSolomonEncoder::supports (src/reed_solomon.rs:76-84). */
 int rs16_supports(int rate, size_t original_count, size_t recovery_count);
-/* Rate::validate (src/rate.rs:91-106). */
+/* Rate::validate (src/rate.rs:91-106).  Shards of 4 GiB or more are an
+ * invalid shard size here (the kernels keep row strides in 32 bits). */
 int rs16_validate(int rate, size_t original_count, size_t recovery_count, size_t shard_bytes, rs16_error* err);
 /* use_high_rate (src/rate/rate_default.rs:15-64): 1 high, 0 low, -1 error. */
 int rs16_use_high_rate(size_t original_count, size_t recovery_count, rs16_error* err);
@@ -506,6 +507,13 @@ void rs16_device_free(rs16_engine* eng, void* d_ptr);
 int rs16_memcpy_htod(rs16_engine* eng, void* d_dst, const void* src, size_t bytes, void* stream, rs16_error* err);
 int rs16_memcpy_dtoh(rs16_engine* eng, void* dst, const void* d_src, size_t bytes, void* stream, rs16_error* err);
 int rs16_memset_device(rs16_engine* eng, void* d_dst, int value, size_t bytes, void* stream, rs16_error* err);
+/* Pitched copies (hipMemcpy2DAsync, then a wait): `rows` rows of `width`
+ * bytes, row i at d + i * d_pitch on the device and h + i * h_pitch on the
+ * host -- a column block of every row of a wide array in one call. */
+int rs16_memcpy2d_htod(rs16_engine* eng, void* d_dst, size_t d_pitch, const void* src, size_t h_pitch, size_t width,
+                       size_t rows, void* stream, rs16_error* err);
+int rs16_memcpy2d_dtoh(rs16_engine* eng, void* dst, size_t h_pitch, const void* d_src, size_t d_pitch, size_t width,
+                       size_t rows, void* stream, rs16_error* err);
 /* Streams (hipStream_t, non-blocking) on the engine's device, for callers
  * without HIP headers that run codecs on streams of their own. */
 void* rs16_stream_create(rs16_engine* eng, rs16_error* err);
@@ -594,6 +602,38 @@ int rs16_host_twiddle_narrow(uint32_t index);
  * i * step, i < count (stopping at 2^32), whose quotient by `divisor` (>= 1)
  * differs from n / divisor. */
 uint64_t rs16_host_fast_div_check(uint32_t divisor, uint32_t n0, uint32_t count, uint32_t step);
+/* The launch constants by which a pass launch picks its address forms, as
+ * the launcher computes them (one host function, which every launch calls;
+ * no device needed), and the geometry of the kernel of pass program `prog`
+ * (rs16_prog_name; the profiling-only ids have no kernel) at tile bits T:
+ *   voff32      1: every lane's byte offset below its wave's row base fits 32
+ *               bits (SGPR base + 32-bit lane offset), 0: 64-bit lane offsets
+ *   full_lanes  1: the launch's waves may take the full-item fast path
+ *   rs_in, rs_seg, rs_out   its byte strides between consecutive row registers
+ *   nslab       slabs of `quads` quads per row
+ *   quads, threads          quads per tile row, threads per workgroup
+ *   load_shb, store_shb     0: rows loaded / stored in layout A, else in layout
+ *               B, consecutive row registers 2^shb tile rows apart
+ *   reg_bits, row_sets      row bits a thread holds in registers (R), row sets
+ *               per wave (HWS): a lane's rows start up to (HWS - 1) 2^R << lo
+ *               (layout A) or (HWS - 1) << lo (layout B) rows below its wave's
+ * from the stride exponent `lo`, the four row strides (bytes), the slice width
+ * `qrow` (quads of 8 bytes), the decoder's segment boundary `chunk` and first
+ * gather row `row_base_in`, the plain loads' row mask and the RS16_DIAG_*
+ * flags.  Returns 1, or 0 when (prog, T) has no kernel (*out untouched). */
+typedef struct rs16_pass_consts {
+    uint32_t voff32, full_lanes, nslab;
+    uint32_t quads, threads, load_shb, store_shb, reg_bits, row_sets;
+    uint64_t rs_in, rs_seg, rs_out;
+} rs16_pass_consts;
+int rs16_host_pass_consts(int prog, int T, uint32_t lo, uint64_t s_in, uint64_t s_out, uint64_t s_seg, uint64_t s_rest,
+                          uint32_t qrow, uint32_t chunk, uint32_t row_base_in, uint32_t in_rows_mask, int diag,
+                          rs16_pass_consts* out);
+/* The same for n launches that differ in their strides and slice width only
+ * (arrays of n; out[i] for launch i): sweeps of many widths in one call. */
+int rs16_host_pass_consts_many(int prog, int T, uint32_t lo, size_t n, const uint64_t* s_in, const uint64_t* s_out,
+                               const uint64_t* s_seg, const uint64_t* s_rest, const uint32_t* qrow, uint32_t chunk,
+                               uint32_t row_base_in, uint32_t in_rows_mask, int diag, rs16_pass_consts* out);
 
 /* Library/build identification, e.g. "rs16-mi355x gfx950". */
 const char* rs16_version(void);

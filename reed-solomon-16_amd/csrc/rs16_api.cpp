@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "rs16_engine.hpp"
+#include "rs16_pass_common.hpp"
 
 using namespace rs16;
 
@@ -112,6 +113,35 @@ extern "C" uint64_t rs16_host_fast_div_check(uint32_t divisor, uint32_t n0, uint
     for (uint64_t i = 0, n = n0; i < count && n < ((uint64_t)1 << 32); i++, n += step)
         bad += fast_div((uint32_t)n, f.mul, f.one) != (uint32_t)n / divisor;
     return bad;
+}
+
+extern "C" int rs16_host_pass_consts_many(int prog, int T, uint32_t lo, size_t n, const uint64_t* s_in,
+                                          const uint64_t* s_out, const uint64_t* s_seg, const uint64_t* s_rest,
+                                          const uint32_t* qrow, uint32_t chunk, uint32_t row_base_in,
+                                          uint32_t in_rows_mask, int diag, rs16_pass_consts* out) {
+    if (prog < 0 || prog >= NUM_PROGS || T < 0 || T > 8 || !out) return 0;
+    const PassKernel& k = pass_kernel_of(prog, T);
+    if (!k.fn) return 0;
+    PassArgs a{};
+    a.lo = lo, a.chunk = chunk, a.row_base_in = row_base_in, a.in_rows_mask = in_rows_mask;
+    a.diag = (uint32_t)diag;
+    for (size_t i = 0; i < n; i++) {
+        a.S_in = s_in[i], a.S_out = s_out[i], a.S_seg = s_seg[i], a.S_rest = s_rest[i], a.qrow = qrow[i];
+        const PassConsts c = pass_launch_consts(k, T, a);  // (the function launch_pass calls)
+        rs16_pass_consts& o = out[i];
+        o.voff32 = c.voff32, o.full_lanes = c.full_lanes, o.nslab = c.nslab;
+        o.quads = (uint32_t)k.quads, o.threads = (uint32_t)k.threads;
+        o.load_shb = (uint32_t)k.load_shb, o.store_shb = (uint32_t)k.store_shb;
+        o.reg_bits = (uint32_t)k.reg_bits, o.row_sets = k.quads >= 64 ? 1u : 64u / (uint32_t)k.quads;
+        o.rs_in = c.rs_in, o.rs_seg = c.rs_seg, o.rs_out = c.rs_out;
+    }
+    return 1;
+}
+extern "C" int rs16_host_pass_consts(int prog, int T, uint32_t lo, uint64_t s_in, uint64_t s_out, uint64_t s_seg,
+                                     uint64_t s_rest, uint32_t qrow, uint32_t chunk, uint32_t row_base_in,
+                                     uint32_t in_rows_mask, int diag, rs16_pass_consts* out) {
+    return rs16_host_pass_consts_many(prog, T, lo, 1, &s_in, &s_out, &s_seg, &s_rest, &qrow, chunk, row_base_in,
+                                      in_rows_mask, diag, out);
 }
 
 extern "C" int rs16_engine_set_profiling(rs16_engine* e, int enable, rs16_error* err) {
@@ -227,7 +257,8 @@ extern "C" int rs16_supports(int rate, size_t k, size_t m) {
 
 extern "C" int rs16_validate(int rate, size_t k, size_t m, size_t S, rs16_error* err) {  // src/rate.rs:91-106
     if (!rs16_supports(rate, k, m)) return set_error(err, RS16_UNSUPPORTED_SHARD_COUNT, k, m);
-    if (S == 0 || (S & 63) != 0) return set_error(err, RS16_INVALID_SHARD_SIZE, S);
+    // (from 4 GiB on the kernels' 32-bit stride arithmetic would wrap: not supported)
+    if (S == 0 || (S & 63) != 0 || (uint64_t)S >> 32) return set_error(err, RS16_INVALID_SHARD_SIZE, S);
     return set_error(err, RS16_OK);
 }
 
@@ -1904,6 +1935,24 @@ extern "C" int rs16_memcpy_dtoh(rs16_engine* e, void* dst, const void* src, size
     if (int rc = e->activate(err)) return rc;
     hipStream_t s = e->pick(stream);
     RS16_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+    RS16_HIP(hipStreamSynchronize(s));
+    return set_error(err, RS16_OK);
+}
+extern "C" int rs16_memcpy2d_htod(rs16_engine* e, void* dst, size_t d_pitch, const void* src, size_t h_pitch,
+                                  size_t width, size_t rows, void* stream, rs16_error* err) {
+    if (width > d_pitch || width > h_pitch) return set_error(err, RS16_INVALID_ARGUMENT);
+    if (int rc = e->activate(err)) return rc;
+    hipStream_t s = e->pick(stream);
+    RS16_HIP(hipMemcpy2DAsync(dst, d_pitch, src, h_pitch, width, rows, hipMemcpyHostToDevice, s));
+    RS16_HIP(hipStreamSynchronize(s));
+    return set_error(err, RS16_OK);
+}
+extern "C" int rs16_memcpy2d_dtoh(rs16_engine* e, void* dst, size_t h_pitch, const void* src, size_t d_pitch,
+                                  size_t width, size_t rows, void* stream, rs16_error* err) {
+    if (width > d_pitch || width > h_pitch) return set_error(err, RS16_INVALID_ARGUMENT);
+    if (int rc = e->activate(err)) return rc;
+    hipStream_t s = e->pick(stream);
+    RS16_HIP(hipMemcpy2DAsync(dst, h_pitch, src, d_pitch, width, rows, hipMemcpyDeviceToHost, s));
     RS16_HIP(hipStreamSynchronize(s));
     return set_error(err, RS16_OK);
 }

@@ -1908,7 +1908,7 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, ((P == DEC_SINGLE || P == DEC
 template <int P, int T, int NV = 0> PassKernel pass_entry() {
     using PT = ProgTraits<P>;
     return {pass_kernel<P, T, NV>, Smem<P, T>::BYTES, Geo<T>::THREADS, Geo<T>::Q,
-            !PT::IFFT ? Geo<T>::SHB : 0, (!PT::FFT && T > 4) ? Geo<T>::SHB : 0};
+            !PT::IFFT ? Geo<T>::SHB : 0, (!PT::FFT && T > 4) ? Geo<T>::SHB : 0, Geo<T>::R};
 }
 // the 12-lookup kernels of program P at T = 0 .. 8
 template <int P> PassKernel pass_row(int T) {

@@ -21,7 +21,21 @@ struct PassKernel {
     // layout of the rows at the loads / at the stores: 0 = A (consecutive row
     // registers are 1 << lo rows apart), else B (1 << (lo + SHB)): SHB
     int load_shb, store_shb;
+    int reg_bits;  // Geo<T>::R, row bits held in registers (2^R rows per thread)
 };
+// The launch constants that decide a launch's address forms (the PassArgs
+// fields of the same names), as launch_pass sets them from the kernel's
+// geometry and the launch's strides, slice width, stride exponent, row
+// alignment and diag flags.  Host arithmetic only: rs16_host_pass_consts
+// (include/rs16.h) shows it to tests without a device.
+struct PassConsts {
+    uint32_t nslab, voff32, full_lanes;
+    uint64_t rs_in, rs_seg, rs_out;
+};
+PassConsts pass_launch_consts(const PassKernel& k, int T, const PassArgs& a);
+// The 12-lookup kernel of (prog, T) (fn nullptr: none), whose geometry every
+// narrow variant of (prog, T) shares.
+const PassKernel& pass_kernel_of(int prog, int T);
 // Narrow-twiddle variants of the two-direction middle passes (NarrowVar,
 // rs16_pass.hpp): nv = 0 is the 12-lookup kernel that every (prog, T) has.
 constexpr int NARROW_VARIANTS = 4;

@@ -39,6 +39,39 @@ static const PassKernel& pick_kernel(int prog, int T, int ni, int nf) {
     return find_kernel(prog, T, 0);
 }
 
+const PassKernel& pass_kernel_of(int prog, int T) { return find_kernel(prog, T, 0); }
+
+PassConsts pass_launch_consts(const PassKernel& k, int T, const PassArgs& a) {
+    PassConsts c;
+    c.nslab = (a.qrow + k.quads - 1) / k.quads;
+    {
+        const uint64_t hws = k.quads >= 64 ? 1 : 64 / k.quads;
+        const uint64_t smax = std::max(std::max(a.S_in, a.S_out), std::max(a.S_seg, a.S_rest));
+        const uint64_t span = (uint64_t)1 << (T + a.lo);  // rows of one tile's aligned block
+        // A lane's byte offset below its wave's row base is lane_rows x S +
+        // offL (rs16_pass.hpp LaneOff): lane_rows, the rows from the wave's
+        // first row set to the lane's, at most (hws - 1) 2^R << lo in layout A
+        // (2^R <= 16 rows per row set; layout B: (hws - 1) << lo), S any of
+        // the four strides, offL the lane's quad within the slice, whose high
+        // dword ends at 8 qrow: the last byte a lane touches lies at most at
+        // (hws - 1) (16 << lo) smax + 8 qrow - 1, which has to stay below 2^32.
+        // (With one row set per wave, T = 7 and T <= 4, the offset is offL
+        // alone.  A lane without a quad forms a larger offset and uses none.)
+        const bool fits = (hws - 1) * ((uint64_t)16 << a.lo) * smax + 8 * (uint64_t)a.qrow <= ((uint64_t)1 << 32);
+        const bool aligned = a.chunk % span == 0 && a.row_base_in % span == 0;
+        // (RS16_DIAG_FORCE_VOFF64: always the 64-bit lane offsets)
+        c.voff32 = fits && aligned && !(a.diag & DIAG_FORCE_VOFF64) ? 1u : 0u;
+    }
+    // The full-item fast path's launch constants (PassArgs::rs_in).
+    c.rs_in = a.S_in << (a.lo + k.load_shb);
+    c.rs_seg = a.S_seg << (a.lo + k.load_shb);
+    c.rs_out = a.S_out << (a.lo + k.store_shb);
+    // (16 row registers at most: the stores' offsets m x rs_out fit 32 bits)
+    const bool full = c.voff32 && a.qrow % k.quads == 0 && a.in_rows_mask == 0 && c.rs_out < ((uint64_t)1 << 28);
+    c.full_lanes = full ? 1u : 0u;
+    return c;
+}
+
 hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles, hipStream_t s) {
     if (prog < 0 || prog >= NUM_PROGS || T < 0 || T > 8) return hipErrorInvalidValue;
     if (num_tiles == 0 || args.qrow == 0) return hipSuccess;
@@ -52,27 +85,15 @@ hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles
         nf = first_narrow_layer(a.lo, T, a.skew_fft, bh_max);
     }
     const PassKernel& k = pick_kernel(prog, T, ni, nf);
-    a.nslab = (a.qrow + k.quads - 1) / k.quads;
+    const PassConsts pc = pass_launch_consts(k, T, a);
+    a.nslab = pc.nslab;
     a.ntiles = num_tiles;
     const uint32_t nwg = num_tiles * a.nslab;  // one workgroup per (tile, slab) item
     if (a.need_hi == 0) a.need_hi = 1u << T;  // no pruning
-    {
-        const uint64_t hws = k.quads >= 64 ? 1 : 64 / k.quads;
-        const uint64_t smax = std::max(std::max(a.S_in, a.S_out), std::max(a.S_seg, a.S_rest));
-        const uint64_t span = (uint64_t)1 << (T + a.lo);  // rows of one tile's aligned block
-        const bool fits = (hws - 1) * ((uint64_t)16 << a.lo) * smax + 1024 < ((uint64_t)1 << 32);
-        const bool aligned = a.chunk % span == 0 && a.row_base_in % span == 0;
-        // (RS16_DIAG_FORCE_VOFF64: always the 64-bit lane offsets)
-        a.voff32 = fits && aligned && !(a.diag & DIAG_FORCE_VOFF64) ? 1u : 0u;
-        a.fd_lds = (a.diag & DIAG_FD_LDS) ? 1u : 0u;
-    }
-    // The full-item fast path's launch constants (PassArgs::rs_in).
-    a.rs_in = a.S_in << (a.lo + k.load_shb);
-    a.rs_seg = a.S_seg << (a.lo + k.load_shb);
-    a.rs_out = a.S_out << (a.lo + k.store_shb);
-    // (16 row registers at most: the stores' offsets m x rs_out fit 32 bits)
-    const bool full = a.voff32 && a.qrow % k.quads == 0 && a.in_rows_mask == 0 && a.rs_out < ((uint64_t)1 << 28);
-    a.full_lanes = full ? 1u : 0u;
+    a.voff32 = pc.voff32;
+    a.fd_lds = (a.diag & DIAG_FD_LDS) ? 1u : 0u;
+    a.rs_in = pc.rs_in, a.rs_seg = pc.rs_seg, a.rs_out = pc.rs_out;
+    a.full_lanes = pc.full_lanes;
     const FastDiv dn = fast_div_of(a.nslab), ds = fast_div_of(a.stripe_tiles);
     a.nslab_mul = dn.mul, a.nslab_one = dn.one;
     a.stripe_mul = ds.mul, a.stripe_one = ds.one;

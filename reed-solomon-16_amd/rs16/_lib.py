@@ -18,7 +18,15 @@ class RS16Error(C.Structure):
     _fields_ = [("code", C.c_int32), ("v0", C.c_uint64), ("v1", C.c_uint64), ("v2", C.c_uint64)]
 
 
+class PassConsts(C.Structure):
+    """rs16_pass_consts (include/rs16.h): a pass launch's address-form constants and its kernel's geometry."""
+    _fields_ = [(n, C.c_uint32) for n in ("voff32", "full_lanes", "nslab", "quads", "threads", "load_shb",
+                                          "store_shb", "reg_bits", "row_sets")] + \
+               [(n, C.c_uint64) for n in ("rs_in", "rs_seg", "rs_out")]
+
+
 _sz, _p, _i, _e = C.c_size_t, C.c_void_p, C.c_int, C.POINTER(RS16Error)
+_u32, _u64 = C.c_uint32, C.c_uint64
 
 # name -> (restype, argtypes).  Must list every symbol of include/rs16.h
 # (tests/test_cabi.py checks both directions).
@@ -30,6 +38,9 @@ SIGNATURES = {
     "rs16_host_twiddle": (C.c_uint32, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rs16_host_twiddle_narrow": (C.c_int, [C.c_uint32]),
     "rs16_host_fast_div_check": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rs16_host_pass_consts": (_i, [_i, _i, _u32, _u64, _u64, _u64, _u64, _u32, _u32, _u32, _u32, _i,
+                                   C.POINTER(PassConsts)]),
+    "rs16_host_pass_consts_many": (_i, [_i, _i, _u32, _sz, _p, _p, _p, _p, _p, _u32, _u32, _u32, _i, _p]),
     "rs16_engine_set_profiling": (_i, [_p, _i, _e]),
     "rs16_engine_profile_read": (_i, [_p, _i, C.POINTER(C.c_double), C.POINTER(C.c_uint64), _e]),
     "rs16_engine_profile_reset": (None, [_p]),
@@ -96,6 +107,8 @@ SIGNATURES = {
     "rs16_memcpy_htod": (_i, [_p, _p, _p, _sz, _p, _e]),
     "rs16_memcpy_dtoh": (_i, [_p, _p, _p, _sz, _p, _e]),
     "rs16_memset_device": (_i, [_p, _p, _i, _sz, _p, _e]),
+    "rs16_memcpy2d_htod": (_i, [_p, _p, _sz, _p, _sz, _sz, _sz, _p, _e]),
+    "rs16_memcpy2d_dtoh": (_i, [_p, _p, _sz, _p, _sz, _sz, _sz, _p, _e]),
     "rs16_encode_host": (_i, [_p, _sz, _sz, _sz, _p, _p, _sz, _e]),
     "rs16_decode_host": (_i, [_p, _sz, _sz, _sz, _p, _p, _p, _p, _sz, _e]),
     "rs16_host_alloc": (_p, [_p, _sz, _e]),

@@ -71,6 +71,11 @@ def test_validate():
     assert e.value == rs16.Error("UnsupportedShardCount", original_count=4096, recovery_count=61440)
     rs16.validate(61440, 4096, 64, "high")
     rs16.validate(4096, 61440, 64, "low")
+    # shards from 4 GiB on: the kernels keep strides in 32 bits
+    rs16.validate(1, 1, 2**32 - 64)
+    with pytest.raises(rs16.Error) as e:
+        rs16.validate(1, 1, 2**32)
+    assert e.value == rs16.Error("InvalidShardSize", shard_bytes=2**32)
 
 
 def test_work_counts():
