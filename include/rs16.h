@@ -634,6 +634,19 @@ int rs16_host_pass_consts(int prog, int T, uint32_t lo, uint64_t s_in, uint64_t 
 int rs16_host_pass_consts_many(int prog, int T, uint32_t lo, size_t n, const uint64_t* s_in, const uint64_t* s_out,
                                const uint64_t* s_seg, const uint64_t* s_rest, const uint32_t* qrow, uint32_t chunk,
                                uint32_t row_base_in, uint32_t in_rows_mask, int diag, rs16_pass_consts* out);
+/* The shape of the launch by which rs16_update_device updates `rows` recovery
+ * rows of `shard_bytes` from `n` deltas, as the launcher computes it (one host
+ * function, which every update calls; no device needed):
+ *   quads_per_lane  8-byte quads of a row a lane works on (1 or 2)
+ *   nslab           slabs of 64 quads_per_lane quads per row, one wave each
+ *   rows_per_wave   consecutive rows a wave updates (the last run may be shorter)
+ *   blocks          workgroups of four waves; wave w has slab w mod nslab of
+ *                   run w / nslab
+ * Any of the four pointers may be NULL.  Returns 1, or 0 where
+ * rs16_update_device launches nothing or fails (rows = 0, a shard size that is
+ * 0, no multiple of 64 or too large, n = 0 or above RS16_UPDATE_MAX_SHARDS). */
+int rs16_host_update_consts(uint32_t rows, uint64_t shard_bytes, uint32_t n, uint32_t* quads_per_lane,
+                            uint32_t* nslab, uint32_t* rows_per_wave, uint64_t* blocks);
 
 /* Library/build identification, e.g. "rs16-mi355x gfx950". */
 const char* rs16_version(void);

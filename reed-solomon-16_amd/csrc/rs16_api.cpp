@@ -143,6 +143,20 @@ extern "C" int rs16_host_pass_consts(int prog, int T, uint32_t lo, uint64_t s_in
     return rs16_host_pass_consts_many(prog, T, lo, 1, &s_in, &s_out, &s_seg, &s_rest, &qrow, chunk, row_base_in,
                                       in_rows_mask, diag, out);
 }
+extern "C" int rs16_host_update_consts(uint32_t rows, uint64_t shard_bytes, uint32_t n, uint32_t* quads_per_lane,
+                                       uint32_t* nslab, uint32_t* rows_per_wave, uint64_t* blocks) {
+    // (the checks of rs16_update_device)
+    if (shard_bytes == 0 || (shard_bytes & 63) != 0 || shard_bytes / 8 > 0xFFFFFFFFu) return 0;
+    UpdateArgs a{};
+    a.S = shard_bytes, a.qrow = (uint32_t)(shard_bytes / 8), a.rows = rows;
+    uint64_t nb;
+    if (!update_launch_consts(a, n, &nb)) return 0;  // (the function launch_update calls)
+    if (quads_per_lane) *quads_per_lane = a.quads_per_lane;
+    if (nslab) *nslab = a.nslab;
+    if (rows_per_wave) *rows_per_wave = a.rows_per_wave;
+    if (blocks) *blocks = nb;
+    return 1;
+}
 
 extern "C" int rs16_engine_set_profiling(rs16_engine* e, int enable, rs16_error* err) {
     if (int rc = e->activate(err)) return rc;

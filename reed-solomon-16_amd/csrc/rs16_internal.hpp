@@ -401,8 +401,14 @@ struct UpdateArgs {
     uint64_t S;              // row stride = row width (bytes)
     uint32_t qrow;           // quads per row = S / 8
     uint32_t row0, rows;
-    uint32_t quads_per_lane, nslab, rows_per_wave;  // set by launch_update
+    uint32_t quads_per_lane, nslab, rows_per_wave;  // set by update_launch_consts
 };
+// The shape of the launch for a.rows rows of a.qrow quads and n deltas: quads
+// per lane, slabs per row, rows per wave, and the workgroup count of four waves
+// each (< 2^24).  False when no launch holds the work (nothing to do, n out of
+// range, 2^32 threads or more at the longest runs).  Host arithmetic only:
+// launch_update calls it and rs16_host_update_consts exports it.
+bool update_launch_consts(UpdateArgs& a, uint32_t n, uint64_t* blocks);
 hipError_t launch_update(UpdateArgs a, uint32_t n, hipStream_t s);
 
 // FWHT / eval_poly.  `work` is a u32[65536] scratch.

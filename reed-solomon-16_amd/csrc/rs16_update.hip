@@ -175,9 +175,10 @@ template <int N> static void launch_n(const UpdateArgs& a, dim3 blocks, hipStrea
     hipLaunchKernelGGL((update_kernel<N, 1>), blocks, dim3(256), 0, s, a);
 }
 
-hipError_t launch_update(UpdateArgs a, uint32_t n, hipStream_t s) {
-    if (!a.rows || !a.qrow) return hipSuccess;
-    if (n == 0 || n > UPDATE_MAX_SHARDS) return hipErrorInvalidValue;
+// The launch's shape from rows, qrow and n (rs16_internal.hpp): host
+// arithmetic only, which rs16_host_update_consts evaluates without a device.
+bool update_launch_consts(UpdateArgs& a, uint32_t n, uint64_t* nblocks) {
+    if (!a.rows || !a.qrow || n == 0 || n > UPDATE_MAX_SHARDS) return false;
     a.quads_per_lane = a.qrow >= UPDATE_Q2_MIN_QROW && n <= UPDATE_Q2_MAX_N ? 2 : 1;
     a.nslab = (a.qrow + 64 * a.quads_per_lane - 1) / (64 * a.quads_per_lane);
     // Rows per wave: enough waves to fill the chip several times over (1024
@@ -188,14 +189,22 @@ hipError_t launch_update(UpdateArgs a, uint32_t n, hipStream_t s) {
     // four waves a workgroup; a launch holds < 2^32 threads (very wide shards: longer runs)
     auto blocks = [&] { return ((uint64_t)((a.rows + a.rows_per_wave - 1) / a.rows_per_wave) * a.nslab + 3) / 4; };
     while (blocks() * 256 > 0xFFFFFFFFull && a.rows_per_wave < a.rows) a.rows_per_wave *= 2;
-    if (blocks() * 256 > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (blocks() * 256 > 0xFFFFFFFFull) return false;
+    *nblocks = blocks();
+    return true;
+}
+
+hipError_t launch_update(UpdateArgs a, uint32_t n, hipStream_t s) {
+    if (!a.rows || !a.qrow) return hipSuccess;
+    uint64_t blocks;
+    if (!update_launch_consts(a, n, &blocks)) return hipErrorInvalidValue;
     typedef void (*Launch)(const UpdateArgs&, dim3, hipStream_t);
     static const Launch launch[UPDATE_MAX_SHARDS] = {
         launch_n<1>,  launch_n<2>,  launch_n<3>,  launch_n<4>,  launch_n<5>,  launch_n<6>,  launch_n<7>,  launch_n<8>,
         launch_n<9>,  launch_n<10>, launch_n<11>, launch_n<12>, launch_n<13>, launch_n<14>, launch_n<15>, launch_n<16>,
         launch_n<17>, launch_n<18>, launch_n<19>, launch_n<20>, launch_n<21>, launch_n<22>, launch_n<23>, launch_n<24>,
         launch_n<25>, launch_n<26>, launch_n<27>, launch_n<28>, launch_n<29>, launch_n<30>, launch_n<31>, launch_n<32>};
-    launch[n - 1](a, dim3((unsigned)blocks()), s);
+    launch[n - 1](a, dim3((unsigned)blocks), s);
     return hipGetLastError();
 }
 
