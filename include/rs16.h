@@ -567,9 +567,13 @@ enum {
                                       derivative / FFT pass, also when the lost originals lie in at most
                                       4 of its output rows per column (default there: a direct product
                                       with the pass's matrix) */
-    RS16_DIAG_WIDE_TWIDDLES = 2048 /* the full 12-lookup multiply in every layer (default: the middle
+    RS16_DIAG_WIDE_TWIDDLES = 2048, /* the full 12-lookup multiply in every layer (default: the middle
                                       passes multiply with 9 lookups in the layers whose twiddles all
                                       lie in the GF(2^8) subfield) */
+    RS16_DIAG_NO_LATE_ROWS = 4096  /* the T = 7 / 8 encoder-family passes always request all their rows
+                                      ahead of the first layer (default: a launch none of whose waves
+                                      needs the general row loads requests most of them from inside
+                                      the first layer; rs16_pass_consts.late_rows) */
 };
 int rs16_engine_set_diagnostics(rs16_engine* eng, int flags);
 /* Deprecated (the round-4 process-wide form, kept for existing callers):
@@ -625,6 +629,9 @@ typedef struct rs16_pass_consts {
     uint32_t voff32, full_lanes, nslab;
     uint32_t quads, threads, load_shb, store_shb, reg_bits, row_sets;
     uint64_t rs_in, rs_seg, rs_out;
+    uint32_t late_rows; /* 1: the launch runs the late-rows kernel variant (32-bit lane offsets, no
+                           row mask, a gather's row limit a multiple of row_sets 2^reg_bits << lo,
+                           no RS16_DIAG_NO_LATE_ROWS; the T = 7 / 8 encoder-family passes only) */
 } rs16_pass_consts;
 int rs16_host_pass_consts(int prog, int T, uint32_t lo, uint64_t s_in, uint64_t s_out, uint64_t s_seg, uint64_t s_rest,
                           uint32_t qrow, uint32_t chunk, uint32_t row_base_in, uint32_t in_rows_mask, int diag,
@@ -634,6 +641,11 @@ int rs16_host_pass_consts(int prog, int T, uint32_t lo, uint64_t s_in, uint64_t 
 int rs16_host_pass_consts_many(int prog, int T, uint32_t lo, size_t n, const uint64_t* s_in, const uint64_t* s_out,
                                const uint64_t* s_seg, const uint64_t* s_rest, const uint32_t* qrow, uint32_t chunk,
                                uint32_t row_base_in, uint32_t in_rows_mask, int diag, rs16_pass_consts* out);
+/* rs16_host_pass_consts for a gathering first pass whose rows at and above
+ * `a_count` are absent (the two calls above: a_count = 0, no wave is cut). */
+int rs16_host_pass_consts_rows(int prog, int T, uint32_t lo, uint64_t s_in, uint64_t s_out, uint64_t s_seg,
+                               uint64_t s_rest, uint32_t qrow, uint32_t chunk, uint32_t row_base_in,
+                               uint32_t in_rows_mask, uint32_t a_count, int diag, rs16_pass_consts* out);
 /* The shape of the launch by which rs16_update_device updates `rows` recovery
  * rows of `shard_bytes` from `n` deltas, as the launcher computes it (one host
  * function, which every update calls; no device needed):

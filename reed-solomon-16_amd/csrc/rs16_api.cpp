@@ -115,16 +115,17 @@ extern "C" uint64_t rs16_host_fast_div_check(uint32_t divisor, uint32_t n0, uint
     return bad;
 }
 
-extern "C" int rs16_host_pass_consts_many(int prog, int T, uint32_t lo, size_t n, const uint64_t* s_in,
-                                          const uint64_t* s_out, const uint64_t* s_seg, const uint64_t* s_rest,
-                                          const uint32_t* qrow, uint32_t chunk, uint32_t row_base_in,
-                                          uint32_t in_rows_mask, int diag, rs16_pass_consts* out) {
+static int host_pass_consts(int prog, int T, uint32_t lo, size_t n, const uint64_t* s_in, const uint64_t* s_out,
+                            const uint64_t* s_seg, const uint64_t* s_rest, const uint32_t* qrow, uint32_t chunk,
+                            uint32_t row_base_in, uint32_t in_rows_mask, uint32_t a_count, int diag,
+                            rs16_pass_consts* out) {
     if (prog < 0 || prog >= NUM_PROGS || T < 0 || T > 8 || !out) return 0;
     const PassKernel& k = pass_kernel_of(prog, T);
     if (!k.fn) return 0;
     PassArgs a{};
     a.lo = lo, a.chunk = chunk, a.row_base_in = row_base_in, a.in_rows_mask = in_rows_mask;
     a.diag = (uint32_t)diag;
+    a.a_count = a_count;
     for (size_t i = 0; i < n; i++) {
         a.S_in = s_in[i], a.S_out = s_out[i], a.S_seg = s_seg[i], a.S_rest = s_rest[i], a.qrow = qrow[i];
         const PassConsts c = pass_launch_consts(k, T, a);  // (the function launch_pass calls)
@@ -134,8 +135,23 @@ extern "C" int rs16_host_pass_consts_many(int prog, int T, uint32_t lo, size_t n
         o.load_shb = (uint32_t)k.load_shb, o.store_shb = (uint32_t)k.store_shb;
         o.reg_bits = (uint32_t)k.reg_bits, o.row_sets = k.quads >= 64 ? 1u : 64u / (uint32_t)k.quads;
         o.rs_in = c.rs_in, o.rs_seg = c.rs_seg, o.rs_out = c.rs_out;
+        o.late_rows = c.late_rows;
     }
     return 1;
+}
+// (a gather with row limit 0: every wave reads the zero page, none is cut)
+extern "C" int rs16_host_pass_consts_many(int prog, int T, uint32_t lo, size_t n, const uint64_t* s_in,
+                                          const uint64_t* s_out, const uint64_t* s_seg, const uint64_t* s_rest,
+                                          const uint32_t* qrow, uint32_t chunk, uint32_t row_base_in,
+                                          uint32_t in_rows_mask, int diag, rs16_pass_consts* out) {
+    return host_pass_consts(prog, T, lo, n, s_in, s_out, s_seg, s_rest, qrow, chunk, row_base_in, in_rows_mask, 0, diag,
+                            out);
+}
+extern "C" int rs16_host_pass_consts_rows(int prog, int T, uint32_t lo, uint64_t s_in, uint64_t s_out, uint64_t s_seg,
+                                          uint64_t s_rest, uint32_t qrow, uint32_t chunk, uint32_t row_base_in,
+                                          uint32_t in_rows_mask, uint32_t a_count, int diag, rs16_pass_consts* out) {
+    return host_pass_consts(prog, T, lo, 1, &s_in, &s_out, &s_seg, &s_rest, &qrow, chunk, row_base_in, in_rows_mask,
+                            a_count, diag, out);
 }
 extern "C" int rs16_host_pass_consts(int prog, int T, uint32_t lo, uint64_t s_in, uint64_t s_out, uint64_t s_seg,
                                      uint64_t s_rest, uint32_t qrow, uint32_t chunk, uint32_t row_base_in,
@@ -219,7 +235,8 @@ extern "C" int rs16_decode_check(rs16_engine* e, void* stream, rs16_error* err) 
 }
 static constexpr int DIAG_ALL = DIAG_FORCE_VOFF64 | DIAG_EVAL_TWO_KERNEL | DIAG_EVAL_FULL | DIAG_NO_COLUMN |
                                 DIAG_FORCE_COLUMN | DIAG_TILE_LAST | DIAG_NO_TILE_LAST | DIAG_FD_LDS |
-                                DIAG_COL_RADIX4 | DIAG_NO_IDENTITY | DIAG_NO_MID_DIRECT | DIAG_WIDE_TWIDDLES;
+                                DIAG_COL_RADIX4 | DIAG_NO_IDENTITY | DIAG_NO_MID_DIRECT | DIAG_WIDE_TWIDDLES |
+                                DIAG_NO_LATE_ROWS;
 extern "C" int rs16_engine_set_diagnostics(rs16_engine* e, int flags) {
     const int old = e->diag;
     e->diag = flags & DIAG_ALL;

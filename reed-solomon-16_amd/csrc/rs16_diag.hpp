@@ -15,6 +15,16 @@
 #define RS16_STAMPS 0
 #endif
 
+// Prologue depth of the late-rows pass kernels (rs16_pass.hpp LateRows): a
+// library built with -DRS16_LATE_DEPTH=n (n = 2, 4, 8; never the shipped one)
+// requests n row pairs ahead of the table commit in every program, for the
+// depth measurements.  0: each program's shipped depth (LateDepth).  Which
+// launches take those kernels at all is a run-time switch of one build:
+// RS16_DIAG_NO_LATE_ROWS (rs16_engine_set_diagnostics) forces pass_kernel.
+#ifndef RS16_LATE_DEPTH
+#define RS16_LATE_DEPTH 0
+#endif
+
 #if RS16_STAMPS
 namespace rs16 {
 template <class Args>

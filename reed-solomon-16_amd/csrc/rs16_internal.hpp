@@ -357,6 +357,7 @@ enum DiagFlags : int {
     DIAG_NO_IDENTITY = 512,   // whole-half erasures: eval_poly and the per-row multipliers anyway (identity_logs)
     DIAG_NO_MID_DIRECT = 1024, // the general decode's middle pass always as DEC_MID (no mid_direct_kernel)
     DIAG_WIDE_TWIDDLES = 2048, // the 12-lookup multiply in every layer (no narrow-twiddle pass variants)
+    DIAG_NO_LATE_ROWS = 4096,  // every wave-staged pass as pass_kernel (no pass_kernel_late; PassConsts::late_rows = 0)
 };
 
 constexpr size_t RS16_ZERO_BYTES = 65536;

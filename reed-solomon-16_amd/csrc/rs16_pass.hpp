@@ -66,6 +66,8 @@
 //   stripes of one geometry; a workgroup's tile index splits into (stripe,
 //   tile within the stripe) and the stripe displaces its array pointers.
 #pragma once
+#include <type_traits>
+
 #include "rs16_pass_common.hpp"
 #include "rs16_fwht.hpp"
 #include "rs16_diag.hpp"
@@ -393,6 +395,85 @@ __device__ __forceinline__ uint32_t wave_rows_mode(const PassArgs& a, const Thr&
     const bool direct = (a.voff32 != 0) & (a.in_rows_mask == 0) & below;
     return direct ? ROWS_DIRECT : (above ? ROWS_ZERO : ROWS_GENERAL);
 }
+// ---------------------------------------------------------------------------
+// Late rows (pass_kernel_late).  In a launch none of whose waves can be
+// ROWS_GENERAL (launch_pass decides: PassConsts::late_rows) the row requests
+// need no guarded block, so they can stand anywhere in straight-line code: the
+// wave requests the first D pairs of its first layer ahead of the table
+// commit (prologue) and pair q + D right before butterfly q of that layer
+// (operator(), GroupLoop's PRE hook).  The VALU starts on pair 0 once D pairs
+// are accepted by the memory pipeline instead of all NR / 2 -- at D < NR / 2,
+// which is a diagnostic build (RS16_LATE_DEPTH, rs16_diag.hpp); the shipped
+// depth requests every pair in the prologue (LateDepth on why).
+// Pair q of the first layer: layout A (IFFT layer 0) rows (2q, 2q + 1), layout
+// B (ENC_LAST: the FFT's top register bit) rows (q, q + NR / 2).
+// Addressing as request_rows: row register m at the wave's SGPR base + m x row
+// stride (launch_pass: 15 strides fit 32 bits) + one 32-bit lane offset;
+// a gather wave at or above the row limit reads the zero page with stride 0.
+// ---------------------------------------------------------------------------
+template <int P> struct LateDepth {
+    // Pairs requested ahead of the table commit.  Shipped: all 8 in every
+    // program, i.e. no request inside the layer -- what the variant keeps is
+    // the straight-line prologue (no general block) and ENC_LAST's pair
+    // order.  Depths 1 / 2 / 4 bring wave 0's first butterfly ~1 us forward on
+    // every box but win or lose the step by box (2: +6 % on one, -1.5 % on
+    // another; 4 in ENC_LAST slower than 8 everywhere); 8 was faster than the
+    // parent in every pair on every box: profiles/r11_late_rows_depth.txt.
+    static constexpr int SHIPPED = 8;
+    static constexpr int value = RS16_LATE_DEPTH > 0 ? RS16_LATE_DEPTH : SHIPPED;
+};
+template <int P, int T> struct LateRows {
+    using G = Geo<T>;
+    static constexpr bool START_B = !ProgTraits<P>::IFFT;
+    static constexpr bool GATHER = ProgTraits<P>::LOAD == LD_GATHER_ENC;
+    static constexpr int RB = START_B ? G::R - 1 : 0;  // the first layer's register bit
+    static constexpr int NP = G::NR / 2;               // its pairs
+    static constexpr int D = LateDepth<P>::value < NP ? LateDepth<P>::value : NP;
+    static_assert(D >= 1 && G::R == 4, "late rows: 16-row sets");
+    uint64_t p;         // the wave's row register 0 (uniform)
+    uint32_t rs, voff;  // stride of consecutive row registers (uniform), the lane's offset
+    __device__ __forceinline__ LateRows(const PassArgs& a, const Thr& c) {
+        const WaveRows<T, START_B> wr(c, a);
+        // (no wave of the launch straddles the limit: below it or the zero page)
+        const bool rows = !GATHER || wr.base < a.a_count;
+        const uint64_t S = GATHER ? a.S_seg : a.S_in;
+        // (a lane without a quad requests the first quad of its slab: request_rows' CLAMP)
+        const uint32_t offL = !c.active ? ((c.offL >> 6) - (c.qt >> 3)) * 64 : c.offL;
+        rs = rows ? (uint32_t)(GATHER ? a.rs_seg : a.rs_in) : 0u;
+        voff = rows ? lane_rows<T, START_B>(c, a) * (uint32_t)S + offL : (c.offL & 0x7FFFu);
+        p = rows ? (uint64_t)(GATHER ? a.seg_a : a.in) + (uint64_t)wr.base * S : (uint64_t)a.zero;
+    }
+    __device__ __forceinline__ void pair(uint32_t (&L)[G::NR], uint32_t (&H)[G::NR], int q) const {
+        const int m = ((q >> RB) << (RB + 1)) + (q & ((1 << RB) - 1));
+        // (the lane offset as a 32-bit value of the block the request stands
+        // in: extended to 64 bits in the prologue's block, it reaches the
+        // layer code as a VGPR pair and the loads lose their SGPR-base form)
+        uint32_t v = voff;
+        asm volatile("" : "+v"(v));
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int mi = m + (i << RB);
+            const gu32* g = (const gu32*)(sgpr_ptr((const uint8_t*)(p + (uint32_t)mi * rs)) + v);
+            L[mi] = g[0];
+            H[mi] = g[8];
+        }
+    }
+    __device__ __forceinline__ void prologue(uint32_t (&L)[G::NR], uint32_t (&H)[G::NR]) const {
+#pragma unroll
+        for (int q = 0; q < D; q++) pair(L, H, q);
+        asm volatile("; late rows: prologue requested");
+    }
+    // before butterfly q of the first layer: pair q + D, fenced so that the
+    // scheduler leaves the request between butterflies q - 1 and q
+    __device__ __forceinline__ void operator()(uint32_t (&L)[G::NR], uint32_t (&H)[G::NR], int q) const {
+        if (q + D < NP) {
+            __builtin_amdgcn_sched_barrier(0);
+            pair(L, H, q + D);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+};
+
 // The stores' side: row register m at base + m x rs_out (launch_pass: the
 // offsets of all row registers fit 32 bits when full_lanes is set), in any
 // order -- the early stores come from inside the last layer block.
@@ -550,6 +631,11 @@ template <int T> struct RevealEntry {
 struct NoFin {
     template <class X> __device__ __forceinline__ void operator()(const X&, const X&, int) const {}
 };
+// No action before a butterfly of the block's first layer (GroupLoop's
+// default; the late-rows kernels pass LateRows).
+struct NoPre {
+    template <class X> __device__ __forceinline__ void operator()(X&, X&, int) const {}
+};
 
 // Breadth-first (layer by layer), except the last FFT block in layout A of
 // all 4 register bits: there the groups run depth-first in pre-order (a
@@ -658,11 +744,16 @@ template <int NV> struct NarrowVar {
 // NK: the direction's first narrow layer -- the layers kb >= NK multiply
 // with mul_xor_narrow (every twiddle of theirs in this launch is a subfield
 // constant: launch_pass picks the kernel variant from first_narrow_layer).
-template <int P, int T, int NK, bool LB, int KB0, int KB1, bool FFT, bool IN_TAB2, int PRUNE, int G, class FIN = NoFin>
+// PRE (the late-rows kernels, LateRows): pre(L, H, q) runs before butterfly q
+// of the block's first layer -- the q-th pair of that layer, counted over its
+// groups -- and requests the rows of a later pair.
+template <int P, int T, int NK, bool LB, int KB0, int KB1, bool FFT, bool IN_TAB2, int PRUNE, int G, class FIN = NoFin,
+          class PRE = NoPre>
 struct GroupLoop {
     static __device__ __forceinline__ void run(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR], const Thr& c,
                                                const PassArgs& a, const uint4* tab1, const uint4* tab2,
-                                               const uint32_t (&cur)[20], uint32_t zmask, const FIN& fin = FIN()) {
+                                               const uint32_t (&cur)[20], uint32_t zmask, const FIN& fin = FIN(),
+                                               const PRE& pre = PRE()) {
         using S = LayerSeq<T, LB, KB0, KB1, FFT>;
         constexpr int s = S::step_of(G), gi = S::index_of(G);
         constexpr int kb = S::kb_of(s);
@@ -699,6 +790,7 @@ struct GroupLoop {
 #pragma unroll
             for (int j = 0; j < (1 << rb); j++) {
                 const int m = (gi << (rb + 1)) + j, m2 = m + (1 << rb);
+                if constexpr (!std::is_same<PRE, NoPre>::value && s == 0) pre(L, H, (gi << rb) + j);
                 if (FFT) {
                     mul_xor_t<NARROW>(L[m], H[m], L[m2], H[m2], cur);
                     L[m2] ^= L[m];
@@ -728,8 +820,8 @@ struct GroupLoop {
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (S::DF && kb == 0) fin(L, H, gi << 1);  // rows 2 gi, 2 gi + 1 are final
         if constexpr (more)
-            GroupLoop<P, T, NK, LB, KB0, KB1, FFT, IN_TAB2, PRUNE, G + 1, FIN>::run(L, H, c, a, tab1, tab2, nxt, zmask,
-                                                                                     fin);
+            GroupLoop<P, T, NK, LB, KB0, KB1, FFT, IN_TAB2, PRUNE, G + 1, FIN, PRE>::run(L, H, c, a, tab1, tab2, nxt,
+                                                                                          zmask, fin, pre);
     }
 };
 
@@ -746,10 +838,10 @@ __device__ __forceinline__ const uint4* lds_vgpr(const uint4* p) {
 
 // Apply the layers for k-bits [KB0, KB1) held in registers of layout LB.
 template <int P, int T, int NK, bool LB, int KB0, int KB1, bool FFT, bool IN_TAB2, int PRUNE = PR_NONE,
-          class FIN = NoFin>
+          class FIN = NoFin, class PRE = NoPre>
 __device__ __forceinline__ void layers(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR], const Thr& c,
                                        const PassArgs& a, const uint4* tab1, const uint4* tab2,
-                                       uint32_t zmask = 0, const FIN& fin = FIN()) {
+                                       uint32_t zmask = 0, const FIN& fin = FIN(), const PRE& pre = PRE()) {
     if constexpr (KB1 > KB0) {
         if constexpr (LB) {
             if constexpr (IN_TAB2) tab2 = lds_vgpr(tab2);
@@ -757,7 +849,8 @@ __device__ __forceinline__ void layers(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[
         }
         uint32_t t0[20];
         load_table_lds(t0, group_table<T, LB, KB0, KB1, FFT, 0, IN_TAB2>(c, tab1, tab2));
-        GroupLoop<P, T, NK, LB, KB0, KB1, FFT, IN_TAB2, PRUNE, 0, FIN>::run(L, H, c, a, tab1, tab2, t0, zmask, fin);
+        GroupLoop<P, T, NK, LB, KB0, KB1, FFT, IN_TAB2, PRUNE, 0, FIN, PRE>::run(L, H, c, a, tab1, tab2, t0, zmask, fin,
+                                                                                 pre);
     }
 }
 
@@ -1514,9 +1607,10 @@ template <int P, int T> struct EvenStore {
 
 // Compute and store one item whose rows are in d (every thread of the
 // workgroup calls it for the same item).
-template <int P, int T, int NV>
+// (PRE: the late-rows kernels' requests inside the first layer block, LateRows)
+template <int P, int T, int NV, class PRE = NoPre>
 __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, uint32_t tile, ItemRegs<P, T>& d,
-                                             uint8_t* smem) {
+                                             uint8_t* smem, const PRE& pre = PRE()) {
     using PT = ProgTraits<P>;
     constexpr int NKI = NarrowVar<NV>::IFFT_FROM, NKF = NarrowVar<NV>::FFT_FROM;
     static_assert(NV == 0 || (PT::IFFT && PT::FFT && T > 4), "narrow variants: two-direction passes only");
@@ -1599,7 +1693,9 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
         bool skip_a = false;
         if constexpr (ZERO_SKIP) skip_a = __all(d.zrow == (1u << NR) - 1);
         if constexpr (WaveStaged<P, T>::value) RS16_STAMP_ROWS(a, 6, L, H, 0, 1);
-        if (!skip_a) layers<P, T, NKI, false, 0, R, false, false>(L, H, c, a, tab1, tab2);
+        if constexpr (!std::is_same<PRE, NoPre>::value)
+            layers<P, T, NKI, false, 0, R, false, false, PR_NONE, NoFin, PRE>(L, H, c, a, tab1, tab2, 0, NoFin(), pre);
+        else if (!skip_a) layers<P, T, NKI, false, 0, R, false, false>(L, H, c, a, tab1, tab2);
         RS16_STAMP(a, 3);
         prio<1>();
         if constexpr (T > 4) {
@@ -1657,8 +1753,11 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
     if constexpr (PT::FFT) {
         if constexpr (T > 4) {
             if constexpr (WaveStaged<P, T>::value && !PT::IFFT) RS16_STAMP_ROWS(a, 6, L, H, 0, NR / 2);
-            layers<P, T, NKF, true, R, (T > 4 ? T : R), true, TWO, (P == DEC_MID ? PR_OUT : PR_NONE)>(L, H, c, a, tab1,
-                                                                                                  tab2);
+            if constexpr (!std::is_same<PRE, NoPre>::value && !PT::IFFT)
+                layers<P, T, NKF, true, R, T, true, TWO, PR_NONE, NoFin, PRE>(L, H, c, a, tab1, tab2, 0, NoFin(), pre);
+            else
+                layers<P, T, NKF, true, R, (T > 4 ? T : R), true, TWO, (P == DEC_MID ? PR_OUT : PR_NONE)>(L, H, c, a, tab1,
+                                                                                                      tab2);
             if constexpr (SPLIT_FD) {
                 // the layout-A bits' derivative terms (fd_image) join the
                 // register rows that feed consumed rows
@@ -1901,14 +2000,77 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, ((P == DEC_SINGLE || P == DEC
     rcn.store(a, c);
 }
 
+// The late-rows variant of a wave-staged pass (LateRows): pass_kernel for a
+// launch without ROWS_GENERAL waves (PassConsts::late_rows).  Item mapping,
+// table staging, layers and stores are pass_kernel's; the rows are requested
+// in two parts, D pairs here and the rest from inside the first layer, all in
+// straight-line code (no general block, so no edge without row loads in front
+// of the table commit's wait).
+template <int P, int T, int NV = 0>
+__global__ void __launch_bounds__(Geo<T>::THREADS, 4) pass_kernel_late(PassArgs a) {
+    using G = Geo<T>;
+    static_assert(WaveStaged<P, T>::value, "late rows: the wave-staged passes");
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t item = blockIdx.x;
+
+    Thr c;
+    c.lane = threadIdx.x & 63;
+    c.w = uni(threadIdx.x >> 6);
+    c.qt = c.lane % G::Q;
+    c.s = c.w * G::HWS + c.lane / G::Q;
+    c.ql = c.qt % Rnd<P, T>::QL;
+    c.round = c.qt / Rnd<P, T>::QL;
+
+    uint32_t tile, slab;
+    set_item(c, a, item, G::Q, tile, slab);
+
+    bool first_stripe = true;
+    if (a.stripe_tiles) {
+        const uint32_t st = uni(fast_div(tile, a.stripe_mul, a.stripe_one));
+        first_stripe = st == 0;
+        tile -= st * a.stripe_tiles;
+        stripe_displace(a, st);
+    }
+    tile += a.tile_base;
+    c.b_low = tile & ((1u << a.lo) - 1);
+    c.b_high = tile >> a.lo;
+    RcvCount<P, T> rcn;
+    rcn.issue(a, c, slab == 0 && first_stripe);
+    RS16_STAMP(a, 0);
+    // (load-issue order by workgroup slot, as pass_kernel)
+    const uint32_t slot = (__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 16) & 15u;
+    if (slot == 0) __builtin_amdgcn_s_setprio(3);
+    else if (slot == 1) __builtin_amdgcn_s_setprio(2);
+    else if (slot == 2) __builtin_amdgcn_s_setprio(1);
+    TileStage<P, T> st;
+    st.issue(a, c);
+    ItemRegs<P, T> cur;
+    cur.zrow = cur.zmask = 0;
+    cur.ztile = false;
+    const LateRows<P, T> rq(a, c);
+    rq.prologue(cur.L, cur.H);
+    RS16_STAMP(a, 1);
+    prio<0>();
+    st.template finish<false>(a, c, smem);
+    rcn.count();
+    RS16_STAMP(a, 2);
+    process_item<P, T, NV, LateRows<P, T>>(a, c, tile, cur, smem, rq);
+    rcn.store(a, c);
+}
+
 // ---------------------------------------------------------------------------
 // What an instantiation unit builds its PassKernel lookup from: taking a
 // kernel's address here is what instantiates it in that unit.
 // ---------------------------------------------------------------------------
+template <int P, int T, int NV> PassFn late_entry() {
+    if constexpr (WaveStaged<P, T>::value) return pass_kernel_late<P, T, NV>;
+    else return nullptr;
+}
 template <int P, int T, int NV = 0> PassKernel pass_entry() {
     using PT = ProgTraits<P>;
     return {pass_kernel<P, T, NV>, Smem<P, T>::BYTES, Geo<T>::THREADS, Geo<T>::Q,
-            !PT::IFFT ? Geo<T>::SHB : 0, (!PT::FFT && T > 4) ? Geo<T>::SHB : 0, Geo<T>::R};
+            !PT::IFFT ? Geo<T>::SHB : 0, (!PT::FFT && T > 4) ? Geo<T>::SHB : 0, Geo<T>::R,
+            late_entry<P, T, NV>(), PT::LOAD == LD_GATHER_ENC ? 1 : 0};
 }
 // the 12-lookup kernels of program P at T = 0 .. 8
 template <int P> PassKernel pass_row(int T) {

@@ -22,15 +22,23 @@ struct PassKernel {
     // registers are 1 << lo rows apart), else B (1 << (lo + SHB)): SHB
     int load_shb, store_shb;
     int reg_bits;  // Geo<T>::R, row bits held in registers (2^R rows per thread)
+    // The late-rows variant of a wave-staged pass (rs16_pass.hpp
+    // pass_kernel_late; nullptr: none), and whether the pass gathers its rows
+    // below the row limit a_count (ENC_FIRST).
+    PassFn late;
+    int gather;
 };
 // The launch constants that decide a launch's address forms (the PassArgs
 // fields of the same names), as launch_pass sets them from the kernel's
 // geometry and the launch's strides, slice width, stride exponent, row
 // alignment and diag flags.  Host arithmetic only: rs16_host_pass_consts
 // (include/rs16.h) shows it to tests without a device.
+// late_rows: the launch takes the kernel's late-rows variant -- no wave of it
+// can be ROWS_GENERAL (rs16_pass.hpp wave_rows_mode).
 struct PassConsts {
     uint32_t nslab, voff32, full_lanes;
     uint64_t rs_in, rs_seg, rs_out;
+    uint32_t late_rows;
 };
 PassConsts pass_launch_consts(const PassKernel& k, int T, const PassArgs& a);
 // The 12-lookup kernel of (prog, T) (fn nullptr: none), whose geometry every

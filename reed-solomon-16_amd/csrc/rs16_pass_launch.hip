@@ -69,6 +69,28 @@ PassConsts pass_launch_consts(const PassKernel& k, int T, const PassArgs& a) {
     // (16 row registers at most: the stores' offsets m x rs_out fit 32 bits)
     const bool full = c.voff32 && a.qrow % k.quads == 0 && a.in_rows_mask == 0 && c.rs_out < ((uint64_t)1 << 28);
     c.full_lanes = full ? 1u : 0u;
+    // The late-rows variant (pass_kernel_late) has no general row loads: it
+    // runs exactly when every wave of the launch is ROWS_DIRECT or ROWS_ZERO
+    // (wave_rows_mode) -- 32-bit lane offsets, no row mask, and, in the
+    // gathering first pass, a row limit that cuts through no wave's rows.  A
+    // wave of that pass (layout A) holds the rows base + (k << lo), k < hws
+    // 2^R, with base = b_low + j (hws 2^R << lo) over all b_low < 2^lo and all
+    // j: a_count = j0 (hws 2^R << lo) + r lies strictly inside the range of
+    // wave (b_low, j0) when b_low < r <= b_low + ((hws 2^R - 1) << lo), which
+    // some b_low satisfies for every r != 0 and none for r = 0.  So: a_count a
+    // multiple of hws 2^R << lo.  Partial slabs and waves wholly above the
+    // limit (the zero page) qualify.  Its row registers are addressed as base
+    // + m x stride in 32 bits (m <= 15): the strides stay below 2^28.
+    // (RS16_DIAG_NO_LATE_ROWS: never.)
+    {
+        const uint64_t hws = k.quads >= 64 ? 1 : 64 / k.quads;
+        const uint64_t wave_span = (hws << k.reg_bits) << a.lo;
+        const bool whole = !k.gather || a.a_count % wave_span == 0;
+        const bool strides = c.rs_in < ((uint64_t)1 << 28) && c.rs_seg < ((uint64_t)1 << 28);
+        c.late_rows = k.late && c.voff32 && a.in_rows_mask == 0 && whole && strides && !(a.diag & DIAG_NO_LATE_ROWS)
+                          ? 1u
+                          : 0u;
+    }
     return c;
 }
 
@@ -98,13 +120,14 @@ hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles
     a.nslab_mul = dn.mul, a.nslab_one = dn.one;
     a.stripe_mul = ds.mul, a.stripe_one = ds.one;
     const size_t lds = (size_t)k.lds;
+    const PassFn fn = pc.late_rows ? k.late : k.fn;
     if (lds > 65536) {
         // (per kernel variant: each is a function of its own)
-        hipError_t e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     dim3 grid(nwg), block(k.threads);
-    hipLaunchKernelGGL(k.fn, grid, block, lds, s, a);
+    hipLaunchKernelGGL(fn, grid, block, lds, s, a);
     return hipGetLastError();
 }
 

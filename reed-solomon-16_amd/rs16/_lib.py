@@ -22,7 +22,7 @@ class PassConsts(C.Structure):
     """rs16_pass_consts (include/rs16.h): a pass launch's address-form constants and its kernel's geometry."""
     _fields_ = [(n, C.c_uint32) for n in ("voff32", "full_lanes", "nslab", "quads", "threads", "load_shb",
                                           "store_shb", "reg_bits", "row_sets")] + \
-               [(n, C.c_uint64) for n in ("rs_in", "rs_seg", "rs_out")]
+               [(n, C.c_uint64) for n in ("rs_in", "rs_seg", "rs_out")] + [("late_rows", C.c_uint32)]
 
 
 _sz, _p, _i, _e = C.c_size_t, C.c_void_p, C.c_int, C.POINTER(RS16Error)
@@ -40,6 +40,8 @@ SIGNATURES = {
     "rs16_host_fast_div_check": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "rs16_host_pass_consts": (_i, [_i, _i, _u32, _u64, _u64, _u64, _u64, _u32, _u32, _u32, _u32, _i,
                                    C.POINTER(PassConsts)]),
+    "rs16_host_pass_consts_rows": (_i, [_i, _i, _u32, _u64, _u64, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _i,
+                                        C.POINTER(PassConsts)]),
     "rs16_host_pass_consts_many": (_i, [_i, _i, _u32, _sz, _p, _p, _p, _p, _p, _u32, _u32, _u32, _i, _p]),
     "rs16_host_update_consts": (_i, [_u32, _u64, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32),
                                      C.POINTER(_u64)]),

@@ -7,13 +7,15 @@ tmin = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 OCC = r"Occupancy \[waves/SIMD\]"
 for p in re.split(r"remark: Function Name: ", txt)[1:]:
     name = p.split()[0]
-    m = re.match(r"_ZN4rs1611pass_kernelILi(\d+)ELi(\d+)E", name)
-    if not m or int(m.group(2)) < tmin:
+    m = re.match(r"_ZN4rs16\d+pass_kernel(_late)?ILi(\d+)ELi(\d+)ELi(\d+)E", name)
+    if not m or int(m.group(3)) < tmin:
         continue
+    late = " late" if m.group(1) else ""
 
     def g(k):
         mm = re.search(k + r": (\d+)", p)
         return mm.group(1) if mm else "?"
 
-    print("P%s T%s  VGPR %s  SGPR %s  occ %s  sspill %s  vspill %s" % (
-        m.group(1), m.group(2), g("VGPRs"), g("SGPRs"), g(OCC), g("SGPRs Spill"), g("VGPRs Spill")))
+    print("P%s T%s NV%s%s  VGPR %s  SGPR %s  occ %s  sspill %s  vspill %s  scratch %s  LDS %s" % (
+        m.group(2), m.group(3), m.group(4), late, g("VGPRs"), g("SGPRs"), g(OCC), g("SGPRs Spill"), g("VGPRs Spill"),
+        g(r"ScratchSize \[bytes/lane\]"), g(r"LDS Size \[bytes/block\]")))

@@ -14,18 +14,97 @@ other sign.  Per kernel, on the straight-line path from the full-item row
 requests on: the last vmcnt wait before the first ds_write_b128, the last
 one before the first v_perm_b32, and whether an s_barrier precedes that
 v_perm.  Exit status 1 if any differs from the expected values.
+
+The late-rows variants (pass_kernel_late, LateRows) request D row pairs ahead
+of the table commit (4 D dword loads before the "late rows: prologue
+requested" marker; D is read off the assembly) and pair g + D right before
+butterfly g of the first layer.  From the marker on, in program order, the
+script counts the row loads requested (global_load_dword) and, at every vmcnt
+wait, the loads that wait retires.  Expected:
+
+    tables     the last wait before the first ds_write_b128 leaves >= 4 D
+               loads in flight (the whole prologue)
+    butterfly  at the first v_perm_b32 that follows the retirement of pair g
+               (g = 0 .. 7, none skipped), exactly the loads requested after
+               pair g are in flight: 4 min(D, 7 - g)
+    form       every late request is an SGPR-base load
+    no s_barrier, and no vmcnt(0) before the wait for the last pair
 """
 import re
 import sys
 
 KERNEL = re.compile(r"^_ZN4rs1611pass_kernelILi([234])ELi([78])ELi(\d)EEEvNS_8PassArgsE:")
+LATE = re.compile(r"^_ZN4rs1616pass_kernel_lateILi([234])ELi([78])ELi(\d)EEEvNS_8PassArgsE:")
 NAMES = {"2": "ENC_FIRST", "3": "ENC_MID", "4": "ENC_LAST"}
 VM = re.compile(r"s_waitcnt.*vmcnt\((\d+)\)")
+ROW_LOAD = re.compile(r"^global_load_dword\s")
+SADDR = re.compile(r"\bs\[\d+:\d+\]")
+NP = 8  # pairs of the first layer (16 rows per lane)
+
+
+def late_kernel(lines, i, name):
+    """Check one late-rows kernel that starts at line i; returns (ok, next line)."""
+    k = i
+    marker = None
+    loads_before = 0
+    while not lines[k].startswith(".Lfunc_end"):
+        t = lines[k].strip()
+        if "late rows: prologue requested" in t:
+            marker = k
+            break
+        if ROW_LOAD.match(t):
+            loads_before += 1
+        k += 1
+    if marker is None or loads_before % 4 or not 0 < loads_before <= 4 * NP:
+        print("%-34s no prologue marker / %d row loads before it  UNEXPECTED" % (name, loads_before))
+        return False, k
+    D = loads_before // 4
+    requested = loads_before   # row loads requested so far
+    done = 0                   # ... retired by the waits so far
+    last = None
+    wait_tab = None
+    flight = []                # loads in flight at butterfly g's first v_perm
+    vaddr = 0
+    barrier = early_zero = False
+    while not lines[k].startswith(".Lfunc_end") and len(flight) < NP:
+        t = lines[k].strip()
+        w = VM.search(t)
+        if w:
+            last = int(w.group(1))
+            if last == 0 and (requested < 4 * NP or done < 4 * (NP - 1)):
+                early_zero = True
+            done = max(done, requested - last)
+        elif ROW_LOAD.match(t):
+            requested += 1
+            vaddr += not SADDR.search(t)
+        elif t.startswith("s_barrier"):
+            barrier = True
+        elif t.startswith("ds_write_b128") and wait_tab is None:
+            wait_tab = last
+        elif t.startswith("v_perm_b32") and done >= 4 * (len(flight) + 1):
+            # (retired past pair g + 1 before butterfly g ran: a wait too deep)
+            flight.append(requested - done if done == 4 * (len(flight) + 1) else -1)
+        k += 1
+    want = [4 * min(D, NP - 1 - g) for g in range(NP)]
+    ok = (wait_tab is not None and wait_tab >= 4 * D and flight == want and requested == 4 * NP and not vaddr
+          and not barrier and not early_zero)
+    print("%-34s D %d  tables vmcnt(%s)  in flight at butterflies %s  VGPR-pair requests %d  barrier: %s  "
+          "early vmcnt(0): %s  %s" % (name, D, wait_tab, ",".join(map(str, flight)), vaddr,
+                                      "yes" if barrier else "no", "yes" if early_zero else "no",
+                                      "ok" if ok else "UNEXPECTED (want %s)" % ",".join(map(str, want))))
+    return ok, k
 
 
 def main():
     lines = open(sys.argv[1]).read().splitlines()
     bad = 0
+    i = 0
+    while i < len(lines):
+        m = LATE.match(lines[i])
+        if m:
+            ok, i = late_kernel(lines, i, "pass_kernel_late<%s,%s,%s>" % (NAMES[m.group(1)], m.group(2), m.group(3)))
+            bad += not ok
+        i += 1
     i = 0
     while i < len(lines):
         m = KERNEL.match(lines[i])
