@@ -17,6 +17,20 @@
  *  - `_device` / `d_` pointers are HIP device pointers on the engine's
  *    device; `stream` is a hipStream_t (NULL = the engine's own stream).
  *    Device-pointer calls are asynchronous on that stream.
+ *  - Received flags: a flag byte means "received" when it is nonzero -- any
+ *    nonzero value (1, 2, 0x80, 0xFF ...), in device and host flag arrays
+ *    alike; only 0 means "not received".  Flag arrays need no alignment, and
+ *    no byte outside [0, count) of a flag array is read as a flag
+ *    (tests/test_gpu_flag_bytes.py).
+ *  - Device shard arrays handed to the codec (the originals / recovery of the
+ *    one-shot, batch, prepared and update calls, the arrays of the engine
+ *    shard ops fft / ifft / mul / xor / xor_within / formal_derivative) must
+ *    start on a 64-byte boundary, else RS16_INVALID_ARGUMENT before anything
+ *    is launched.  64 is the layout's block size, not a measured number:
+ *    shard sizes and strides are already multiples of it, so every row then
+ *    starts on a block.  (The add_*_shard_device calls copy their shard and
+ *    take any address; the u16 arrays of fwht / eval_poly and the RCCL
+ *    buffers are not shard arrays of the codec.)
  *  - One engine must not be used from two threads at once (it owns scratch
  *    workspace); create one engine per device/thread.  It may be used on
  *    several streams: a call that needs the engine's scratch on stream s

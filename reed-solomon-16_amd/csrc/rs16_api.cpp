@@ -428,6 +428,12 @@ extern "C" int rs16_engine_synchronize(rs16_engine* e, void* stream, rs16_error*
 
 // ---- engine ops -----------------------------------------------------------
 static bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
+// A caller's device shard array starts on a 64-byte boundary (include/rs16.h,
+// "Conventions"): the kernels load rows as 16-byte vectors and derive row
+// addresses from the base, and 64 bytes is the layout's block, as for shard
+// sizes and strides.  Checked by the extern "C" wrappers only, before any
+// launch; the engine's own methods pass base + 64 j to themselves.
+static bool shard_aligned(const void* p) { return ((uintptr_t)p & 63) == 0; }
 
 static int check_transform(size_t shard_count, size_t S, size_t pos, size_t size, size_t trunc, size_t skew_delta,
                            rs16_error* err) {
@@ -441,6 +447,7 @@ static int check_transform(size_t shard_count, size_t S, size_t pos, size_t size
 extern "C" int rs16_engine_fft(rs16_engine* e, void* data, size_t shard_count, size_t S, size_t pos, size_t size,
                                size_t trunc, size_t skew_delta, void* stream, rs16_error* err) {
     if (int rc = check_transform(shard_count, S, pos, size, trunc, skew_delta, err)) return rc;
+    if (!shard_aligned(data)) return set_error(err, RS16_INVALID_ARGUMENT);
     if (int rc = e->activate(err)) return rc;
     if (int rc = e->fft((uint8_t*)data, S, pos, size, skew_delta, e->pick(stream), err)) return rc;
     return set_error(err, RS16_OK);
@@ -452,6 +459,7 @@ extern "C" int rs16_engine_fft_skew_end(rs16_engine* e, void* data, size_t shard
 extern "C" int rs16_engine_ifft(rs16_engine* e, void* data, size_t shard_count, size_t S, size_t pos, size_t size,
                                 size_t trunc, size_t skew_delta, void* stream, rs16_error* err) {
     if (int rc = check_transform(shard_count, S, pos, size, trunc, skew_delta, err)) return rc;
+    if (!shard_aligned(data)) return set_error(err, RS16_INVALID_ARGUMENT);
     if (int rc = e->activate(err)) return rc;
     if (int rc = e->ifft((uint8_t*)data, S, pos, size, skew_delta, e->pick(stream), err)) return rc;
     return set_error(err, RS16_OK);
@@ -481,13 +489,13 @@ extern "C" int rs16_engine_eval_poly(rs16_engine* e, uint16_t* d, size_t trunc, 
     return set_error(err, RS16_OK);
 }
 extern "C" int rs16_engine_mul(rs16_engine* e, void* x, size_t bytes, uint16_t log_m, void* stream, rs16_error* err) {
-    if (bytes & 63) return set_error(err, RS16_INVALID_ARGUMENT);
+    if ((bytes & 63) || !shard_aligned(x)) return set_error(err, RS16_INVALID_ARGUMENT);
     if (int rc = e->activate(err)) return rc;
     RS16_HIP(launch_mul((uint8_t*)x, bytes, log_m, e->d_mul_tab, e->pick(stream)));
     return set_error(err, RS16_OK);
 }
 extern "C" int rs16_engine_xor(rs16_engine* e, void* x, const void* y, size_t bytes, void* stream, rs16_error* err) {
-    if (bytes & 63) return set_error(err, RS16_INVALID_ARGUMENT);
+    if ((bytes & 63) || !shard_aligned(x) || !shard_aligned(y)) return set_error(err, RS16_INVALID_ARGUMENT);
     if (int rc = e->activate(err)) return rc;
     RS16_HIP(launch_xor((uint8_t*)x, (const uint8_t*)y, bytes, e->pick(stream)));
     return set_error(err, RS16_OK);
@@ -496,12 +504,12 @@ extern "C" int rs16_engine_xor_within(rs16_engine* e, void* data, size_t shard_c
                                       size_t count, void* stream, rs16_error* err) {
     if ((S & 63) || x + count > shard_count || y + count > shard_count || (x < y ? x + count > y : y + count > x))
         return set_error(err, RS16_INVALID_ARGUMENT);
-    uint8_t* d = (uint8_t*)data;
+    uint8_t* d = (uint8_t*)data;  // (rs16_engine_xor checks the alignment: x S and y S are multiples of 64)
     return rs16_engine_xor(e, d + x * S, d + y * S, count * S, stream, err);
 }
 extern "C" int rs16_engine_formal_derivative(rs16_engine* e, void* data, size_t n, size_t S, void* stream,
                                              rs16_error* err) {
-    if ((S & 63) || S == 0 || !is_pow2(n)) return set_error(err, RS16_INVALID_ARGUMENT);
+    if ((S & 63) || S == 0 || !is_pow2(n) || !shard_aligned(data)) return set_error(err, RS16_INVALID_ARGUMENT);
     if (int rc = e->activate(err)) return rc;
     hipStream_t s = e->pick(stream);
     if (int rc = e->order(s, err)) return rc;
@@ -1012,6 +1020,7 @@ extern "C" int rs16_encode_device(rs16_engine* e, size_t k, size_t m, size_t S, 
                                   void* d_recovery, void* stream, rs16_error* err) {
     bool high;
     if (int rc = resolve_rate(RS16_RATE_DEFAULT, k, m, S, &high, err)) return rc;
+    if (!shard_aligned(d_original) || !shard_aligned(d_recovery)) return set_error(err, RS16_INVALID_ARGUMENT);
     if (int rc = e->activate(err)) return rc;
     hipStream_t s = e->pick(stream);
     if (int rc = e->order(s, err)) return rc;
@@ -1056,7 +1065,7 @@ extern "C" int rs16_encode_device_batch(rs16_engine* e, size_t k, size_t m, size
     if (nstripes == 0) return set_error(err, RS16_OK);
     // (strides in whole 64-byte blocks, as shard sizes: every row stays aligned)
     if (!d_original || !d_recovery || original_stride < k * S || recovery_stride < m * S || original_stride % 64 ||
-        recovery_stride % 64)
+        recovery_stride % 64 || !shard_aligned(d_original) || !shard_aligned(d_recovery))
         return set_error(err, RS16_INVALID_ARGUMENT);
     const size_t chunk = next_pow2(m);
     // one launch holds < 2^32 tiles; stay far below
@@ -1572,6 +1581,7 @@ extern "C" int rs16_decode_device(rs16_engine* e, size_t k, size_t m, size_t S, 
     e->forget_decode();  // (whatever happens below, the previous decode is not checked again)
     if (orig_recv > k || rec_recv > m) return set_error(err, RS16_INVALID_ARGUMENT);
     if (orig_recv + rec_recv < k) return set_error(err, RS16_NOT_ENOUGH_SHARDS, k, orig_recv, rec_recv);
+    if (!shard_aligned(d_original) || !shard_aligned(d_recovery)) return set_error(err, RS16_INVALID_ARGUMENT);
     DecodeGeom g = decode_geom(high, k, m);
     g.a_recv = high ? rec_recv : orig_recv;
     g.b_recv = high ? orig_recv : rec_recv;
@@ -1638,6 +1648,8 @@ extern "C" int rs16_decode_device_prepared(rs16_engine* e, size_t k, size_t m, s
                                            const void* d_recovery, void* stream, rs16_error* err) {
     const rs16_engine::Prepared p = e->prep;
     if (!p.valid || p.k != k || p.m != m || p.S != S) return set_error(err, RS16_INVALID_ARGUMENT);
+    // (misaligned shard arrays: refused like a wrong geometry, the preparation stays)
+    if (!shard_aligned(d_original) || !shard_aligned(d_recovery)) return set_error(err, RS16_INVALID_ARGUMENT);
     e->prep.valid = false;
     if (p.nothing) return note_flags_only(e, p.g, p.fl_a, p.fl_b, stream, err);
     if (int rc = e->activate(err)) return rc;
@@ -1663,6 +1675,7 @@ extern "C" int rs16_decode_device_batch(rs16_engine* e, size_t k, size_t m, size
     if (orig_recv > k || rec_recv > m) return set_error(err, RS16_INVALID_ARGUMENT);
     if (orig_recv + rec_recv < k) return set_error(err, RS16_NOT_ENOUGH_SHARDS, k, orig_recv, rec_recv);
     if (nstripes == 0) return set_error(err, RS16_OK);
+    if (!shard_aligned(d_original) || !shard_aligned(d_recovery)) return set_error(err, RS16_INVALID_ARGUMENT);
     if (orig_recv == k) {
         DecodeGeom g0 = decode_geom(high, k, m);
         g0.a_recv = high ? rec_recv : orig_recv;
@@ -1722,8 +1735,8 @@ extern "C" int rs16_decode_device_batch_varied(rs16_engine* e, size_t k, size_t 
     if (nstripes == 0) return set_error(err, RS16_OK);
     if (!d_original || !d_recovery || !d_original_received || !d_recovery_received || !original_received_counts ||
         !recovery_received_counts || original_stride < k * S || recovery_stride < m * S || original_stride % 64 ||
-        recovery_stride % 64 || original_received_stride < k || recovery_received_stride < m ||
-        nstripes > ((size_t)1 << 16))
+        recovery_stride % 64 || !shard_aligned(d_original) || !shard_aligned(d_recovery) ||
+        original_received_stride < k || recovery_received_stride < m || nstripes > ((size_t)1 << 16))
         return set_error(err, RS16_INVALID_ARGUMENT);
     for (size_t i = 0; i < nstripes; i++) {
         const size_t o = original_received_counts[i], r = recovery_received_counts[i];
@@ -1894,7 +1907,8 @@ extern "C" int rs16_update_device(rs16_update_plan* p, size_t S, const void* d_d
     if (recovery_pos > p->m || recovery_n > p->m - recovery_pos) return set_error(err, RS16_INVALID_ARGUMENT);
     if (recovery_n == 0) return set_error(err, RS16_OK);
     // (quads per row as a 32-bit count)
-    if (!d_delta || !d_recovery || S / 8 > 0xFFFFFFFFu) return set_error(err, RS16_INVALID_ARGUMENT);
+    if (!d_delta || !d_recovery || S / 8 > 0xFFFFFFFFu || !shard_aligned(d_delta) || !shard_aligned(d_recovery))
+        return set_error(err, RS16_INVALID_ARGUMENT);
     rs16_engine* e = p->eng;
     if (int rc = e->activate(err)) return rc;
     UpdateArgs a{};
