@@ -7,9 +7,9 @@ The device and the host read the caller's flag bytes in a dozen separately
 written places (rs16_misc.hip: erasure_at / received_at, nz80 + sdot4 in
 eval_fused_kernel, eval_small_kernel; rs16_col.hip: ColEval::prep and the
 gathers of col_kernel / col2_kernel; rs16_pass.hpp: RcvCount; the reveal's
-row_lost_original in rs16_pass_common.hpp; rs16_api.cpp: the host counts,
-copy_runs, the flags-only count of rs16_decode_check).  A reader written as
-`& 1`, `== 1`, a signed `> 0` or a byte sum restores wrong data for a caller
+row_lost_original in rs16_pass_common.hpp; rs16_api_host.cpp: the host counts,
+copy_runs; rs16_api.cpp: the flags-only count of rs16_decode_check).  A reader
+written as `& 1`, `== 1`, a signed `> 0` or a byte sum restores wrong data for a caller
 whose "true" is not 1; the cases below are the smallest shapes that reach
 each reader (DESIGN.md 3.11, rs16_engine::decode_eval), with flags "dressed"
 in a palette of nonzero values.

@@ -1,6 +1,6 @@
 """The Rate-level API with shards in host memory:
 ReedSolomonEncoder / ReedSolomonDecoder add_*_shard copy host shards into a
-page-locked image of the work buffer (rs16_api.cpp "Host staging"), stream
+page-locked image of the work buffer (rs16_api_coders.cpp "Host staging"), stream
 runs of consecutive rows to HBM while the caller keeps adding, and bring the
 results back in one DMA copy.  Checked against the oracle (tests/oracle_bind)
 bit for bit:
