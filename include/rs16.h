@@ -584,10 +584,15 @@ enum {
     RS16_DIAG_WIDE_TWIDDLES = 2048, /* the full 12-lookup multiply in every layer (default: the middle
                                       passes multiply with 9 lookups in the layers whose twiddles all
                                       lie in the GF(2^8) subfield) */
-    RS16_DIAG_NO_LATE_ROWS = 4096  /* the T = 7 / 8 encoder-family passes always request all their rows
+    RS16_DIAG_NO_LATE_ROWS = 4096, /* the T = 7 / 8 encoder-family passes always request all their rows
                                       ahead of the first layer (default: a launch none of whose waves
                                       needs the general row loads requests most of them from inside
                                       the first layer; rs16_pass_consts.late_rows) */
+    RS16_DIAG_NO_PAIRED_ROWS = 8192 /* the engine's work buffer keeps the shard layout between the passes
+                                      of every sequence (default: the three-pass encode and the identity
+                                      decode of 2^14 / 2^15-row chunks, widths a multiple of 512 bytes,
+                                      keep a quad's two dwords next to each other there and move a row
+                                      with one 8-byte access per lane; rs16_host_paired_rows) */
 };
 int rs16_engine_set_diagnostics(rs16_engine* eng, int flags);
 /* Deprecated (the round-4 process-wide form, kept for existing callers):
@@ -660,6 +665,20 @@ int rs16_host_pass_consts_many(int prog, int T, uint32_t lo, size_t n, const uin
 int rs16_host_pass_consts_rows(int prog, int T, uint32_t lo, uint64_t s_in, uint64_t s_out, uint64_t s_seg,
                                uint64_t s_rest, uint32_t qrow, uint32_t chunk, uint32_t row_base_in,
                                uint32_t in_rows_mask, uint32_t a_count, int diag, rs16_pass_consts* out);
+/* Whether the three pass launches over a chunk of `chunk_rows` rows (a power
+ * of two) of width S bytes -- the three-pass encode, or the identity decode of
+ * one half -- keep the engine's work buffer in the paired row form (a quad's
+ * low and high dword adjacent: one 8-byte access per row and lane), as the
+ * engine decides it (one host function; no device needed).  1 exactly when
+ * all three launches (first / middle / last encoder pass at L / 2, L - L / 2
+ * and L / 2 row bits) report late_rows and full_lanes in rs16_host_pass_consts_rows,
+ * the chunk has 2^14 or 2^15 rows (the chunks whose three passes all have such
+ * kernels) and RS16_DIAG_NO_PAIRED_ROWS is not set in `diag`.  S_user: the
+ * caller's row stride; a_count: the first pass's row limit; seg_chunk,
+ * row_base_in: the decode's segment boundary and first gather row (0, 0 in an
+ * encode).  The form never leaves the engine: results are identical. */
+int rs16_host_paired_rows(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count, uint32_t seg_chunk,
+                          uint32_t row_base_in, int diag);
 /* The shape of the launch by which rs16_update_device updates `rows` recovery
  * rows of `shard_bytes` from `n` deltas, as the launcher computes it (one host
  * function, which every update calls; no device needed):

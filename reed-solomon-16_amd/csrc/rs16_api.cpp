@@ -147,6 +147,11 @@ extern "C" int rs16_host_pass_consts(int prog, int T, uint32_t lo, uint64_t s_in
     return rs16_host_pass_consts_many(prog, T, lo, 1, &s_in, &s_out, &s_seg, &s_rest, &qrow, chunk, row_base_in,
                                       in_rows_mask, diag, out);
 }
+extern "C" int rs16_host_paired_rows(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count,
+                                     uint32_t seg_chunk, uint32_t row_base_in, int diag) {
+    // (the function encode_high_fused and decode_passes call)
+    return paired_rows_sequence(chunk_rows, S, S_user, a_count, seg_chunk, row_base_in, diag) ? 1 : 0;
+}
 extern "C" int rs16_host_update_consts(uint32_t rows, uint64_t shard_bytes, uint32_t n, uint32_t* quads_per_lane,
                                        uint32_t* nslab, uint32_t* rows_per_wave, uint64_t* blocks) {
     // (the checks of rs16_update_device)
@@ -224,7 +229,7 @@ extern "C" int rs16_decode_check(rs16_engine* e, void* stream, rs16_error* err) 
 static constexpr int DIAG_ALL = DIAG_FORCE_VOFF64 | DIAG_EVAL_TWO_KERNEL | DIAG_EVAL_FULL | DIAG_NO_COLUMN |
                                 DIAG_FORCE_COLUMN | DIAG_TILE_LAST | DIAG_NO_TILE_LAST | DIAG_FD_LDS |
                                 DIAG_COL_RADIX4 | DIAG_NO_IDENTITY | DIAG_NO_MID_DIRECT | DIAG_WIDE_TWIDDLES |
-                                DIAG_NO_LATE_ROWS;
+                                DIAG_NO_LATE_ROWS | DIAG_NO_PAIRED_ROWS;
 extern "C" int rs16_engine_set_diagnostics(rs16_engine* e, int flags) {
     const int old = e->diag;
     e->diag = flags & DIAG_ALL;

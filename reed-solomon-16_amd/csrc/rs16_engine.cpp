@@ -94,6 +94,10 @@ static PassArgs base_args(const rs16_engine* e, size_t S) {
     a.S_in = a.S_out = a.S_seg = a.S_rest = S;
     a.qrow = (uint32_t)(S / 8);
     a.diag = (uint32_t)e->diag;
+    // the work buffer's rows in the reference form: only the two sequences
+    // that ask paired_rows_sequence (encode_high_fused, the identity decode)
+    // set anything else, for their own three launches
+    a.paired = 0;
     return a;
 }
 
@@ -397,16 +401,21 @@ int rs16_engine::encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, 
     // 8 / 7 / 8 split measured 2-3 us slower per encode, CHANGELOG.md round 3)
     const int lo = L / 2, hi = L - lo;
     const size_t zs = chunk * S;
+    // Z in the paired row form between the three passes, or not at all
+    const bool paired = paired_rows_sequence((uint32_t)chunk, S, S_user, a.a_count, a.chunk, a.row_base_in, diag);
     a.out = Z;
     a.lo = 0;
+    a.paired = paired ? paired_sides_of(ENC_FIRST) : 0;
     RS16_PASS(ENC_FIRST, lo, a, batch(1u << hi, 0, zs, bs_orig), s);
     a.in = Z;
     a.lo = lo;
+    a.paired = paired ? paired_sides_of(ENC_MID) : 0;
     RS16_PASS(ENC_MID, hi, a, batch(1u << lo, zs, zs, 0), s);
     a.in = Z;
     a.out = d_rec;
     a.S_out = S_user;
     a.lo = 0;
+    a.paired = paired ? paired_sides_of(ENC_LAST) : 0;
     const uint32_t tiles = (uint32_t)((m + ((size_t)1 << lo) - 1) >> lo);
     RS16_PASS(ENC_LAST, lo, a, batch(tiles, zs, bs_rec, 0), s);
     return RS16_OK;
@@ -650,17 +659,22 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
             a.cnt_flags = g.high ? flags_a : flags_b;
             a.cnt_base = src;
             a.cnt_seg = g.high ? 0 : 1;
+            // (Z in the paired row form between these three passes, as in the encode)
+            const bool paired = paired_rows_sequence(half, S, S_user, a.a_count, a.chunk, a.row_base_in, diag);
             a.lo = 0;
             a.out = Z;
+            a.paired = paired ? paired_sides_of(ENC_FIRST) : 0;
             RS16_PASS_AS(PROF_DEC_HALF_FIRST, ENC_FIRST, lo, a, batch(1u << hi, 0, 0, zs), s);
             a.rcount = nullptr;
             a.lo = lo;
             a.in = Z;
+            a.paired = paired ? paired_sides_of(ENC_MID) : 0;
             RS16_PASS_AS(PROF_DEC_HALF_MID, ENC_MID, hi, a, batch(1u << lo, zs, 0, zs), s);
             a.lo = 0;
             a.out = rest;
             a.S_out = S_user;
             a.out_rows = orig;
+            a.paired = paired ? paired_sides_of(ENC_LAST) : 0;
             a.rcount = rcount;
             a.cnt_flags = g.high ? flags_b : flags_a;
             a.cnt_base = dst;
@@ -708,6 +722,8 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
             return col(c, Lh, COL_DEC_EWORK, s, err);
         }
         const int lo = Lh / 2, hi = Lh - lo;
+        // (unpaired: this ENC_MID reads the rows a decoder pass wrote)
+        a.paired = 0;
         a.lo = 0;
         a.out = Z;
         RS16_PASS_AS(PROF_DEC_HALF_FIRST, DEC_FIRST, lo, a, batch(1u << hi, 0, 0, zs), s);

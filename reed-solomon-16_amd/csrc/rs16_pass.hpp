@@ -422,7 +422,18 @@ template <int P> struct LateDepth {
     static constexpr int SHIPPED = 8;
     static constexpr int value = RS16_LATE_DEPTH > 0 ? RS16_LATE_DEPTH : SHIPPED;
 };
-template <int P, int T> struct LateRows {
+// PAIR (paired rows): the rows are in the paired form of the work buffer Z
+// (quad Qg of a row at bytes [8 Qg, 8 Qg + 8), low dword
+// first) and a request is one 8-byte load into (L[m], H[m]).  Paired launches
+// are full_lanes launches of the plain loads (launch_pass): every lane has a
+// quad and no wave reads the zero page.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) u32x2 gu32x2;
+typedef __attribute__((address_space(1))) uint64_t gu64;
+// byte offset of the lane's quad in a paired row, from its offset offL =
+// (Qg >> 3) * 64 + (Qg & 7) * 4 in the reference form: 8 Qg
+__device__ __forceinline__ uint32_t pair_off(uint32_t offL) { return offL + (offL & 28u); }
+template <int P, int T, bool PAIR = false> struct LateRows {
     using G = Geo<T>;
     static constexpr bool START_B = !ProgTraits<P>::IFFT;
     static constexpr bool GATHER = ProgTraits<P>::LOAD == LD_GATHER_ENC;
@@ -430,6 +441,7 @@ template <int P, int T> struct LateRows {
     static constexpr int NP = G::NR / 2;               // its pairs
     static constexpr int D = LateDepth<P>::value < NP ? LateDepth<P>::value : NP;
     static_assert(D >= 1 && G::R == 4, "late rows: 16-row sets");
+    static_assert(!PAIR || !GATHER, "paired rows: the work buffer, not the caller's shards");
     uint64_t p;         // the wave's row register 0 (uniform)
     uint32_t rs, voff;  // stride of consecutive row registers (uniform), the lane's offset
     __device__ __forceinline__ LateRows(const PassArgs& a, const Thr& c) {
@@ -437,6 +449,12 @@ template <int P, int T> struct LateRows {
         // (no wave of the launch straddles the limit: below it or the zero page)
         const bool rows = !GATHER || wr.base < a.a_count;
         const uint64_t S = GATHER ? a.S_seg : a.S_in;
+        if constexpr (PAIR) {
+            rs = (uint32_t)a.rs_in;
+            voff = lane_rows<T, START_B>(c, a) * (uint32_t)S + pair_off(c.offL);
+            p = (uint64_t)a.in + (uint64_t)wr.base * S;
+            return;
+        }
         // (a lane without a quad requests the first quad of its slab: request_rows' CLAMP)
         const uint32_t offL = !c.active ? ((c.offL >> 6) - (c.qt >> 3)) * 64 : c.offL;
         rs = rows ? (uint32_t)(GATHER ? a.rs_seg : a.rs_in) : 0u;
@@ -453,6 +471,12 @@ template <int P, int T> struct LateRows {
 #pragma unroll
         for (int i = 0; i < 2; i++) {
             const int mi = m + (i << RB);
+            if constexpr (PAIR) {
+                const u32x2 x = *(const gu32x2*)(sgpr_ptr((const uint8_t*)(p + (uint32_t)mi * rs)) + v);
+                L[mi] = x.x;
+                H[mi] = x.y;
+                continue;
+            }
             const gu32* g = (const gu32*)(sgpr_ptr((const uint8_t*)(p + (uint32_t)mi * rs)) + v);
             L[mi] = g[0];
             H[mi] = g[8];
@@ -477,7 +501,11 @@ template <int P, int T> struct LateRows {
 // The stores' side: row register m at base + m x rs_out (launch_pass: the
 // offsets of all row registers fit 32 bits when full_lanes is set), in any
 // order -- the early stores come from inside the last layer block.
-template <int P, int T> struct FastStore {
+// PAIR: the rows go out in the paired form, one 8-byte store per row (a
+// paired launch is a full_lanes launch of the plain stores: `on` in every wave).
+template <int P, int T, bool PAIR = false> struct FastStore {
+    static_assert(!PAIR || (FastRows<P, T>::STORE && ProgTraits<P>::STORE == ST_PLAIN),
+                  "paired rows: the plain stores' full-item form");
     static constexpr bool END_B = !ProgTraits<P>::FFT && T > 4;
     const PassArgs& a;
     const Thr& cs;
@@ -494,6 +522,16 @@ template <int P, int T> struct FastStore {
     __device__ __forceinline__ void row(int m, uint32_t L, uint32_t H) const {
         // (the lane offset from cs.offL at each store, as the general path
         // forms it: kept across the early stores' layer block it costs a VGPR)
+        if constexpr (PAIR) {
+            const uint32_t voff = lane_rows<T, END_B>(cs, a) * (uint32_t)a.S_out + pair_off(cs.offL);
+            gu64* g = (gu64*)(sgpr_ptr((const uint8_t*)(p + (uint32_t)m * (uint32_t)a.rs_out)) + voff);
+            // (as one 64-bit value: built as the vector {L, H}, the kernels
+            // keep their row registers in scratch, 72 bytes per lane)
+            const uint64_t x = ((uint64_t)H << 32) | L;
+            if constexpr (ProgTraits<P>::ST_NT) __builtin_nontemporal_store(x, g);
+            else *g = x;
+            return;
+        }
         const uint32_t voff = lane_rows<T, END_B>(cs, a) * (uint32_t)a.S_out + cs.offL;
         gu32* g = (gu32*)(sgpr_ptr((const uint8_t*)(p + (uint32_t)m * (uint32_t)a.rs_out)) + voff);
         if constexpr (ProgTraits<P>::ST_NT) {
@@ -1499,15 +1537,15 @@ __device__ __forceinline__ void store_rows(const PassArgs& a, const Thr& cs, con
 // so rows m, m + 1 are final as soon as their layer-0 group is done; this
 // functor stores them there, spreading the item's stores over the block
 // instead of a burst after it.
-template <int P, int T> struct EarlyStore {
+template <int P, int T, bool PAIR = false> struct EarlyStore {
     const PassArgs& a;
     const Thr& cs;
     const uint4* rvt;
     const uint32_t* lostf;
-    const FastStore<P, T> fs;
+    const FastStore<P, T, PAIR> fs;
     __device__ __forceinline__ void operator()(const uint32_t (&L)[Geo<T>::NR], const uint32_t (&H)[Geo<T>::NR],
                                                int m) const {
-        if (fs.on) {
+        if (PAIR || fs.on) {
             fs.row(m, L[m], H[m]);
             fs.row(m + 1, L[m + 1], H[m + 1]);
         } else if (a.voff32) {
@@ -1587,12 +1625,12 @@ __device__ __forceinline__ void ifft_b_halves(uint32_t (&L)[Geo<T>::NR], uint32_
     HalfLoop<T, 0, FIN>::run(L, H, tab1, t0, fin);
 }
 // fin of ifft_b_halves: the even rows
-template <int P, int T> struct EvenStore {
+template <int P, int T, bool PAIR = false> struct EvenStore {
     const PassArgs& a;
     const Thr& cs;
-    const FastStore<P, T> fs;
+    const FastStore<P, T, PAIR> fs;
     __device__ __forceinline__ void operator()(const uint32_t (&L)[Geo<T>::NR], const uint32_t (&H)[Geo<T>::NR]) const {
-        if (fs.on) {
+        if (PAIR || fs.on) {
 #pragma unroll
             for (int m = 0; m < Geo<T>::NR; m += 2) fs.row(m, L[m], H[m]);
             return;
@@ -1607,8 +1645,9 @@ template <int P, int T> struct EvenStore {
 
 // Compute and store one item whose rows are in d (every thread of the
 // workgroup calls it for the same item).
-// (PRE: the late-rows kernels' requests inside the first layer block, LateRows)
-template <int P, int T, int NV, class PRE = NoPre>
+// (PRE: the late-rows kernels' requests inside the first layer block, LateRows;
+// PAIR_OUT: the stores write paired rows, FastStore)
+template <int P, int T, int NV, class PRE = NoPre, bool PAIR_OUT = false>
 __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, uint32_t tile, ItemRegs<P, T>& d,
                                              uint8_t* smem, const PRE& pre = PRE()) {
     using PT = ProgTraits<P>;
@@ -1726,7 +1765,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
             if constexpr (EARLY_B) {
                 Thr cs = c;
                 asm volatile("" : "+v"(cs.offL));
-                ifft_b_halves<T>(L, H, tab1, EvenStore<P, T>{a, cs, FastStore<P, T>(a, cs)});
+                ifft_b_halves<T>(L, H, tab1, EvenStore<P, T, PAIR_OUT>{a, cs, FastStore<P, T, PAIR_OUT>(a, cs)});
             } else {
                 // (SHARED: the layout-B tables t >= TSPLIT sit beside the image)
                 const uint4* tab1b = SM::SHARED ? (const uint4*)(smem + SM::TABB_OFF) - G::TSPLIT * 5 : tab1;
@@ -1823,8 +1862,9 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
             Thr cs = c;
             asm volatile("" : "+v"(cs.offL));
             layers<P, T, NKF, false, 0, R, true, (TWO && !(SM::RESTAGE))>(L, H, c, a, tab1, tab2, 0,
-                                                                        EarlyStore<P, T>{a, cs, rvt, lostf,
-                                                                                         FastStore<P, T>(a, cs)});
+                                                                        EarlyStore<P, T, PAIR_OUT>{
+                                                                            a, cs, rvt, lostf,
+                                                                            FastStore<P, T, PAIR_OUT>(a, cs)});
         } else if (need) {
             layers<P, T, NKF, false, 0, R, true, (TWO && !(SM::RESTAGE))>(L, H, c, a, tab1, tab2);
         }
@@ -1851,8 +1891,8 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
     cs.b_high = uni(cs.b_high);
     asm volatile("" : "+s"(cs.b_low), "+s"(cs.b_high));
     asm volatile("" : "+v"(cs.offL));
-    const FastStore<P, T> fs(a, cs);
-    if (fs.on) {
+    const FastStore<P, T, PAIR_OUT> fs(a, cs);
+    if (PAIR_OUT || fs.on) {
         // (EARLY_B: the even rows went out inside the last block)
 #pragma unroll
         for (int m = EARLY_B ? 1 : 0; m < NR; m += EARLY_B ? 2 : 1) fs.row(m, L[m], H[m]);
@@ -2057,6 +2097,64 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, 4) pass_kernel_late(PassArgs 
     process_item<P, T, NV, LateRows<P, T>>(a, c, tile, cur, smem, rq);
     rcn.store(a, c);
 }
+// The same kernel reading (PAIR_IN) and / or writing (PAIR_OUT) the work
+// buffer's rows in the paired form (LateRows, FastStore) -- a compile-time
+// choice, because a guarded block at the request sites is what the late-rows
+// variant exists to avoid.  (A kernel of its own name, written out: with one
+// more template parameter, or with its body in a function shared with the
+// flavours, pass_kernel_late compiles to other machine code.)
+template <int P, int T, int NV, bool PAIR_IN, bool PAIR_OUT>
+__global__ void __launch_bounds__(Geo<T>::THREADS, 4) pass_kernel_late_paired(PassArgs a) {
+    static_assert(PAIR_IN || PAIR_OUT, "the unpaired kernel is pass_kernel_late");
+    using G = Geo<T>;
+    static_assert(WaveStaged<P, T>::value, "late rows: the wave-staged passes");
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t item = blockIdx.x;
+
+    Thr c;
+    c.lane = threadIdx.x & 63;
+    c.w = uni(threadIdx.x >> 6);
+    c.qt = c.lane % G::Q;
+    c.s = c.w * G::HWS + c.lane / G::Q;
+    c.ql = c.qt % Rnd<P, T>::QL;
+    c.round = c.qt / Rnd<P, T>::QL;
+
+    uint32_t tile, slab;
+    set_item(c, a, item, G::Q, tile, slab);
+
+    bool first_stripe = true;
+    if (a.stripe_tiles) {
+        const uint32_t st = uni(fast_div(tile, a.stripe_mul, a.stripe_one));
+        first_stripe = st == 0;
+        tile -= st * a.stripe_tiles;
+        stripe_displace(a, st);
+    }
+    tile += a.tile_base;
+    c.b_low = tile & ((1u << a.lo) - 1);
+    c.b_high = tile >> a.lo;
+    RcvCount<P, T> rcn;
+    rcn.issue(a, c, slab == 0 && first_stripe);
+    RS16_STAMP(a, 0);
+    // (load-issue order by workgroup slot, as pass_kernel)
+    const uint32_t slot = (__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 16) & 15u;
+    if (slot == 0) __builtin_amdgcn_s_setprio(3);
+    else if (slot == 1) __builtin_amdgcn_s_setprio(2);
+    else if (slot == 2) __builtin_amdgcn_s_setprio(1);
+    TileStage<P, T> st;
+    st.issue(a, c);
+    ItemRegs<P, T> cur;
+    cur.zrow = cur.zmask = 0;
+    cur.ztile = false;
+    const LateRows<P, T, PAIR_IN> rq(a, c);
+    rq.prologue(cur.L, cur.H);
+    RS16_STAMP(a, 1);
+    prio<0>();
+    st.template finish<false>(a, c, smem);
+    rcn.count();
+    RS16_STAMP(a, 2);
+    process_item<P, T, NV, LateRows<P, T, PAIR_IN>, PAIR_OUT>(a, c, tile, cur, smem, rq);
+    rcn.store(a, c);
+}
 
 // ---------------------------------------------------------------------------
 // What an instantiation unit builds its PassKernel lookup from: taking a
@@ -2065,6 +2163,12 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, 4) pass_kernel_late(PassArgs 
 template <int P, int T, int NV> PassFn late_entry() {
     if constexpr (WaveStaged<P, T>::value) return pass_kernel_late<P, T, NV>;
     else return nullptr;
+}
+// the paired flavour of program P's late-rows kernel (ENC_FIRST writes paired
+// rows, ENC_MID reads and writes them, ENC_LAST reads them)
+template <int P, int T, int NV = 0> PassFn paired_entry() {
+    static_assert(P == ENC_FIRST || P == ENC_MID || P == ENC_LAST, "paired rows: the encoder's three passes");
+    return pass_kernel_late_paired<P, T, NV, P != ENC_FIRST, P != ENC_LAST>;
 }
 template <int P, int T, int NV = 0> PassKernel pass_entry() {
     using PT = ProgTraits<P>;

@@ -27,6 +27,11 @@ struct PassKernel {
     // below the row limit a_count (ENC_FIRST).
     PassFn late;
     int gather;
+    // The paired-rows flavour of the late-rows variant (pass_kernel_late with
+    // PAIR_IN / PAIR_OUT; nullptr: none): ENC_FIRST writes the work buffer's
+    // rows in the paired form, ENC_MID reads and writes them, ENC_LAST reads
+    // them.  Only the kernels a paired sequence can launch exist.
+    PassFn paired = nullptr;
 };
 // The launch constants that decide a launch's address forms (the PassArgs
 // fields of the same names), as launch_pass sets them from the kernel's

@@ -1,12 +1,34 @@
 // rs16_pass_enc.hip -- the pass kernels of the encoder and of the plain
 // transforms: GEN_FFT, GEN_IFFT, ENC_FIRST, ENC_MID (with its narrow-twiddle
-// variants), ENC_LAST and ENC_SINGLE at T = 0 .. 8.  (Encoder and decoder
-// programs in one unit each: see the Makefile on why not finer.)
+// variants), ENC_LAST and ENC_SINGLE at T = 0 .. 8, and the paired-rows
+// flavours of the late-rows ENC_FIRST / ENC_MID / ENC_LAST kernels.  (Encoder
+// and decoder programs in one unit each: see the Makefile on why not finer.)
 #include "rs16_pass.hpp"
 
 namespace rs16 {
 
-PassKernel pass_kernels_enc(int prog, int T, int nv) {
+// The paired-rows flavours (pass_kernel_late with PAIR_IN / PAIR_OUT), only
+// for the kernels a paired sequence can launch: three late-rows passes exist
+// for chunks of 2^14 rows (T = 7 / 7 / 7) and 2^15 rows (7 / 8 / 7).
+static PassFn paired_kernel(int prog, int T, int nv) {
+    if (prog == ENC_FIRST && T == 7 && nv == 0) return paired_entry<ENC_FIRST, 7>();
+    if (prog == ENC_LAST && T == 7 && nv == 0) return paired_entry<ENC_LAST, 7>();
+    if (prog == ENC_MID && T == 7) {
+        if (nv == 0) return paired_entry<ENC_MID, 7, 0>();
+        if (nv == 1) return paired_entry<ENC_MID, 7, 1>();
+    }
+    if (prog == ENC_MID && T == 8) {
+        switch (nv) {
+            case 0: return paired_entry<ENC_MID, 8, 0>();
+            case 1: return paired_entry<ENC_MID, 8, 1>();
+            case 2: return paired_entry<ENC_MID, 8, 2>();
+            case 3: return paired_entry<ENC_MID, 8, 3>();
+        }
+    }
+    return nullptr;
+}
+
+static PassKernel unpaired_kernels_enc(int prog, int T, int nv) {
     if (prog == ENC_MID) {
         switch (nv) {
             case 0: return pass_row<ENC_MID>(T);
@@ -27,6 +49,12 @@ PassKernel pass_kernels_enc(int prog, int T, int nv) {
         case ENC_SINGLE: return pass_row<ENC_SINGLE>(T);
         default: return {};
     }
+}
+
+PassKernel pass_kernels_enc(int prog, int T, int nv) {
+    PassKernel k = unpaired_kernels_enc(prog, T, nv);
+    if (k.fn) k.paired = paired_kernel(prog, T, nv);
+    return k;
 }
 
 }  // namespace rs16

@@ -94,6 +94,36 @@ PassConsts pass_launch_consts(const PassKernel& k, int T, const PassArgs& a) {
     return c;
 }
 
+// The three launches of a sequence as rs16_engine plans them (encode_high_fused,
+// the identity branch of decode_passes): L / 2 contiguous row bits gathered
+// from the caller's rows (stride S_user), L - L / 2 strided ones on the work
+// buffer, L / 2 contiguous ones stored to the caller's rows.
+bool paired_rows_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count, uint32_t seg_chunk,
+                          uint32_t row_base_in, int diag) {
+    if (diag & DIAG_NO_PAIRED_ROWS) return false;
+    if (chunk_rows < 512 || (chunk_rows & (chunk_rows - 1)) || S == 0 || S % 8 || S / 8 > 0xFFFFFFFFu) return false;
+    int L = 0;
+    while (((uint32_t)1 << L) < chunk_rows) L++;
+    const int lo = L / 2, hi = L - lo;
+    PassArgs a{};
+    a.S_in = a.S_out = a.S_rest = S;
+    a.S_seg = S_user;
+    a.qrow = (uint32_t)(S / 8);
+    a.a_count = a_count, a.chunk = seg_chunk, a.row_base_in = row_base_in;
+    a.diag = (uint32_t)diag;
+    const struct { int prog, T; uint32_t lo; uint64_t S_out; } seq[3] = {
+        {ENC_FIRST, lo, 0, S}, {ENC_MID, hi, (uint32_t)lo, S}, {ENC_LAST, lo, 0, S_user}};
+    for (const auto& p : seq) {
+        if (p.T > 8) return false;
+        // (the geometry and the flavours of (prog, T) are those of every narrow variant)
+        const PassKernel& k = find_kernel(p.prog, p.T, 0);
+        a.lo = p.lo, a.S_out = p.S_out;
+        const PassConsts c = pass_launch_consts(k, p.T, a);
+        if (!k.fn || !k.paired || !c.late_rows || !c.full_lanes) return false;
+    }
+    return true;
+}
+
 hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles, hipStream_t s) {
     if (prog < 0 || prog >= NUM_PROGS || T < 0 || T > 8) return hipErrorInvalidValue;
     if (num_tiles == 0 || args.qrow == 0) return hipSuccess;
@@ -120,7 +150,15 @@ hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles
     a.nslab_mul = dn.mul, a.nslab_one = dn.one;
     a.stripe_mul = ds.mul, a.stripe_one = ds.one;
     const size_t lds = (size_t)k.lds;
-    const PassFn fn = pc.late_rows ? k.late : k.fn;
+    PassFn fn = pc.late_rows ? k.late : k.fn;
+    if (a.paired) {
+        // Paired rows are the sequence's choice (paired_rows_sequence): a
+        // launch that cannot keep it is an error, never the other form --
+        // its neighbour pass would read or write the rows the other way.
+        if (a.paired != paired_sides_of(prog) || !k.paired || !pc.late_rows || !pc.full_lanes)
+            return hipErrorInvalidValue;
+        fn = k.paired;
+    }
     if (lds > 65536) {
         // (per kernel variant: each is a function of its own)
         hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -29,21 +29,31 @@ wait, the loads that wait retires.  Expected:
                pair g are in flight: 4 min(D, 7 - g)
     form       every late request is an SGPR-base load
     no s_barrier, and no vmcnt(0) before the wait for the last pair
+
+The paired-rows flavours (pass_kernel_late_paired) that read paired rows
+request a row with one global_load_dwordx2: 2 D requests in the prologue and
+exactly 2 min(D, 7 - g) in flight at butterfly g; the rest as above.  (The
+flavour of the gathering first pass reads the caller's rows with dword loads
+and is checked as the unpaired kernel is.)
 """
 import re
 import sys
 
 KERNEL = re.compile(r"^_ZN4rs1611pass_kernelILi([234])ELi([78])ELi(\d)EEEvNS_8PassArgsE:")
 LATE = re.compile(r"^_ZN4rs1616pass_kernel_lateILi([234])ELi([78])ELi(\d)EEEvNS_8PassArgsE:")
+PAIRED = re.compile(r"^_ZN4rs1623pass_kernel_late_pairedILi([234])ELi([78])ELi(\d)ELb([01])ELb([01])EEEvNS_8PassArgsE:")
 NAMES = {"2": "ENC_FIRST", "3": "ENC_MID", "4": "ENC_LAST"}
 VM = re.compile(r"s_waitcnt.*vmcnt\((\d+)\)")
 ROW_LOAD = re.compile(r"^global_load_dword\s")
+ROW_LOAD2 = re.compile(r"^global_load_dwordx2\s")
 SADDR = re.compile(r"\bs\[\d+:\d+\]")
 NP = 8  # pairs of the first layer (16 rows per lane)
 
 
-def late_kernel(lines, i, name):
-    """Check one late-rows kernel that starts at line i; returns (ok, next line)."""
+def late_kernel(lines, i, name, row_load=ROW_LOAD, per=4):
+    """Check one late-rows kernel that starts at line i; returns (ok, next line).
+    row_load / per: the row request's instruction and the requests per pair of
+    rows (4 dword loads; 2 dwordx2 loads of paired rows)."""
     k = i
     marker = None
     loads_before = 0
@@ -52,13 +62,13 @@ def late_kernel(lines, i, name):
         if "late rows: prologue requested" in t:
             marker = k
             break
-        if ROW_LOAD.match(t):
+        if row_load.match(t):
             loads_before += 1
         k += 1
-    if marker is None or loads_before % 4 or not 0 < loads_before <= 4 * NP:
+    if marker is None or loads_before % per or not 0 < loads_before <= per * NP:
         print("%-34s no prologue marker / %d row loads before it  UNEXPECTED" % (name, loads_before))
         return False, k
-    D = loads_before // 4
+    D = loads_before // per
     requested = loads_before   # row loads requested so far
     done = 0                   # ... retired by the waits so far
     last = None
@@ -71,22 +81,22 @@ def late_kernel(lines, i, name):
         w = VM.search(t)
         if w:
             last = int(w.group(1))
-            if last == 0 and (requested < 4 * NP or done < 4 * (NP - 1)):
+            if last == 0 and (requested < per * NP or done < per * (NP - 1)):
                 early_zero = True
             done = max(done, requested - last)
-        elif ROW_LOAD.match(t):
+        elif row_load.match(t):
             requested += 1
             vaddr += not SADDR.search(t)
         elif t.startswith("s_barrier"):
             barrier = True
         elif t.startswith("ds_write_b128") and wait_tab is None:
             wait_tab = last
-        elif t.startswith("v_perm_b32") and done >= 4 * (len(flight) + 1):
+        elif t.startswith("v_perm_b32") and done >= per * (len(flight) + 1):
             # (retired past pair g + 1 before butterfly g ran: a wait too deep)
-            flight.append(requested - done if done == 4 * (len(flight) + 1) else -1)
+            flight.append(requested - done if done == per * (len(flight) + 1) else -1)
         k += 1
-    want = [4 * min(D, NP - 1 - g) for g in range(NP)]
-    ok = (wait_tab is not None and wait_tab >= 4 * D and flight == want and requested == 4 * NP and not vaddr
+    want = [per * min(D, NP - 1 - g) for g in range(NP)]
+    ok = (wait_tab is not None and wait_tab >= per * D and flight == want and requested == per * NP and not vaddr
           and not barrier and not early_zero)
     print("%-34s D %d  tables vmcnt(%s)  in flight at butterflies %s  VGPR-pair requests %d  barrier: %s  "
           "early vmcnt(0): %s  %s" % (name, D, wait_tab, ",".join(map(str, flight)), vaddr,
@@ -103,6 +113,15 @@ def main():
         m = LATE.match(lines[i])
         if m:
             ok, i = late_kernel(lines, i, "pass_kernel_late<%s,%s,%s>" % (NAMES[m.group(1)], m.group(2), m.group(3)))
+            bad += not ok
+        m = PAIRED.match(lines[i]) if i < len(lines) else None
+        if m:
+            name = "late_paired<%s,%s,%s,in %s,out %s>" % (NAMES[m.group(1)], m.group(2), m.group(3), m.group(4),
+                                                          m.group(5))
+            if m.group(4) == "1":
+                ok, i = late_kernel(lines, i, name, ROW_LOAD2, 2)
+            else:
+                ok, i = late_kernel(lines, i, name)
             bad += not ok
         i += 1
     i = 0
