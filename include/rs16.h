@@ -588,11 +588,15 @@ enum {
                                       ahead of the first layer (default: a launch none of whose waves
                                       needs the general row loads requests most of them from inside
                                       the first layer; rs16_pass_consts.late_rows) */
-    RS16_DIAG_NO_PAIRED_ROWS = 8192 /* the engine's work buffer keeps the shard layout between the passes
+    RS16_DIAG_NO_PAIRED_ROWS = 8192, /* the engine's work buffer keeps the shard layout between the passes
                                       of every sequence (default: the three-pass encode and the identity
                                       decode of 2^14 / 2^15-row chunks, widths a multiple of 512 bytes,
                                       keep a quad's two dwords next to each other there and move a row
                                       with one 8-byte access per lane; rs16_host_paired_rows) */
+    RS16_DIAG_NO_TOWER_ROWS = 16384 /* paired rows of the work buffer stay in the shards' coordinates
+                                      (default: they are kept as a + b beta over the GF(2^8) subfield, in
+                                      which the middle pass multiplies by a subfield twiddle with 6
+                                      lookups instead of 9; rs16_host_tower_rows) */
 };
 int rs16_engine_set_diagnostics(rs16_engine* eng, int flags);
 /* Deprecated (the round-4 process-wide form, kept for existing callers):
@@ -679,6 +683,25 @@ int rs16_host_pass_consts_rows(int prog, int T, uint32_t lo, uint64_t s_in, uint
  * encode).  The form never leaves the engine: results are identical. */
 int rs16_host_paired_rows(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count, uint32_t seg_chunk,
                           uint32_t row_base_in, int diag);
+/* Tower form of the work buffer's paired rows.  With beta = v_8 of the Cantor
+ * basis every element (lo, hi) is a + b beta, a = lo ^ B(hi) and b = hi in the
+ * GF(2^8) subfield; v_{8+i} = a_i + v_i beta gives B's columns a_i.
+ * rs16_host_tower_rows: rs16_host_paired_rows for the tower form -- 1 exactly
+ * when the sequence is paired and RS16_DIAG_NO_TOWER_ROWS is not set.
+ * rs16_host_tower_basis: a_i as the tables derived it (i < 8; else ~0).
+ * rs16_host_tower_conv: out[] = in[] switched between the two forms (the
+ * kernels' lookups, v_perm emulated; its own inverse), `bytes` a multiple of 64.
+ * rs16_host_tower_twiddle: the 20-dword table of skew index `index` in tower
+ * coordinates, as the middle pass of a tower sequence stages it (0: out of range).
+ * rs16_host_mul_tower: out[] = that table applied to in[] (tower form in and
+ * out), with the 12-lookup multiply or, `narrow` != 0, the 6-lookup one of the
+ * layers whose twiddles are subfield elements. */
+int rs16_host_tower_rows(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count, uint32_t seg_chunk,
+                         uint32_t row_base_in, int diag);
+uint32_t rs16_host_tower_basis(uint32_t i);
+void rs16_host_tower_conv(const void* in, void* out, size_t bytes);
+int rs16_host_tower_twiddle(uint32_t index, uint32_t* table20);
+void rs16_host_mul_tower(const void* in, void* out, size_t bytes, uint32_t index, int narrow);
 /* The shape of the launch by which rs16_update_device updates `rows` recovery
  * rows of `shard_bytes` from `n` deltas, as the launcher computes it (one host
  * function, which every update calls; no device needed):

@@ -66,8 +66,7 @@ extern "C" size_t rs16_error_message(const rs16_error* e, char* buf, size_t len)
     return n;
 }
 
-template <class Mul> static void host_mul(const void* in, void* out, size_t bytes, uint16_t log_m, Mul mul) {
-    const uint32_t* t = &host_tables().mul_tab[(size_t)log_m * TAB_DWORDS];
+template <class F> static void host_mul_table(const void* in, void* out, size_t bytes, const uint32_t* t, F mul) {
     const uint8_t* src = (const uint8_t*)in;
     uint8_t* dst = (uint8_t*)out;
     for (size_t q = 0; q < bytes / 8; q++) {
@@ -79,6 +78,9 @@ template <class Mul> static void host_mul(const void* in, void* out, size_t byte
         memcpy(dst + off, &ol, 4);
         memcpy(dst + off + 32, &oh, 4);
     }
+}
+template <class Mul> static void host_mul(const void* in, void* out, size_t bytes, uint16_t log_m, Mul mul) {
+    host_mul_table(in, out, bytes, &host_tables().mul_tab[(size_t)log_m * TAB_DWORDS], mul);
 }
 extern "C" void rs16_host_mul(const void* in, void* out, size_t bytes, uint16_t log_m) {
     host_mul(in, out, bytes, log_m, mul_xor);
@@ -151,6 +153,37 @@ extern "C" int rs16_host_paired_rows(uint32_t chunk_rows, uint64_t S, uint64_t S
                                      uint32_t seg_chunk, uint32_t row_base_in, int diag) {
     // (the function encode_high_fused and decode_passes call)
     return paired_rows_sequence(chunk_rows, S, S_user, a_count, seg_chunk, row_base_in, diag) ? 1 : 0;
+}
+extern "C" int rs16_host_tower_rows(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count,
+                                    uint32_t seg_chunk, uint32_t row_base_in, int diag) {
+    // (the function encode_high_fused and decode_passes call)
+    return tower_rows_sequence(chunk_rows, S, S_user, a_count, seg_chunk, row_base_in, diag) ? 1 : 0;
+}
+extern "C" uint32_t rs16_host_tower_basis(uint32_t i) { return i < 8 ? host_tables().tower_a[i] : ~0u; }
+extern "C" void rs16_host_tower_conv(const void* in, void* out, size_t bytes) {
+    // (the kernels' code path: B's pools through tower_conv, v_perm emulated)
+    TowerB tb;
+    memcpy(tb.p, host_tables().tower_b, sizeof tb.p);
+    const uint8_t* src = (const uint8_t*)in;
+    uint8_t* dst = (uint8_t*)out;
+    for (size_t q = 0; q < bytes / 8; q++) {
+        const size_t off = (q >> 3) * 64 + (q & 7) * 4;
+        uint32_t l, h;
+        memcpy(&l, src + off, 4);
+        memcpy(&h, src + off + 32, 4);
+        tower_conv(l, h, tb);
+        memcpy(dst + off, &l, 4);
+        memcpy(dst + off + 32, &h, 4);
+    }
+}
+extern "C" int rs16_host_tower_twiddle(uint32_t index, uint32_t* table20) {
+    if (index >= GF_MODULUS) return 0;
+    if (table20) memcpy(table20, &host_tables().skew_tab_tower[(size_t)index * TAB_DWORDS], 20 * sizeof(uint32_t));
+    return 1;
+}
+extern "C" void rs16_host_mul_tower(const void* in, void* out, size_t bytes, uint32_t index, int narrow) {
+    const uint32_t* t = &host_tables().skew_tab_tower[(size_t)(index < GF_MODULUS ? index : GF_MODULUS) * TAB_DWORDS];
+    host_mul_table(in, out, bytes, t, narrow ? mul_xor_tower_narrow : mul_xor);
 }
 extern "C" int rs16_host_update_consts(uint32_t rows, uint64_t shard_bytes, uint32_t n, uint32_t* quads_per_lane,
                                        uint32_t* nslab, uint32_t* rows_per_wave, uint64_t* blocks) {
@@ -229,7 +262,7 @@ extern "C" int rs16_decode_check(rs16_engine* e, void* stream, rs16_error* err) 
 static constexpr int DIAG_ALL = DIAG_FORCE_VOFF64 | DIAG_EVAL_TWO_KERNEL | DIAG_EVAL_FULL | DIAG_NO_COLUMN |
                                 DIAG_FORCE_COLUMN | DIAG_TILE_LAST | DIAG_NO_TILE_LAST | DIAG_FD_LDS |
                                 DIAG_COL_RADIX4 | DIAG_NO_IDENTITY | DIAG_NO_MID_DIRECT | DIAG_WIDE_TWIDDLES |
-                                DIAG_NO_LATE_ROWS | DIAG_NO_PAIRED_ROWS;
+                                DIAG_NO_LATE_ROWS | DIAG_NO_PAIRED_ROWS | DIAG_NO_TOWER_ROWS;
 extern "C" int rs16_engine_set_diagnostics(rs16_engine* e, int flags) {
     const int old = e->diag;
     e->diag = flags & DIAG_ALL;
@@ -349,11 +382,13 @@ extern "C" rs16_engine* rs16_engine_new_ex(int device, int flags, rs16_error* er
     }
     e->flags = flags;
     if ((he = hipMalloc(&e->d_skew_tab, (size_t)GF_ORDER * TAB_DWORDS * 4)) != hipSuccess) return fail(he);
+    if ((he = hipMalloc(&e->d_skew_tab_tower, (size_t)GF_ORDER * TAB_DWORDS * 4)) != hipSuccess) return fail(he);
     if ((he = hipMalloc(&e->d_mul_tab, t.mul_tab.size() * 4)) != hipSuccess) return fail(he);
     if ((he = hipMalloc(&e->d_log_walsh, GF_ORDER * 2)) != hipSuccess) return fail(he);
     if ((he = hipMalloc(&e->d_zero_sink, RS16_ZERO_BYTES)) != hipSuccess) return fail(he);
     if ((he = hipMemset(e->d_zero_sink, 0, RS16_ZERO_BYTES)) != hipSuccess) return fail(he);
     if ((he = hipMemcpy(e->d_skew_tab, t.skew_tab.data(), t.skew_tab.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(he);
+    if ((he = hipMemcpy(e->d_skew_tab_tower, t.skew_tab_tower.data(), t.skew_tab_tower.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(he);
     if ((he = hipMemcpy(e->d_mul_tab, t.mul_tab.data(), t.mul_tab.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(he);
     if ((he = hipMemcpy(e->d_log_walsh, t.log_walsh.data(), GF_ORDER * 2, hipMemcpyHostToDevice)) != hipSuccess) return fail(he);
     set_error(err, RS16_OK);
@@ -400,6 +435,7 @@ extern "C" void rs16_engine_free(rs16_engine* e) {
     }
     if (e->sl_fork) (void)hipEventDestroy(e->sl_fork);
     if (e->d_skew_tab) (void)hipFree(e->d_skew_tab);
+    if (e->d_skew_tab_tower) (void)hipFree(e->d_skew_tab_tower);
     if (e->d_mul_tab) (void)hipFree(e->d_mul_tab);
     if (e->d_col_img) (void)hipFree(e->d_col_img);
     if (e->d_col_v) (void)hipFree(e->d_col_v);

@@ -402,20 +402,25 @@ int rs16_engine::encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, 
     const int lo = L / 2, hi = L - lo;
     const size_t zs = chunk * S;
     // Z in the paired row form between the three passes, or not at all
+    // (and, with it, in tower form: the middle pass on the tower twiddle table)
     const bool paired = paired_rows_sequence((uint32_t)chunk, S, S_user, a.a_count, a.chunk, a.row_base_in, diag);
+    const uint32_t tower =
+        tower_rows_sequence((uint32_t)chunk, S, S_user, a.a_count, a.chunk, a.row_base_in, diag) ? PAIRED_TOWER : 0;
     a.out = Z;
     a.lo = 0;
-    a.paired = paired ? paired_sides_of(ENC_FIRST) : 0;
+    a.paired = paired ? paired_sides_of(ENC_FIRST) | tower : 0;
     RS16_PASS(ENC_FIRST, lo, a, batch(1u << hi, 0, zs, bs_orig), s);
     a.in = Z;
     a.lo = lo;
-    a.paired = paired ? paired_sides_of(ENC_MID) : 0;
+    a.paired = paired ? paired_sides_of(ENC_MID) | tower : 0;
+    if (tower) a.skew_tab = d_skew_tab_tower;
     RS16_PASS(ENC_MID, hi, a, batch(1u << lo, zs, zs, 0), s);
+    a.skew_tab = d_skew_tab;
     a.in = Z;
     a.out = d_rec;
     a.S_out = S_user;
     a.lo = 0;
-    a.paired = paired ? paired_sides_of(ENC_LAST) : 0;
+    a.paired = paired ? paired_sides_of(ENC_LAST) | tower : 0;
     const uint32_t tiles = (uint32_t)((m + ((size_t)1 << lo) - 1) >> lo);
     RS16_PASS(ENC_LAST, lo, a, batch(tiles, zs, bs_rec, 0), s);
     return RS16_OK;
@@ -661,20 +666,24 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
             a.cnt_seg = g.high ? 0 : 1;
             // (Z in the paired row form between these three passes, as in the encode)
             const bool paired = paired_rows_sequence(half, S, S_user, a.a_count, a.chunk, a.row_base_in, diag);
+            const uint32_t tower =
+                tower_rows_sequence(half, S, S_user, a.a_count, a.chunk, a.row_base_in, diag) ? PAIRED_TOWER : 0;
             a.lo = 0;
             a.out = Z;
-            a.paired = paired ? paired_sides_of(ENC_FIRST) : 0;
+            a.paired = paired ? paired_sides_of(ENC_FIRST) | tower : 0;
             RS16_PASS_AS(PROF_DEC_HALF_FIRST, ENC_FIRST, lo, a, batch(1u << hi, 0, 0, zs), s);
             a.rcount = nullptr;
             a.lo = lo;
             a.in = Z;
-            a.paired = paired ? paired_sides_of(ENC_MID) : 0;
+            a.paired = paired ? paired_sides_of(ENC_MID) | tower : 0;
+            if (tower) a.skew_tab = d_skew_tab_tower;
             RS16_PASS_AS(PROF_DEC_HALF_MID, ENC_MID, hi, a, batch(1u << lo, zs, 0, zs), s);
+            a.skew_tab = d_skew_tab;
             a.lo = 0;
             a.out = rest;
             a.S_out = S_user;
             a.out_rows = orig;
-            a.paired = paired ? paired_sides_of(ENC_LAST) : 0;
+            a.paired = paired ? paired_sides_of(ENC_LAST) | tower : 0;
             a.rcount = rcount;
             a.cnt_flags = g.high ? flags_b : flags_a;
             a.cnt_base = dst;

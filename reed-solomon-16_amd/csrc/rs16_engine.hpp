@@ -77,6 +77,7 @@ struct rs16_engine {
     // diagnostic switches of this engine (rs16::DiagFlags, rs16_engine_set_diagnostics)
     int diag = 0;
     uint32_t* d_skew_tab = nullptr;  // v_perm table per twiddle index (8 MiB)
+    uint32_t* d_skew_tab_tower = nullptr;  // the same in tower coordinates: the middle pass of a tower sequence
     uint32_t* d_mul_tab = nullptr;
     uint32_t* d_col_img = nullptr;   // column codec table images (HostTables::col_img)
     uint32_t* d_col_v = nullptr;     // column codec eval_poly tables (HostTables::col_v)

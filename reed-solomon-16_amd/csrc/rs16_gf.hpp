@@ -151,6 +151,46 @@ RS16_HD void mul_xor_narrow(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH
     mul_xor_t<true>(xL, xH, yL, yH, t);
 }
 
+// Tower form (tables: rs16_tables.cpp).  With beta =
+// v_8 every element is a + b beta with a, b in the GF(2^8) subfield: b = the
+// high byte, a = the low byte ^ B(high byte).  tower_conv switches a quad
+// between the two forms (its own inverse, the high dword stays): three
+// lookups of H's selectors in B's pools tb[0 .. 4] (groups H0-2, H3-5, H6-7).
+// In tower form a subfield constant multiplies a and b by the same byte map
+// and crosses nothing between them: mul_xor_tower_narrow, 6 lookups from
+// dwords 0, 1, 4, 5 and 16 of the constant's tower table (its L -> lo pools).
+constexpr uint32_t TOWER_B_DWORD = 20;  // B's pools: dwords 20 .. 24 of skew table entry 0
+struct TowerB {
+    uint32_t p[5];
+};
+// (s3, s4, s5 of y: the selectors of the high dword)
+RS16_HD void tower_conv_sel(uint32_t& L, const MulSel& y, const TowerB& tb) {
+    const uint32_t b0 = perm(tb.p[1], tb.p[0], y.s3);
+    const uint32_t b1 = perm(tb.p[3], tb.p[2], y.s4);
+    const uint32_t b2 = perm(tb.p[4], tb.p[4], y.s5);
+    L = xor3(L, b0, b1) ^ b2;
+}
+RS16_HD MulSel high_selectors(uint32_t H) {
+    const uint32_t a = H >> 3;
+    return MulSel{0, 0, 0, H & 0x07070707u, a & 0x07070707u, (a >> 3) & 0x03030303u};
+}
+RS16_HD void tower_conv(uint32_t& L, uint32_t H, const TowerB& tb) { tower_conv_sel(L, high_selectors(H), tb); }
+// the selectors of a row whose high dword's are known (y) and whose low dword changed since
+RS16_HD MulSel low_selectors(uint32_t L, const MulSel& y) {
+    const uint32_t a = L >> 3;
+    return MulSel{L & 0x07070707u, a & 0x07070707u, (a >> 3) & 0x03030303u, y.s3, y.s4, y.s5};
+}
+RS16_HD void mul_xor_tower_narrow_sel(uint32_t& xL, uint32_t& xH, const MulSel& y, const uint32_t* t) {
+    const uint32_t l0 = perm(t[1], t[0], y.s0), h0 = perm(t[1], t[0], y.s3);
+    const uint32_t l1 = perm(t[5], t[4], y.s1), h1 = perm(t[5], t[4], y.s4);
+    const uint32_t l2 = perm(t[16], t[16], y.s2), h2 = perm(t[16], t[16], y.s5);
+    xL = xor3(xL, l0, l1) ^ l2;
+    xH = xor3(xH, h0, h1) ^ h2;
+}
+RS16_HD void mul_xor_tower_narrow(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const uint32_t* t) {
+    mul_xor_tower_narrow_sel(xL, xH, mul_selectors(yL, yH), t);
+}
+
 // Ones'-complement add/sub on logs (reference add_mod/sub_mod,
 // src/engine.rs:90-100), in 32-bit arithmetic.
 RS16_HD uint32_t add_mod(uint32_t x, uint32_t y) {

@@ -16,6 +16,13 @@ struct HostTables {
     std::vector<uint32_t> skew_entry;  // GF_ORDER entries: mul-table entry of each twiddle
     std::vector<uint32_t> mul_tab;     // TAB_ENTRIES * TAB_DWORDS
     std::vector<uint32_t> skew_tab;    // GF_ORDER * TAB_DWORDS: mul_tab row of skew_entry[i]
+    // Tower form of the work rows: v_{8+i} = tower_a[i]
+    // + v_i v_8; tower_b, the pools by which a pass applies (lo, hi) -> (lo ^
+    // B(hi), hi) (tower_conv, rs16_gf.hpp); skew_tab_tower, skew_tab with
+    // every twiddle's map in tower coordinates.  All derived from the basis.
+    uint8_t tower_a[8] = {};
+    uint32_t tower_b[5] = {};
+    std::vector<uint32_t> skew_tab_tower;
     // Column codec (rs16_col.hip): the 2^L - 1 twiddle tables (20 dwords
     // each, tile-group order) of a 2^L-row transform at skew delta d 2^L,
     // contiguous, for L = COL_LMIN .. COL_LGEN and d < col_img_count(L);
@@ -367,6 +374,7 @@ enum DiagFlags : int {
     DIAG_WIDE_TWIDDLES = 2048, // the 12-lookup multiply in every layer (no narrow-twiddle pass variants)
     DIAG_NO_LATE_ROWS = 4096,  // every wave-staged pass as pass_kernel (no pass_kernel_late; PassConsts::late_rows = 0)
     DIAG_NO_PAIRED_ROWS = 8192, // the work buffer's rows in the reference form in every sequence (paired_rows_sequence)
+    DIAG_NO_TOWER_ROWS = 16384, // paired rows stay in Cantor coordinates (tower_rows_sequence; the 9-lookup narrow multiply)
 };
 
 constexpr size_t RS16_ZERO_BYTES = 65536;
@@ -388,7 +396,14 @@ bool paired_rows_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint
                           uint32_t row_base_in, int diag);
 // Which sides of a launch are paired rows (PassArgs::paired), and the sides a
 // paired sequence asks of program prog (0: not one of its passes).
-enum PairedSides : uint32_t { PAIRED_IN = 1, PAIRED_OUT = 2 };
+// PAIRED_TOWER (with the sides, never alone): the paired rows are in tower
+// form -- tower_rows_sequence, the same decision for a
+// sequence that paired_rows_sequence allows, off under DIAG_NO_TOWER_ROWS.  The
+// middle pass of such a sequence is launched with the tower twiddle table in
+// PassArgs::skew_tab (HostTables::skew_tab_tower).
+enum PairedSides : uint32_t { PAIRED_IN = 1, PAIRED_OUT = 2, PAIRED_TOWER = 4 };
+bool tower_rows_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count, uint32_t seg_chunk,
+                         uint32_t row_base_in, int diag);
 inline uint32_t paired_sides_of(int prog) {
     return prog == ENC_FIRST ? PAIRED_OUT : prog == ENC_MID ? PAIRED_IN | PAIRED_OUT : prog == ENC_LAST ? PAIRED_IN : 0u;
 }

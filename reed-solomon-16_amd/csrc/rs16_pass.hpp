@@ -5,7 +5,8 @@
 // 168-247; src/rate/rate_low.rs:168-247).
 //
 // Included only by the units that instantiate pass_kernel<P, T, NV>
-// (rs16_pass_enc.hip, rs16_pass_dec.hip); launch_pass (rs16_pass_launch.hip)
+// (rs16_pass_enc.hip, rs16_pass_dec.hip; rs16_pass_tower.hip for the tower
+// flavours pass_kernel_late_tower); launch_pass (rs16_pass_launch.hip)
 // reaches the kernels through their PassKernel lookups.
 //
 // Structure of one pass
@@ -785,8 +786,13 @@ template <int NV> struct NarrowVar {
 // PRE (the late-rows kernels, LateRows): pre(L, H, q) runs before butterfly q
 // of the block's first layer -- the q-th pair of that layer, counted over its
 // groups -- and requests the rows of a later pair.
+// TW (the tower kernels, pass_kernel_late_tower): the rows are in tower form
+// where the pass keeps them so -- ENC_MID throughout, its narrow layers with
+// the 6-lookup multiply of one byte map; ENC_LAST's rows as loaded, converted
+// in its first layer (pre.tb: B's pools), the multiplicand ahead of its low
+// selectors, which it shares its high ones with.
 template <int P, int T, int NK, bool LB, int KB0, int KB1, bool FFT, bool IN_TAB2, int PRUNE, int G, class FIN = NoFin,
-          class PRE = NoPre>
+          class PRE = NoPre, bool TW = false>
 struct GroupLoop {
     static __device__ __forceinline__ void run(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR], const Thr& c,
                                                const PassArgs& a, const uint4* tab1, const uint4* tab2,
@@ -829,7 +835,25 @@ struct GroupLoop {
             for (int j = 0; j < (1 << rb); j++) {
                 const int m = (gi << (rb + 1)) + j, m2 = m + (1 << rb);
                 if constexpr (!std::is_same<PRE, NoPre>::value && s == 0) pre(L, H, (gi << rb) + j);
-                if (FFT) {
+                if constexpr (TW && P == ENC_LAST && LB && FFT && s == 0) {
+                    MulSel y = high_selectors(H[m2]);
+                    tower_conv_sel(L[m2], y, pre.tb);
+                    y = low_selectors(L[m2], y);
+                    tower_conv(L[m], H[m], pre.tb);
+                    mul_xor_sel<false>(L[m], H[m], y, cur);
+                    L[m2] ^= L[m];
+                    H[m2] ^= H[m];
+                } else if constexpr (TW && P == ENC_MID && NARROW) {
+                    if (FFT) {
+                        mul_xor_tower_narrow(L[m], H[m], L[m2], H[m2], cur);
+                        L[m2] ^= L[m];
+                        H[m2] ^= H[m];
+                    } else {
+                        L[m2] ^= L[m];
+                        H[m2] ^= H[m];
+                        mul_xor_tower_narrow(L[m], H[m], L[m2], H[m2], cur);
+                    }
+                } else if (FFT) {
                     mul_xor_t<NARROW>(L[m], H[m], L[m2], H[m2], cur);
                     L[m2] ^= L[m];
                     H[m2] ^= H[m];
@@ -858,8 +882,8 @@ struct GroupLoop {
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (S::DF && kb == 0) fin(L, H, gi << 1);  // rows 2 gi, 2 gi + 1 are final
         if constexpr (more)
-            GroupLoop<P, T, NK, LB, KB0, KB1, FFT, IN_TAB2, PRUNE, G + 1, FIN, PRE>::run(L, H, c, a, tab1, tab2, nxt,
-                                                                                          zmask, fin, pre);
+            GroupLoop<P, T, NK, LB, KB0, KB1, FFT, IN_TAB2, PRUNE, G + 1, FIN, PRE, TW>::run(L, H, c, a, tab1, tab2,
+                                                                                              nxt, zmask, fin, pre);
     }
 };
 
@@ -876,7 +900,7 @@ __device__ __forceinline__ const uint4* lds_vgpr(const uint4* p) {
 
 // Apply the layers for k-bits [KB0, KB1) held in registers of layout LB.
 template <int P, int T, int NK, bool LB, int KB0, int KB1, bool FFT, bool IN_TAB2, int PRUNE = PR_NONE,
-          class FIN = NoFin, class PRE = NoPre>
+          class FIN = NoFin, class PRE = NoPre, bool TW = false>
 __device__ __forceinline__ void layers(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR], const Thr& c,
                                        const PassArgs& a, const uint4* tab1, const uint4* tab2,
                                        uint32_t zmask = 0, const FIN& fin = FIN(), const PRE& pre = PRE()) {
@@ -887,8 +911,8 @@ __device__ __forceinline__ void layers(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[
         }
         uint32_t t0[20];
         load_table_lds(t0, group_table<T, LB, KB0, KB1, FFT, 0, IN_TAB2>(c, tab1, tab2));
-        GroupLoop<P, T, NK, LB, KB0, KB1, FFT, IN_TAB2, PRUNE, 0, FIN, PRE>::run(L, H, c, a, tab1, tab2, t0, zmask, fin,
-                                                                                 pre);
+        GroupLoop<P, T, NK, LB, KB0, KB1, FFT, IN_TAB2, PRUNE, 0, FIN, PRE, TW>::run(L, H, c, a, tab1, tab2, t0, zmask,
+                                                                                     fin, pre);
     }
 }
 
@@ -1624,6 +1648,57 @@ __device__ __forceinline__ void ifft_b_halves(uint32_t (&L)[Geo<T>::NR], uint32_
     load_table_lds(t0, tab1 + ((1 << T) - (1 << (T - kb)) + gi) * 5);
     HalfLoop<T, 0, FIN>::run(L, H, tab1, t0, fin);
 }
+// The tower kernels' form of the same block (ENC_FIRST writing Z in tower
+// form): in each half's last layer (kb = T - 1, which every row passes once)
+// both rows of a butterfly are final and are converted there -- the
+// multiplicand from the high selectors its multiply extracted, the product's
+// row from its own.  (A loop of its own: HalfLoop stays the code it was.)
+template <int T, int G, class FIN> struct HalfLoopTower {
+    static __device__ __forceinline__ void run(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR],
+                                               const uint4* tab1, const uint32_t (&cur)[20], const FIN& fin,
+                                               const TowerB& tb) {
+        using S = HalfSeq<T>;
+        constexpr int e = S::at(G), half = e >> 8, kb = (e >> 4) & 15, gi = e & 15, rb = kb - S::SH;
+        constexpr bool more = G + 1 < S::total();
+        uint32_t nxt[20];
+        if constexpr (more) {
+            constexpr int kb2 = (S::at(G + 1) >> 4) & 15, gi2 = S::at(G + 1) & 15;
+            load_table_lds(nxt, tab1 + ((1 << T) - (1 << (T - kb2)) + gi2) * 5);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < (1 << rb); j++) {
+            if (rb > 0 && (j & 1) != half) continue;
+            const int m = (gi << (rb + 1)) + j, m2 = m + (1 << rb);
+            L[m2] ^= L[m];
+            H[m2] ^= H[m];
+            if constexpr (kb == T - 1) {
+                const MulSel y = mul_selectors(L[m2], H[m2]);
+                mul_xor_sel<false>(L[m], H[m], y, cur);
+                tower_conv_sel(L[m2], y, tb);
+                tower_conv(L[m], H[m], tb);
+            } else {
+                mul_xor(L[m], H[m], L[m2], H[m2], cur);
+            }
+            asm volatile("" : "+v"(L[m]), "+v"(H[m]), "+v"(L[m2]), "+v"(H[m2]));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (more) {
+            if constexpr (half == 0 && (S::at(G + 1) >> 8) == 1) fin(L, H);  // the even rows are final
+            HalfLoopTower<T, G + 1, FIN>::run(L, H, tab1, nxt, fin, tb);
+        }
+    }
+};
+template <int T, class FIN>
+__device__ __forceinline__ void ifft_b_halves_tower(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR],
+                                                    const uint4* tab1, const FIN& fin, const TowerB& tb) {
+    static_assert(HalfSeq<T>::SH < Geo<T>::R, "every row's last layer is kb = T - 1, in its own half");
+    constexpr int e = HalfSeq<T>::at(0), kb = (e >> 4) & 15, gi = e & 15;
+    tab1 = lds_vgpr(tab1);
+    uint32_t t0[20];
+    load_table_lds(t0, tab1 + ((1 << T) - (1 << (T - kb)) + gi) * 5);
+    HalfLoopTower<T, 0, FIN>::run(L, H, tab1, t0, fin, tb);
+}
 // fin of ifft_b_halves: the even rows
 template <int P, int T, bool PAIR = false> struct EvenStore {
     const PassArgs& a;
@@ -1646,8 +1721,10 @@ template <int P, int T, bool PAIR = false> struct EvenStore {
 // Compute and store one item whose rows are in d (every thread of the
 // workgroup calls it for the same item).
 // (PRE: the late-rows kernels' requests inside the first layer block, LateRows;
-// PAIR_OUT: the stores write paired rows, FastStore)
-template <int P, int T, int NV, class PRE = NoPre, bool PAIR_OUT = false>
+// PAIR_OUT: the stores write paired rows, FastStore; TOWER: Z's rows are in
+// tower form -- ENC_FIRST converts its rows in its last layer, ENC_MID works in
+// that form, ENC_LAST converts in its first layer; pre.tb holds B's pools)
+template <int P, int T, int NV, class PRE = NoPre, bool PAIR_OUT = false, bool TOWER = false>
 __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, uint32_t tile, ItemRegs<P, T>& d,
                                              uint8_t* smem, const PRE& pre = PRE()) {
     using PT = ProgTraits<P>;
@@ -1733,7 +1810,8 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
         if constexpr (ZERO_SKIP) skip_a = __all(d.zrow == (1u << NR) - 1);
         if constexpr (WaveStaged<P, T>::value) RS16_STAMP_ROWS(a, 6, L, H, 0, 1);
         if constexpr (!std::is_same<PRE, NoPre>::value)
-            layers<P, T, NKI, false, 0, R, false, false, PR_NONE, NoFin, PRE>(L, H, c, a, tab1, tab2, 0, NoFin(), pre);
+            layers<P, T, NKI, false, 0, R, false, false, PR_NONE, NoFin, PRE, TOWER>(L, H, c, a, tab1, tab2, 0, NoFin(),
+                                                                                     pre);
         else if (!skip_a) layers<P, T, NKI, false, 0, R, false, false>(L, H, c, a, tab1, tab2);
         RS16_STAMP(a, 3);
         prio<1>();
@@ -1765,7 +1843,14 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
             if constexpr (EARLY_B) {
                 Thr cs = c;
                 asm volatile("" : "+v"(cs.offL));
-                ifft_b_halves<T>(L, H, tab1, EvenStore<P, T, PAIR_OUT>{a, cs, FastStore<P, T, PAIR_OUT>(a, cs)});
+                if constexpr (TOWER)
+                    ifft_b_halves_tower<T>(L, H, tab1, EvenStore<P, T, PAIR_OUT>{a, cs, FastStore<P, T, PAIR_OUT>(a, cs)},
+                                           pre.tb);
+                else
+                    ifft_b_halves<T>(L, H, tab1, EvenStore<P, T, PAIR_OUT>{a, cs, FastStore<P, T, PAIR_OUT>(a, cs)});
+            } else if constexpr (TOWER) {
+                const uint4* tab1b = SM::SHARED ? (const uint4*)(smem + SM::TABB_OFF) - G::TSPLIT * 5 : tab1;
+                layers<P, T, NKI, true, R, T, false, false, PR_NONE, NoFin, NoPre, true>(L, H, c, a, tab1b, tab2);
             } else {
                 // (SHARED: the layout-B tables t >= TSPLIT sit beside the image)
                 const uint4* tab1b = SM::SHARED ? (const uint4*)(smem + SM::TABB_OFF) - G::TSPLIT * 5 : tab1;
@@ -1793,7 +1878,10 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
         if constexpr (T > 4) {
             if constexpr (WaveStaged<P, T>::value && !PT::IFFT) RS16_STAMP_ROWS(a, 6, L, H, 0, NR / 2);
             if constexpr (!std::is_same<PRE, NoPre>::value && !PT::IFFT)
-                layers<P, T, NKF, true, R, T, true, TWO, PR_NONE, NoFin, PRE>(L, H, c, a, tab1, tab2, 0, NoFin(), pre);
+                layers<P, T, NKF, true, R, T, true, TWO, PR_NONE, NoFin, PRE, TOWER>(L, H, c, a, tab1, tab2, 0, NoFin(),
+                                                                                     pre);
+            else if constexpr (TOWER)
+                layers<P, T, NKF, true, R, T, true, TWO, PR_NONE, NoFin, NoPre, true>(L, H, c, a, tab1, tab2);
             else
                 layers<P, T, NKF, true, R, (T > 4 ? T : R), true, TWO, (P == DEC_MID ? PR_OUT : PR_NONE)>(L, H, c, a, tab1,
                                                                                                       tab2);
@@ -1858,7 +1946,13 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
             need = any != 0;
         }
         // second direction's layout-A tables: restaged into tab1 (T > 4), else in tab2
-        if constexpr (EARLY) {
+        if constexpr (EARLY && TOWER) {
+            Thr cs = c;
+            asm volatile("" : "+v"(cs.offL));
+            layers<P, T, NKF, false, 0, R, true, (TWO && !(SM::RESTAGE)), PR_NONE, EarlyStore<P, T, PAIR_OUT>, NoPre,
+                   true>(L, H, c, a, tab1, tab2, 0,
+                         EarlyStore<P, T, PAIR_OUT>{a, cs, rvt, lostf, FastStore<P, T, PAIR_OUT>(a, cs)});
+        } else if constexpr (EARLY) {
             Thr cs = c;
             asm volatile("" : "+v"(cs.offL));
             layers<P, T, NKF, false, 0, R, true, (TWO && !(SM::RESTAGE))>(L, H, c, a, tab1, tab2, 0,
@@ -2153,6 +2247,73 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, 4) pass_kernel_late_paired(Pa
     rcn.count();
     RS16_STAMP(a, 2);
     process_item<P, T, NV, LateRows<P, T, PAIR_IN>, PAIR_OUT>(a, c, tile, cur, smem, rq);
+    rcn.store(a, c);
+}
+
+// The paired kernels of a sequence that keeps Z in tower form (DESIGN.md
+// section 3.1; rs16_pass_tower.hip instantiates them).  The rows' requests and
+// stores are the paired kernels'; ENC_FIRST and ENC_LAST carry B's pools (read
+// from the padding of the twiddle table's entry 0, uniform) beside their row
+// requests, ENC_MID needs none: its twiddle table is the tower one
+// (PassArgs::skew_tab, the engine's choice per launch).
+template <int P, int T, bool PAIR> struct LateRowsTower : LateRows<P, T, PAIR> {
+    TowerB tb;
+    __device__ __forceinline__ LateRowsTower(const PassArgs& a, const Thr& c) : LateRows<P, T, PAIR>(a, c) {
+        const cu32p q = (cu32p)a.skew_tab + TOWER_B_DWORD;
+#pragma unroll
+        for (int i = 0; i < 5; i++) tb.p[i] = q[i];
+    }
+};
+template <int P, int T, int NV> __global__ void __launch_bounds__(Geo<T>::THREADS, 4) pass_kernel_late_tower(PassArgs a) {
+    static_assert(P == ENC_FIRST || P == ENC_MID || P == ENC_LAST, "tower rows: the encoder's three passes");
+    constexpr bool PAIR_IN = P != ENC_FIRST, PAIR_OUT = P != ENC_LAST;
+    using G = Geo<T>;
+    using RQ = typename std::conditional<P == ENC_MID, LateRows<P, T, PAIR_IN>, LateRowsTower<P, T, PAIR_IN>>::type;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t item = blockIdx.x;
+
+    Thr c;
+    c.lane = threadIdx.x & 63;
+    c.w = uni(threadIdx.x >> 6);
+    c.qt = c.lane % G::Q;
+    c.s = c.w * G::HWS + c.lane / G::Q;
+    c.ql = c.qt % Rnd<P, T>::QL;
+    c.round = c.qt / Rnd<P, T>::QL;
+
+    uint32_t tile, slab;
+    set_item(c, a, item, G::Q, tile, slab);
+
+    bool first_stripe = true;
+    if (a.stripe_tiles) {
+        const uint32_t st = uni(fast_div(tile, a.stripe_mul, a.stripe_one));
+        first_stripe = st == 0;
+        tile -= st * a.stripe_tiles;
+        stripe_displace(a, st);
+    }
+    tile += a.tile_base;
+    c.b_low = tile & ((1u << a.lo) - 1);
+    c.b_high = tile >> a.lo;
+    RcvCount<P, T> rcn;
+    rcn.issue(a, c, slab == 0 && first_stripe);
+    RS16_STAMP(a, 0);
+    // (load-issue order by workgroup slot, as pass_kernel)
+    const uint32_t slot = (__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 16) & 15u;
+    if (slot == 0) __builtin_amdgcn_s_setprio(3);
+    else if (slot == 1) __builtin_amdgcn_s_setprio(2);
+    else if (slot == 2) __builtin_amdgcn_s_setprio(1);
+    TileStage<P, T> st;
+    st.issue(a, c);
+    ItemRegs<P, T> cur;
+    cur.zrow = cur.zmask = 0;
+    cur.ztile = false;
+    const RQ rq(a, c);
+    rq.prologue(cur.L, cur.H);
+    RS16_STAMP(a, 1);
+    prio<0>();
+    st.template finish<false>(a, c, smem);
+    rcn.count();
+    RS16_STAMP(a, 2);
+    process_item<P, T, NV, RQ, PAIR_OUT, true>(a, c, tile, cur, smem, rq);
     rcn.store(a, c);
 }
 

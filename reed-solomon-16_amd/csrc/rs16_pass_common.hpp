@@ -32,6 +32,10 @@ struct PassKernel {
     // rows in the paired form, ENC_MID reads and writes them, ENC_LAST reads
     // them.  Only the kernels a paired sequence can launch exist.
     PassFn paired = nullptr;
+    // The paired flavour that keeps the work buffer's rows in tower form
+    // (pass_kernel_late_tower, rs16_pass_tower.hip; nullptr: none).  Filled in
+    // by launch_pass's kernel table: the tower kernels are a unit of their own.
+    PassFn tower = nullptr;
 };
 // The launch constants that decide a launch's address forms (the PassArgs
 // fields of the same names), as launch_pass sets them from the kernel's
@@ -56,6 +60,7 @@ constexpr int NARROW_VARIANTS = 4;
 // file; prog in [0, NUM_PROGS), T in [0, 8], nv in [0, NARROW_VARIANTS).
 PassKernel pass_kernels_enc(int prog, int T, int nv);  // rs16_pass_enc.hip: GEN_*, ENC_*
 PassKernel pass_kernels_dec(int prog, int T, int nv);  // rs16_pass_dec.hip: DEC_*
+PassFn pass_kernels_tower(int prog, int T, int nv);    // rs16_pass_tower.hip: the tower flavours (nullptr: none)
 
 #if defined(__HIPCC__) || defined(__HIP__)
 // ---------------------------------------------------------------------------

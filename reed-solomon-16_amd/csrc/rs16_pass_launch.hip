@@ -18,6 +18,7 @@ struct KernelTable {
                 for (int nv = 0; nv < NARROW_VARIANTS; nv++) {
                     const PassKernel e = pass_kernels_enc(prog, T, nv);
                     k[prog][T][nv] = e.fn ? e : pass_kernels_dec(prog, T, nv);
+                    if (k[prog][T][nv].paired) k[prog][T][nv].tower = pass_kernels_tower(prog, T, nv);
                 }
     }
 };
@@ -124,6 +125,19 @@ bool paired_rows_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint
     return true;
 }
 
+// Tower form goes with the paired form: the same gate, the diagnostic switch,
+// and a tower flavour of each of the three kernels (every narrow variant of
+// the middle pass has one where the 12-lookup kernel has).
+bool tower_rows_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count, uint32_t seg_chunk,
+                         uint32_t row_base_in, int diag) {
+    if (diag & DIAG_NO_TOWER_ROWS) return false;
+    if (!paired_rows_sequence(chunk_rows, S, S_user, a_count, seg_chunk, row_base_in, diag)) return false;
+    int L = 0;
+    while (((uint32_t)1 << L) < chunk_rows) L++;
+    const int lo = L / 2, hi = L - lo;
+    return find_kernel(ENC_FIRST, lo, 0).tower && find_kernel(ENC_MID, hi, 0).tower && find_kernel(ENC_LAST, lo, 0).tower;
+}
+
 hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles, hipStream_t s) {
     if (prog < 0 || prog >= NUM_PROGS || T < 0 || T > 8) return hipErrorInvalidValue;
     if (num_tiles == 0 || args.qrow == 0) return hipSuccess;
@@ -155,9 +169,11 @@ hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles
         // Paired rows are the sequence's choice (paired_rows_sequence): a
         // launch that cannot keep it is an error, never the other form --
         // its neighbour pass would read or write the rows the other way.
-        if (a.paired != paired_sides_of(prog) || !k.paired || !pc.late_rows || !pc.full_lanes)
+        const bool tower = (a.paired & PAIRED_TOWER) != 0;
+        if ((a.paired & ~(uint32_t)PAIRED_TOWER) != paired_sides_of(prog) || !k.paired || !pc.late_rows ||
+            !pc.full_lanes || (tower && !k.tower))
             return hipErrorInvalidValue;
-        fn = k.paired;
+        fn = tower ? k.tower : k.paired;
     }
     if (lds > 65536) {
         // (per kernel variant: each is a function of its own)

@@ -29,6 +29,14 @@ inline uint16_t gf_mul(const HostTables& t, uint16_t x, uint32_t log_m) {
     return x == 0 ? 0 : t.exp[add_mod(t.log[x], log_m)];
 }
 
+// (lo, hi) -> (lo ^ B(hi), hi): Cantor coordinates <-> tower form, its own inverse
+inline uint16_t tower_conv(const HostTables& t, uint16_t x) {
+    uint16_t r = x;
+    for (int i = 0; i < 8; i++)
+        if ((x >> (8 + i)) & 1) r ^= t.tower_a[i];
+    return r;
+}
+
 void fwht_full(std::vector<uint16_t>& v) {
     for (uint32_t d = 1; d < GF_ORDER; d <<= 1)
         for (uint32_t r = 0; r < GF_ORDER; r += 2 * d)
@@ -140,6 +148,62 @@ void build(HostTables& t) {
             abort();
         }
     }
+
+    // Tower form.  With beta = v_8 the high byte's
+    // basis vectors are v_{8+i} = a_i + v_i beta with a_i in the subfield
+    // span(v_0 .. v_7), so an element (lo, hi) is a + b beta with b = hi and a
+    // = lo ^ B(hi), B the 8 x 8 bit matrix with columns a_i.  The a_i are
+    // derived here; a basis without that form cannot take the tower form.
+    for (uint32_t i = 0; i < 8; i++) {
+        const uint16_t a = (uint16_t)((1u << (8 + i)) ^ gf_mul(t, (uint16_t)(1u << i), t.log[1u << 8]));
+        if (a >= 256) {
+            fprintf(stderr, "rs16: basis vector v_%u is not a_i + v_i v_8 with a_i in the subfield\n", 8 + i);
+            abort();
+        }
+        t.tower_a[i] = (uint8_t)a;
+    }
+    // B's lookup pools, by the three selector groups of a high byte (bits
+    // 0-2, 3-5, 6-7) as a multiply table holds them: 2 + 2 + 1 dwords.
+    for (uint32_t v = 0; v < 8; v++) {
+        t.tower_b[v >> 2] |= (tower_conv(t, (uint16_t)(v << 8)) & 0xFFu) << (8 * (v & 3));
+        t.tower_b[2 + (v >> 2)] |= (tower_conv(t, (uint16_t)(v << 11)) & 0xFFu) << (8 * (v & 3));
+        if (v < 4) t.tower_b[4] |= (tower_conv(t, (uint16_t)(v << 14)) & 0xFFu) << (8 * v);
+    }
+    // The twiddle tables in tower coordinates: conv . M_c . conv for every
+    // skew index, in the layout of skew_tab.  The middle passes of a tower
+    // sequence stage these; a subfield twiddle's table must then map both
+    // bytes by one byte map and cross nothing between them -- checked here,
+    // once, as the narrow rule above.
+    t.skew_tab_tower.assign((size_t)GF_ORDER * TAB_DWORDS, 0);
+    for (uint32_t i = 0; i < GF_MODULUS; i++) {
+        const uint32_t lm = t.skew_entry[i];
+        if (lm == ZERO_ENTRY) continue;
+        uint32_t* e = &t.skew_tab_tower[(size_t)i * TAB_DWORDS];
+        auto prod = [&](uint32_t x) { return tower_conv(t, gf_mul(t, tower_conv(t, (uint16_t)x), lm)); };
+        for (int g = 0; g < 4; g++)
+            for (uint32_t v = 0; v < 8; v++) {
+                const uint16_t p = prod(v << kOff3[g]);
+                for (int ob = 0; ob < 2; ob++) e[(g * 2 + ob) * 2 + (v >> 2)] |= ((p >> (8 * ob)) & 0xFFu) << (8 * (v & 3));
+            }
+        for (int gg = 0; gg < 2; gg++)
+            for (uint32_t v = 0; v < 4; v++) {
+                const uint16_t p = prod(v << kOff2[gg]);
+                for (int ob = 0; ob < 2; ob++) e[16 + gg * 2 + ob] |= ((p >> (8 * ob)) & 0xFFu) << (8 * v);
+            }
+        if (!twiddle_narrow(i)) continue;
+        const bool cross = (e[2] | e[3] | e[6] | e[7] | e[17] | e[8] | e[9] | e[12] | e[13] | e[18]) != 0;
+        const bool same = e[10] == e[0] && e[11] == e[1] && e[14] == e[4] && e[15] == e[5] && e[19] == e[16];
+        if (cross || !same) {
+            fprintf(stderr, "rs16: tower table of subfield twiddle %u %s\n", i,
+                    cross ? "crosses between the bytes" : "maps the two bytes differently");
+            abort();
+        }
+    }
+    // The conversion's pools ride in the padding of entry 0 of both twiddle
+    // tables (dwords TOWER_B_DWORD ..): the T = 7 passes of a tower sequence
+    // read them from the table they stage their twiddles from.
+    std::copy_n(t.tower_b, 5, &t.skew_tab[TOWER_B_DWORD]);
+    std::copy_n(t.tower_b, 5, &t.skew_tab_tower[TOWER_B_DWORD]);
 
     // Column codec images: table g of layer kb (g = 2^L - 2^(L-kb) + j, group
     // j covering rows [j 2^(kb+1), (j+1) 2^(kb+1))) is the twiddle of skew

@@ -29,7 +29,7 @@ __all__ = [
     "supports", "validate", "use_high_rate", "encode_device_batch", "decode_device_batch", "encoder_work_count", "decoder_work_count",
     "RATE_DEFAULT", "RATE_HIGH", "RATE_LOW", "GF_ORDER", "GF_MODULUS", "set_diagnostics",
     "DIAG_FORCE_VOFF64", "DIAG_EVAL_TWO_KERNEL", "DIAG_EVAL_FULL", "DIAG_NO_COLUMN", "DIAG_FORCE_COLUMN",
-    "DIAG_TILE_LAST", "DIAG_NO_TILE_LAST", "DIAG_FD_LDS", "DIAG_COL_RADIX4", "DIAG_NO_IDENTITY", "DIAG_NO_MID_DIRECT", "DIAG_WIDE_TWIDDLES", "DIAG_NO_LATE_ROWS", "DIAG_NO_PAIRED_ROWS", "encode_host", "decode_host",
+    "DIAG_TILE_LAST", "DIAG_NO_TILE_LAST", "DIAG_FD_LDS", "DIAG_COL_RADIX4", "DIAG_NO_IDENTITY", "DIAG_NO_MID_DIRECT", "DIAG_WIDE_TWIDDLES", "DIAG_NO_LATE_ROWS", "DIAG_NO_PAIRED_ROWS", "DIAG_NO_TOWER_ROWS", "encode_host", "decode_host",
     "encode_host_batch", "decode_host_batch", "decode_prepare", "decode_device_prepared",
     "UpdatePlan", "update_recovery_device", "UPDATE_MAX_SHARDS",
     "encode_host_multi", "decode_host_multi", "Comm", "column_slice", "scatter_columns", "gather_columns",
@@ -44,6 +44,7 @@ DIAG_NO_MID_DIRECT = 1024
 DIAG_WIDE_TWIDDLES = 2048
 DIAG_NO_LATE_ROWS = 4096
 DIAG_NO_PAIRED_ROWS = 8192
+DIAG_NO_TOWER_ROWS = 16384
 # Test convenience only: the flags set_diagnostics() without an engine gave
 # every live engine, and that engines created later in this Python process
 # start with.  The library itself keeps the switches per engine.

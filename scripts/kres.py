@@ -7,10 +7,10 @@ tmin = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 OCC = r"Occupancy \[waves/SIMD\]"
 for p in re.split(r"remark: Function Name: ", txt)[1:]:
     name = p.split()[0]
-    m = re.match(r"_ZN4rs16\d+pass_kernel(_late(?:_paired)?)?ILi(\d+)ELi(\d+)ELi(\d+)E(?:Lb([01])ELb([01])E)?", name)
+    m = re.match(r"_ZN4rs16\d+pass_kernel(_late(?:_paired|_tower)?)?ILi(\d+)ELi(\d+)ELi(\d+)E(?:Lb([01])ELb([01])E)?", name)
     if not m or int(m.group(3)) < tmin:
         continue
-    late = " late" if m.group(1) else ""
+    late = {None: "", "_late": " late", "_late_paired": " late", "_late_tower": " late tower"}[m.group(1)]
     if m.group(5):  # the paired-rows flavours: which sides are paired
         late += " paired " + "+".join(s for s, on in (("in", m.group(5)), ("out", m.group(6))) if on == "1")
 

@@ -3,9 +3,10 @@
 the wave-staged pass kernels (rs16_pass.hpp WaveStaged)?
 
     scripts/staging_waits.py rs16_pass_enc.s
+    scripts/staging_waits.py rs16_pass_tower.s
 
-The .s is the device assembly of rs16_pass_enc.hip (the Makefile's flags plus
-`--cuda-device-only -S`).  The speed of those kernels rests on the compiler's
+The .s is the device assembly of rs16_pass_enc.hip or rs16_pass_tower.hip (the
+Makefile's flags plus `--cuda-device-only -S`).  The speed of those kernels rests on the compiler's
 wait insertion: the tables must be written with every row load still in
 flight (vmcnt >= 2 x 16 rows) and the first butterfly must wait for its own
 rows only (vmcnt 28: rows 0, 1; ENC_LAST 14: rows 0, 8).  A control-flow shape
@@ -35,6 +36,12 @@ request a row with one global_load_dwordx2: 2 D requests in the prologue and
 exactly 2 min(D, 7 - g) in flight at butterfly g; the rest as above.  (The
 flavour of the gathering first pass reads the caller's rows with dword loads
 and is checked as the unpaired kernel is.)
+
+The tower flavours (pass_kernel_late_tower, rs16_pass_tower.s) are checked as
+the paired flavours of the same programs are: the first pass reads the
+caller's rows, the middle and last passes paired rows.  In the last pass the
+first v_perm_b32 of butterfly g is the conversion of its rows out of tower
+form, which waits for the same pair.
 """
 import re
 import sys
@@ -42,6 +49,7 @@ import sys
 KERNEL = re.compile(r"^_ZN4rs1611pass_kernelILi([234])ELi([78])ELi(\d)EEEvNS_8PassArgsE:")
 LATE = re.compile(r"^_ZN4rs1616pass_kernel_lateILi([234])ELi([78])ELi(\d)EEEvNS_8PassArgsE:")
 PAIRED = re.compile(r"^_ZN4rs1623pass_kernel_late_pairedILi([234])ELi([78])ELi(\d)ELb([01])ELb([01])EEEvNS_8PassArgsE:")
+TOWER = re.compile(r"^_ZN4rs1622pass_kernel_late_towerILi([234])ELi([78])ELi(\d)EEEvNS_8PassArgsE:")
 NAMES = {"2": "ENC_FIRST", "3": "ENC_MID", "4": "ENC_LAST"}
 VM = re.compile(r"s_waitcnt.*vmcnt\((\d+)\)")
 ROW_LOAD = re.compile(r"^global_load_dword\s")
@@ -119,6 +127,14 @@ def main():
             name = "late_paired<%s,%s,%s,in %s,out %s>" % (NAMES[m.group(1)], m.group(2), m.group(3), m.group(4),
                                                           m.group(5))
             if m.group(4) == "1":
+                ok, i = late_kernel(lines, i, name, ROW_LOAD2, 2)
+            else:
+                ok, i = late_kernel(lines, i, name)
+            bad += not ok
+        m = TOWER.match(lines[i]) if i < len(lines) else None
+        if m:
+            name = "late_tower<%s,%s,%s>" % (NAMES[m.group(1)], m.group(2), m.group(3))
+            if m.group(1) != "2":
                 ok, i = late_kernel(lines, i, name, ROW_LOAD2, 2)
             else:
                 ok, i = late_kernel(lines, i, name)
