@@ -152,12 +152,12 @@ extern "C" int rs16_host_pass_consts(int prog, int T, uint32_t lo, uint64_t s_in
 extern "C" int rs16_host_paired_rows(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count,
                                      uint32_t seg_chunk, uint32_t row_base_in, int diag) {
     // (the function encode_high_fused and decode_passes call)
-    return paired_rows_sequence(chunk_rows, S, S_user, a_count, seg_chunk, row_base_in, diag) ? 1 : 0;
+    return z_form_sequence(chunk_rows, S, S_user, a_count, seg_chunk, row_base_in, diag) >= Z_PAIRED ? 1 : 0;
 }
 extern "C" int rs16_host_tower_rows(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count,
                                     uint32_t seg_chunk, uint32_t row_base_in, int diag) {
     // (the function encode_high_fused and decode_passes call)
-    return tower_rows_sequence(chunk_rows, S, S_user, a_count, seg_chunk, row_base_in, diag) ? 1 : 0;
+    return z_form_sequence(chunk_rows, S, S_user, a_count, seg_chunk, row_base_in, diag) == Z_TOWER ? 1 : 0;
 }
 extern "C" uint32_t rs16_host_tower_basis(uint32_t i) { return i < 8 ? host_tables().tower_a[i] : ~0u; }
 extern "C" void rs16_host_tower_conv(const void* in, void* out, size_t bytes) {

@@ -94,10 +94,7 @@ static PassArgs base_args(const rs16_engine* e, size_t S) {
     a.S_in = a.S_out = a.S_seg = a.S_rest = S;
     a.qrow = (uint32_t)(S / 8);
     a.diag = (uint32_t)e->diag;
-    // the work buffer's rows in the reference form: only the two sequences
-    // that ask paired_rows_sequence (encode_high_fused, the identity decode)
-    // set anything else, for their own three launches
-    a.paired = 0;
+    a.z_form = Z_SHARD;  // (only the sequences that ask z_form_sequence set another form: z_form_args)
     return a;
 }
 
@@ -309,6 +306,13 @@ int rs16_engine::col_multi(size_t k, size_t m, size_t S, size_t S_user, const ui
     return profiled(PROF_COL_ENC, s, err, [&](uint64_t*) { return launch_col_multi(c, high, s); });
 }
 
+// A launch of program prog in a sequence that keeps the work buffer in form f:
+// the form, and its twiddle table (a tower middle pass: in tower coordinates).
+void rs16_engine::z_form_args(PassArgs& a, int prog, ZForm f) const {
+    a.z_form = f;
+    a.skew_tab = prog == ENC_MID && f == Z_TOWER ? d_skew_tab_tower : d_skew_tab;
+}
+
 // Engine::fft over 2^L rows: L <= 8 in one pass; otherwise the high
 // (L - L/2) row bits as a strided pass, then the low L/2 bits contiguous.
 int rs16_engine::fft(uint8_t* data, size_t S, size_t pos, size_t size, size_t skew_delta, hipStream_t s,
@@ -322,7 +326,7 @@ int rs16_engine::fft(uint8_t* data, size_t S, size_t pos, size_t size, size_t sk
         RS16_PASS(GEN_FFT, L, a, 1, s);
         return RS16_OK;
     }
-    const int lo = L / 2, hi = L - lo;
+    const int lo = row_split(L).lo, hi = row_split(L).hi;
     a.lo = lo;
     RS16_PASS(GEN_FFT, hi, a, 1u << lo, s);
     a.lo = 0;
@@ -341,7 +345,7 @@ int rs16_engine::ifft(uint8_t* data, size_t S, size_t pos, size_t size, size_t s
         RS16_PASS(GEN_IFFT, L, a, 1, s);
         return RS16_OK;
     }
-    const int lo = L / 2, hi = L - lo;
+    const int lo = row_split(L).lo, hi = row_split(L).hi;
     a.lo = 0;
     RS16_PASS(GEN_IFFT, lo, a, 1u << hi, s);
     a.lo = lo;
@@ -397,30 +401,23 @@ int rs16_engine::encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, 
         RS16_PASS(ENC_SINGLE, L, a, batch(1, 0, bs_rec, bs_orig), s);
         return RS16_OK;
     }
-    // odd L: the extra row bit goes to the strided two-direction pass (an
-    // 8 / 7 / 8 split measured 2-3 us slower per encode, CHANGELOG.md round 3)
-    const int lo = L / 2, hi = L - lo;
+    const int lo = row_split(L).lo, hi = row_split(L).hi;
     const size_t zs = chunk * S;
-    // Z in the paired row form between the three passes, or not at all
-    // (and, with it, in tower form: the middle pass on the tower twiddle table)
-    const bool paired = paired_rows_sequence((uint32_t)chunk, S, S_user, a.a_count, a.chunk, a.row_base_in, diag);
-    const uint32_t tower =
-        tower_rows_sequence((uint32_t)chunk, S, S_user, a.a_count, a.chunk, a.row_base_in, diag) ? PAIRED_TOWER : 0;
+    // the form of Z between the three passes, one decision for all of them
+    const ZForm zf = z_form_sequence((uint32_t)chunk, S, S_user, a.a_count, a.chunk, a.row_base_in, diag);
     a.out = Z;
     a.lo = 0;
-    a.paired = paired ? paired_sides_of(ENC_FIRST) | tower : 0;
+    z_form_args(a, ENC_FIRST, zf);
     RS16_PASS(ENC_FIRST, lo, a, batch(1u << hi, 0, zs, bs_orig), s);
     a.in = Z;
     a.lo = lo;
-    a.paired = paired ? paired_sides_of(ENC_MID) | tower : 0;
-    if (tower) a.skew_tab = d_skew_tab_tower;
+    z_form_args(a, ENC_MID, zf);
     RS16_PASS(ENC_MID, hi, a, batch(1u << lo, zs, zs, 0), s);
-    a.skew_tab = d_skew_tab;
     a.in = Z;
     a.out = d_rec;
     a.S_out = S_user;
     a.lo = 0;
-    a.paired = paired ? paired_sides_of(ENC_LAST) | tower : 0;
+    z_form_args(a, ENC_LAST, zf);
     const uint32_t tiles = (uint32_t)((m + ((size_t)1 << lo) - 1) >> lo);
     RS16_PASS(ENC_LAST, lo, a, batch(tiles, zs, bs_rec, 0), s);
     return RS16_OK;
@@ -656,7 +653,7 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
             // as it is -> IFFT -> FFT -> its rows are the restored originals,
             // i.e. the encoder's three passes with the half's twiddles; the
             // first and last count the received flags for rs16_decode_check
-            const int lo = Lh / 2, hi = Lh - lo;
+            const int lo = row_split(Lh).lo, hi = row_split(Lh).hi;
             a.seg_a = g.high ? seg_a : seg_b;
             a.bs_seg = g.high ? bs_a : bs_b;
             a.a_count = half;
@@ -664,26 +661,22 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
             a.cnt_flags = g.high ? flags_a : flags_b;
             a.cnt_base = src;
             a.cnt_seg = g.high ? 0 : 1;
-            // (Z in the paired row form between these three passes, as in the encode)
-            const bool paired = paired_rows_sequence(half, S, S_user, a.a_count, a.chunk, a.row_base_in, diag);
-            const uint32_t tower =
-                tower_rows_sequence(half, S, S_user, a.a_count, a.chunk, a.row_base_in, diag) ? PAIRED_TOWER : 0;
+            // (the form of Z between these three passes, as in the encode)
+            const ZForm zf = z_form_sequence(half, S, S_user, a.a_count, a.chunk, a.row_base_in, diag);
             a.lo = 0;
             a.out = Z;
-            a.paired = paired ? paired_sides_of(ENC_FIRST) | tower : 0;
+            z_form_args(a, ENC_FIRST, zf);
             RS16_PASS_AS(PROF_DEC_HALF_FIRST, ENC_FIRST, lo, a, batch(1u << hi, 0, 0, zs), s);
             a.rcount = nullptr;
             a.lo = lo;
             a.in = Z;
-            a.paired = paired ? paired_sides_of(ENC_MID) | tower : 0;
-            if (tower) a.skew_tab = d_skew_tab_tower;
+            z_form_args(a, ENC_MID, zf);
             RS16_PASS_AS(PROF_DEC_HALF_MID, ENC_MID, hi, a, batch(1u << lo, zs, 0, zs), s);
-            a.skew_tab = d_skew_tab;
             a.lo = 0;
             a.out = rest;
             a.S_out = S_user;
             a.out_rows = orig;
-            a.paired = paired ? paired_sides_of(ENC_LAST) | tower : 0;
+            z_form_args(a, ENC_LAST, zf);
             a.rcount = rcount;
             a.cnt_flags = g.high ? flags_b : flags_a;
             a.cnt_base = dst;
@@ -730,9 +723,8 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
             c.elog = (const uint32_t*)evset->work32.p;  // (eval_poly without its last H_lo: elog_fused)
             return col(c, Lh, COL_DEC_EWORK, s, err);
         }
-        const int lo = Lh / 2, hi = Lh - lo;
-        // (unpaired: this ENC_MID reads the rows a decoder pass wrote)
-        a.paired = 0;
+        const int lo = row_split(Lh).lo, hi = row_split(Lh).hi;
+        // (form 0 throughout: this ENC_MID reads the rows a decoder pass wrote)
         a.lo = 0;
         a.out = Z;
         RS16_PASS_AS(PROF_DEC_HALF_FIRST, DEC_FIRST, lo, a, batch(1u << hi, 0, 0, zs), s);

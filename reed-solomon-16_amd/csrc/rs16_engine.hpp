@@ -221,6 +221,8 @@ struct rs16_engine {
     int prof_collect(rs16_error* err);
 
     // Engine ops on device shard arrays (validated by the C ABI layer).
+    // the form field and twiddle table of one launch of a three-pass sequence (z_form_sequence)
+    void z_form_args(rs16::PassArgs& a, int prog, rs16::ZForm f) const;
     int fft(uint8_t* data, size_t S, size_t pos, size_t size, size_t skew_delta, hipStream_t s, rs16_error* err);
     int ifft(uint8_t* data, size_t S, size_t pos, size_t size, size_t skew_delta, hipStream_t s, rs16_error* err);
 

@@ -256,14 +256,13 @@ struct PassArgs {
     uint32_t full_lanes;
     // item / nslab and tile / stripe_tiles without a division (FastDiv)
     uint32_t nslab_one, stripe_one;
-    // Paired rows, set by the engine per sequence
-    // (paired_rows_sequence): PAIRED_IN / PAIRED_OUT -- the launch reads /
-    // writes the work buffer's rows in the paired form.  Host side only:
-    // launch_pass takes the kernel flavour compiled for it, and fails where
-    // the launch does not qualify.  0: the reference form, which every
-    // sequence but the three-pass encode and the identity decode passes.
+    // The form of the work buffer's rows (ZForm) in the sequence this launch
+    // belongs to, set by the engine per sequence (rs16_engine::z_form_args).
+    // Host side only: launch_pass takes the kernel flavour compiled for the
+    // form, and fails where the launch does not qualify.  0 (Z_SHARD): every
+    // launch outside the three-pass encode and the identity decode.
     // (In what was padding: the struct's size and every offset stay.)
-    uint32_t paired;
+    uint32_t z_form;
     uint64_t nslab_mul, stripe_mul;
 };
 
@@ -373,40 +372,37 @@ enum DiagFlags : int {
     DIAG_NO_MID_DIRECT = 1024, // the general decode's middle pass always as DEC_MID (no mid_direct_kernel)
     DIAG_WIDE_TWIDDLES = 2048, // the 12-lookup multiply in every layer (no narrow-twiddle pass variants)
     DIAG_NO_LATE_ROWS = 4096,  // every wave-staged pass as pass_kernel (no pass_kernel_late; PassConsts::late_rows = 0)
-    DIAG_NO_PAIRED_ROWS = 8192, // the work buffer's rows in the reference form in every sequence (paired_rows_sequence)
-    DIAG_NO_TOWER_ROWS = 16384, // paired rows stay in Cantor coordinates (tower_rows_sequence; the 9-lookup narrow multiply)
+    DIAG_NO_PAIRED_ROWS = 8192, // the work buffer's rows in the reference form in every sequence (z_form_sequence: Z_SHARD)
+    DIAG_NO_TOWER_ROWS = 16384, // paired rows stay in Cantor coordinates (z_form_sequence: at most Z_PAIRED; the 9-lookup narrow multiply)
 };
 
 constexpr size_t RS16_ZERO_BYTES = 65536;
 
 // Launch `num_tiles` tiles (x nslab slabs) of program P with tile bits T.
 hipError_t launch_pass(int prog, int T, const PassArgs& a, uint32_t num_tiles, hipStream_t s);
-// Paired rows are a property of a sequence: the pass that writes the work
-// buffer and the pass that reads it must agree.  The one decision for the
-// three-pass sequences ENC_FIRST -> ENC_MID -> ENC_LAST over a chunk of
-// chunk_rows rows of width S (the three-pass encode and the identity decode;
-// S_user: the caller's row stride, a_count: the gather's row limit, seg_chunk /
-// row_base_in: the decode's segment boundary and first gather row, 0 in the
-// encode): paired exactly when every one of the three launches takes the
+// 2^L rows (L > 8) over two passes: lo contiguous row bits, hi strided ones.
+// Odd L: the extra bit goes to the strided pass (an 8 / 7 / 8 split measured
+// 2-3 us slower per encode, CHANGELOG.md round 3).
+struct RowSplit {
+    int lo, hi;
+};
+inline RowSplit row_split(int L) { return {L / 2, L - L / 2}; }
+// The form of the work buffer's rows between the passes of a sequence
+// ENC_FIRST -> ENC_MID -> ENC_LAST (the three-pass encode, the identity
+// decode): the shards' own; a quad's two dwords adjacent (DESIGN.md section
+// 2); or paired and in tower coordinates (section 3.1), where the middle pass
+// gets the tower twiddle table (HostTables::skew_tab_tower) as its skew_tab.
+// A property of the sequence: the pass that writes the buffer and the pass
+// that reads it must agree.
+enum ZForm : uint32_t { Z_SHARD = 0, Z_PAIRED, Z_TOWER };
+// The one decision (host arithmetic only; the parameters: include/rs16.h,
+// rs16_host_paired_rows, which with rs16_host_tower_rows shows it to tests).
+// At least Z_PAIRED exactly when each of the three launches takes the
 // late-rows kernel with full lanes (pass_launch_consts), that kernel has a
-// paired flavour (chunks of 2^14 and 2^15 rows) and DIAG_NO_PAIRED_ROWS is
-// not set.  The engine passes it down in PassArgs::paired; host arithmetic
-// only (rs16_host_paired_rows shows it to tests).
-bool paired_rows_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count, uint32_t seg_chunk,
-                          uint32_t row_base_in, int diag);
-// Which sides of a launch are paired rows (PassArgs::paired), and the sides a
-// paired sequence asks of program prog (0: not one of its passes).
-// PAIRED_TOWER (with the sides, never alone): the paired rows are in tower
-// form -- tower_rows_sequence, the same decision for a
-// sequence that paired_rows_sequence allows, off under DIAG_NO_TOWER_ROWS.  The
-// middle pass of such a sequence is launched with the tower twiddle table in
-// PassArgs::skew_tab (HostTables::skew_tab_tower).
-enum PairedSides : uint32_t { PAIRED_IN = 1, PAIRED_OUT = 2, PAIRED_TOWER = 4 };
-bool tower_rows_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count, uint32_t seg_chunk,
-                         uint32_t row_base_in, int diag);
-inline uint32_t paired_sides_of(int prog) {
-    return prog == ENC_FIRST ? PAIRED_OUT : prog == ENC_MID ? PAIRED_IN | PAIRED_OUT : prog == ENC_LAST ? PAIRED_IN : 0u;
-}
+// paired flavour (chunks of 2^14 and 2^15 rows) and DIAG_NO_PAIRED_ROWS is not
+// set; Z_TOWER when each also has a tower flavour and no DIAG_NO_TOWER_ROWS.
+ZForm z_form_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count, uint32_t seg_chunk,
+                      uint32_t row_base_in, int diag);
 // DEC_LAST at T = 8 as one wave per quad column of a tile (rs16_pass_small.hpp
 // tile_last_kernel): `num_tiles` tiles (x stripes, PassArgs::stripe_tiles),
 // rows at lo = 0, counted from the stripe's first lost tile (read from

@@ -1611,52 +1611,17 @@ template <int T> struct HalfSeq {
         return g;
     }
 };
-template <int T, int G, class FIN> struct HalfLoop {
-    static __device__ __forceinline__ void run(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR],
-                                               const uint4* tab1, const uint32_t (&cur)[20], const FIN& fin) {
-        using S = HalfSeq<T>;
-        constexpr int e = S::at(G), half = e >> 8, kb = (e >> 4) & 15, gi = e & 15, rb = kb - S::SH;
-        constexpr bool more = G + 1 < S::total();
-        uint32_t nxt[20];
-        if constexpr (more) {
-            constexpr int kb2 = (S::at(G + 1) >> 4) & 15, gi2 = S::at(G + 1) & 15;
-            load_table_lds(nxt, tab1 + ((1 << T) - (1 << (T - kb2)) + gi2) * 5);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < (1 << rb); j++) {
-            if (rb > 0 && (j & 1) != half) continue;
-            const int m = (gi << (rb + 1)) + j, m2 = m + (1 << rb);
-            L[m2] ^= L[m];
-            H[m2] ^= H[m];
-            mul_xor(L[m], H[m], L[m2], H[m2], cur);
-            asm volatile("" : "+v"(L[m]), "+v"(H[m]), "+v"(L[m2]), "+v"(H[m2]));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (more) {
-            if constexpr (half == 0 && (S::at(G + 1) >> 8) == 1) fin(L, H);  // the even rows are final
-            HalfLoop<T, G + 1, FIN>::run(L, H, tab1, nxt, fin);
-        }
-    }
-};
-template <int T, class FIN>
-__device__ __forceinline__ void ifft_b_halves(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR], const uint4* tab1,
-                                              const FIN& fin) {
-    constexpr int e = HalfSeq<T>::at(0), kb = (e >> 4) & 15, gi = e & 15;
-    tab1 = lds_vgpr(tab1);
-    uint32_t t0[20];
-    load_table_lds(t0, tab1 + ((1 << T) - (1 << (T - kb)) + gi) * 5);
-    HalfLoop<T, 0, FIN>::run(L, H, tab1, t0, fin);
-}
-// The tower kernels' form of the same block (ENC_FIRST writing Z in tower
-// form): in each half's last layer (kb = T - 1, which every row passes once)
-// both rows of a butterfly are final and are converted there -- the
+// TB = TowerB: the tower kernels' form of the block (ENC_FIRST writing Z in
+// tower form).  In each half's last layer (kb = T - 1, which every row passes
+// once) both rows of a butterfly are final and are converted there -- the
 // multiplicand from the high selectors its multiply extracted, the product's
-// row from its own.  (A loop of its own: HalfLoop stays the code it was.)
-template <int T, int G, class FIN> struct HalfLoopTower {
+// row from its own.
+struct NoTower {};
+template <int T, int G, class FIN, class TB = NoTower> struct HalfLoop {
+    static_assert(std::is_same<TB, NoTower>::value || HalfSeq<T>::SH < Geo<T>::R, "a row's last layer: kb = T - 1");
     static __device__ __forceinline__ void run(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR],
                                                const uint4* tab1, const uint32_t (&cur)[20], const FIN& fin,
-                                               const TowerB& tb) {
+                                               const TB& tb = TB()) {
         using S = HalfSeq<T>;
         constexpr int e = S::at(G), half = e >> 8, kb = (e >> 4) & 15, gi = e & 15, rb = kb - S::SH;
         constexpr bool more = G + 1 < S::total();
@@ -1672,7 +1637,7 @@ template <int T, int G, class FIN> struct HalfLoopTower {
             const int m = (gi << (rb + 1)) + j, m2 = m + (1 << rb);
             L[m2] ^= L[m];
             H[m2] ^= H[m];
-            if constexpr (kb == T - 1) {
+            if constexpr (!std::is_same<TB, NoTower>::value && kb == T - 1) {
                 const MulSel y = mul_selectors(L[m2], H[m2]);
                 mul_xor_sel<false>(L[m], H[m], y, cur);
                 tower_conv_sel(L[m2], y, tb);
@@ -1685,19 +1650,18 @@ template <int T, int G, class FIN> struct HalfLoopTower {
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (more) {
             if constexpr (half == 0 && (S::at(G + 1) >> 8) == 1) fin(L, H);  // the even rows are final
-            HalfLoopTower<T, G + 1, FIN>::run(L, H, tab1, nxt, fin, tb);
+            HalfLoop<T, G + 1, FIN, TB>::run(L, H, tab1, nxt, fin, tb);
         }
     }
 };
-template <int T, class FIN>
-__device__ __forceinline__ void ifft_b_halves_tower(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR],
-                                                    const uint4* tab1, const FIN& fin, const TowerB& tb) {
-    static_assert(HalfSeq<T>::SH < Geo<T>::R, "every row's last layer is kb = T - 1, in its own half");
+template <int T, class FIN, class TB = NoTower>
+__device__ __forceinline__ void ifft_b_halves(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR], const uint4* tab1,
+                                              const FIN& fin, const TB& tb = TB()) {
     constexpr int e = HalfSeq<T>::at(0), kb = (e >> 4) & 15, gi = e & 15;
     tab1 = lds_vgpr(tab1);
     uint32_t t0[20];
     load_table_lds(t0, tab1 + ((1 << T) - (1 << (T - kb)) + gi) * 5);
-    HalfLoopTower<T, 0, FIN>::run(L, H, tab1, t0, fin, tb);
+    HalfLoop<T, 0, FIN, TB>::run(L, H, tab1, t0, fin, tb);
 }
 // fin of ifft_b_halves: the even rows
 template <int P, int T, bool PAIR = false> struct EvenStore {
@@ -1843,18 +1807,13 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
             if constexpr (EARLY_B) {
                 Thr cs = c;
                 asm volatile("" : "+v"(cs.offL));
-                if constexpr (TOWER)
-                    ifft_b_halves_tower<T>(L, H, tab1, EvenStore<P, T, PAIR_OUT>{a, cs, FastStore<P, T, PAIR_OUT>(a, cs)},
-                                           pre.tb);
-                else
-                    ifft_b_halves<T>(L, H, tab1, EvenStore<P, T, PAIR_OUT>{a, cs, FastStore<P, T, PAIR_OUT>(a, cs)});
-            } else if constexpr (TOWER) {
-                const uint4* tab1b = SM::SHARED ? (const uint4*)(smem + SM::TABB_OFF) - G::TSPLIT * 5 : tab1;
-                layers<P, T, NKI, true, R, T, false, false, PR_NONE, NoFin, NoPre, true>(L, H, c, a, tab1b, tab2);
+                const EvenStore<P, T, PAIR_OUT> even{a, cs, FastStore<P, T, PAIR_OUT>(a, cs)};
+                if constexpr (TOWER) ifft_b_halves<T>(L, H, tab1, even, pre.tb);  // (B's pools: LateRowsTower)
+                else ifft_b_halves<T>(L, H, tab1, even);
             } else {
                 // (SHARED: the layout-B tables t >= TSPLIT sit beside the image)
                 const uint4* tab1b = SM::SHARED ? (const uint4*)(smem + SM::TABB_OFF) - G::TSPLIT * 5 : tab1;
-                layers<P, T, NKI, true, R, (T > 4 ? T : R), false, false, (ZERO_SKIP ? PR_ZERO : PR_NONE)>(
+                layers<P, T, NKI, true, R, T, false, false, (ZERO_SKIP ? PR_ZERO : PR_NONE), NoFin, NoPre, TOWER>(
                     L, H, c, a, tab1b, tab2, d.zmask);
             }
             in_b = true;
@@ -1880,11 +1839,9 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
             if constexpr (!std::is_same<PRE, NoPre>::value && !PT::IFFT)
                 layers<P, T, NKF, true, R, T, true, TWO, PR_NONE, NoFin, PRE, TOWER>(L, H, c, a, tab1, tab2, 0, NoFin(),
                                                                                      pre);
-            else if constexpr (TOWER)
-                layers<P, T, NKF, true, R, T, true, TWO, PR_NONE, NoFin, NoPre, true>(L, H, c, a, tab1, tab2);
             else
-                layers<P, T, NKF, true, R, (T > 4 ? T : R), true, TWO, (P == DEC_MID ? PR_OUT : PR_NONE)>(L, H, c, a, tab1,
-                                                                                                      tab2);
+                layers<P, T, NKF, true, R, T, true, TWO, (P == DEC_MID ? PR_OUT : PR_NONE), NoFin, NoPre, TOWER>(
+                    L, H, c, a, tab1, tab2);
             if constexpr (SPLIT_FD) {
                 // the layout-A bits' derivative terms (fd_image) join the
                 // register rows that feed consumed rows
@@ -1946,19 +1903,12 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
             need = any != 0;
         }
         // second direction's layout-A tables: restaged into tab1 (T > 4), else in tab2
-        if constexpr (EARLY && TOWER) {
+        if constexpr (EARLY) {
             Thr cs = c;
             asm volatile("" : "+v"(cs.offL));
             layers<P, T, NKF, false, 0, R, true, (TWO && !(SM::RESTAGE)), PR_NONE, EarlyStore<P, T, PAIR_OUT>, NoPre,
-                   true>(L, H, c, a, tab1, tab2, 0,
-                         EarlyStore<P, T, PAIR_OUT>{a, cs, rvt, lostf, FastStore<P, T, PAIR_OUT>(a, cs)});
-        } else if constexpr (EARLY) {
-            Thr cs = c;
-            asm volatile("" : "+v"(cs.offL));
-            layers<P, T, NKF, false, 0, R, true, (TWO && !(SM::RESTAGE))>(L, H, c, a, tab1, tab2, 0,
-                                                                        EarlyStore<P, T, PAIR_OUT>{
-                                                                            a, cs, rvt, lostf,
-                                                                            FastStore<P, T, PAIR_OUT>(a, cs)});
+                   TOWER>(L, H, c, a, tab1, tab2, 0,
+                          EarlyStore<P, T, PAIR_OUT>{a, cs, rvt, lostf, FastStore<P, T, PAIR_OUT>(a, cs)});
         } else if (need) {
             layers<P, T, NKF, false, 0, R, true, (TWO && !(SM::RESTAGE))>(L, H, c, a, tab1, tab2);
         }
@@ -2004,6 +1954,64 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
     RS16_STAMP_END(a);
 }
 
+// The four pass kernels below share their head, and the three late-rows ones
+// their body, as text: two macros expanded inside each __global__ definition.
+// Not as functions: with the late body in a __device__ __forceinline__
+// function template that the flavours call, or with more template parameters
+// on pass_kernel_late, 26 of the 86 kernels of the encoder's and the tower
+// unit compile to other machine code (scripts/isa_compare.py).  The kernels'
+// names and template parameters stay: scripts/kres.py and staging_waits.py
+// match them.
+// RS16_PASS_HEAD (`a`, `G` in scope; leaves c, tile, slab, rcn): the item of
+// this workgroup (launch_pass: one per workgroup), its thread coordinates,
+// with batched stripes the stripe's arrays and the tile within the stripe.
+#define RS16_PASS_HEAD(P, T) \
+    const uint32_t item = blockIdx.x; \
+    Thr c; \
+    c.lane = threadIdx.x & 63; \
+    c.w = uni(threadIdx.x >> 6); \
+    c.qt = c.lane % G::Q; \
+    c.s = c.w * G::HWS + c.lane / G::Q; \
+    c.ql = c.qt % Rnd<P, T>::QL; \
+    c.round = c.qt / Rnd<P, T>::QL; \
+    uint32_t tile, slab; \
+    set_item(c, a, item, G::Q, tile, slab); \
+    bool first_stripe = true; \
+    if (a.stripe_tiles) { \
+        const uint32_t st = uni(fast_div(tile, a.stripe_mul, a.stripe_one)); \
+        first_stripe = st == 0; \
+        tile -= st * a.stripe_tiles; \
+        stripe_displace(a, st); \
+    } \
+    tile += a.tile_base; \
+    c.b_low = tile & ((1u << a.lo) - 1); \
+    c.b_high = tile >> a.lo; \
+    RcvCount<P, T> rcn; \
+    rcn.issue(a, c, slab == 0 && first_stripe);
+// RS16_LATE_BODY: a late-rows kernel after its head -- load-issue order by
+// workgroup slot (as pass_kernel), table staging, the first D row pairs through
+// RQ (a LateRows type, named by a `using`: no commas), then process_item.
+#define RS16_LATE_BODY(P, T, NV, RQ, PAIR_OUT, TOWER) \
+    RS16_STAMP(a, 0); \
+    const uint32_t slot = (__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 16) & 15u; \
+    if (slot == 0) __builtin_amdgcn_s_setprio(3); \
+    else if (slot == 1) __builtin_amdgcn_s_setprio(2); \
+    else if (slot == 2) __builtin_amdgcn_s_setprio(1); \
+    TileStage<P, T> st; \
+    st.issue(a, c); \
+    ItemRegs<P, T> cur; \
+    cur.zrow = cur.zmask = 0; \
+    cur.ztile = false; \
+    const RQ rq(a, c); \
+    rq.prologue(cur.L, cur.H); \
+    RS16_STAMP(a, 1); \
+    prio<0>(); \
+    st.template finish<false>(a, c, smem); \
+    rcn.count(); \
+    RS16_STAMP(a, 2); \
+    process_item<P, T, NV, RQ, PAIR_OUT, TOWER>(a, c, tile, cur, smem, rq); \
+    rcn.store(a, c);
+
 // The pass: workgroup b processes item b of the launch (4 waves per SIMD,
 // except the one-pass decoders, whose larger register sets take 1).
 template <int P, int T, int NV = 0>
@@ -2011,32 +2019,7 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, ((P == DEC_SINGLE || P == DEC
     pass_kernel(PassArgs a) {
     using G = Geo<T>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t item = blockIdx.x;  // (launch_pass: one workgroup per item)
-
-    Thr c;
-    c.lane = threadIdx.x & 63;
-    c.w = uni(threadIdx.x >> 6);
-    c.qt = c.lane % G::Q;
-    c.s = c.w * G::HWS + c.lane / G::Q;
-    c.ql = c.qt % Rnd<P, T>::QL;
-    c.round = c.qt / Rnd<P, T>::QL;
-
-    uint32_t tile, slab;
-    set_item(c, a, item, G::Q, tile, slab);
-
-    bool first_stripe = true;
-    if (a.stripe_tiles) {
-        // batched stripes: the stripe's arrays, the tile within the stripe
-        const uint32_t st = uni(fast_div(tile, a.stripe_mul, a.stripe_one));
-        first_stripe = st == 0;
-        tile -= st * a.stripe_tiles;
-        stripe_displace(a, st);
-    }
-    tile += a.tile_base;
-    c.b_low = tile & ((1u << a.lo) - 1);
-    c.b_high = tile >> a.lo;
-    RcvCount<P, T> rcn;
-    rcn.issue(a, c, slab == 0 && first_stripe);
+    RS16_PASS_HEAD(P, T)
     if constexpr (P == DEC_FIRST) {
         // a tile without received rows is skipped (process_item): return
         // before its table staging and row loads, so its slot frees at once
@@ -2145,117 +2128,30 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, 4) pass_kernel_late(PassArgs 
     using G = Geo<T>;
     static_assert(WaveStaged<P, T>::value, "late rows: the wave-staged passes");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t item = blockIdx.x;
-
-    Thr c;
-    c.lane = threadIdx.x & 63;
-    c.w = uni(threadIdx.x >> 6);
-    c.qt = c.lane % G::Q;
-    c.s = c.w * G::HWS + c.lane / G::Q;
-    c.ql = c.qt % Rnd<P, T>::QL;
-    c.round = c.qt / Rnd<P, T>::QL;
-
-    uint32_t tile, slab;
-    set_item(c, a, item, G::Q, tile, slab);
-
-    bool first_stripe = true;
-    if (a.stripe_tiles) {
-        const uint32_t st = uni(fast_div(tile, a.stripe_mul, a.stripe_one));
-        first_stripe = st == 0;
-        tile -= st * a.stripe_tiles;
-        stripe_displace(a, st);
-    }
-    tile += a.tile_base;
-    c.b_low = tile & ((1u << a.lo) - 1);
-    c.b_high = tile >> a.lo;
-    RcvCount<P, T> rcn;
-    rcn.issue(a, c, slab == 0 && first_stripe);
-    RS16_STAMP(a, 0);
-    // (load-issue order by workgroup slot, as pass_kernel)
-    const uint32_t slot = (__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 16) & 15u;
-    if (slot == 0) __builtin_amdgcn_s_setprio(3);
-    else if (slot == 1) __builtin_amdgcn_s_setprio(2);
-    else if (slot == 2) __builtin_amdgcn_s_setprio(1);
-    TileStage<P, T> st;
-    st.issue(a, c);
-    ItemRegs<P, T> cur;
-    cur.zrow = cur.zmask = 0;
-    cur.ztile = false;
-    const LateRows<P, T> rq(a, c);
-    rq.prologue(cur.L, cur.H);
-    RS16_STAMP(a, 1);
-    prio<0>();
-    st.template finish<false>(a, c, smem);
-    rcn.count();
-    RS16_STAMP(a, 2);
-    process_item<P, T, NV, LateRows<P, T>>(a, c, tile, cur, smem, rq);
-    rcn.store(a, c);
+    RS16_PASS_HEAD(P, T)
+    using RQ = LateRows<P, T>;
+    RS16_LATE_BODY(P, T, NV, RQ, false, false)
 }
 // The same kernel reading (PAIR_IN) and / or writing (PAIR_OUT) the work
 // buffer's rows in the paired form (LateRows, FastStore) -- a compile-time
 // choice, because a guarded block at the request sites is what the late-rows
-// variant exists to avoid.  (A kernel of its own name, written out: with one
-// more template parameter, or with its body in a function shared with the
-// flavours, pass_kernel_late compiles to other machine code.)
+// variant exists to avoid.  (A kernel of its own name: see RS16_PASS_HEAD.)
 template <int P, int T, int NV, bool PAIR_IN, bool PAIR_OUT>
 __global__ void __launch_bounds__(Geo<T>::THREADS, 4) pass_kernel_late_paired(PassArgs a) {
     static_assert(PAIR_IN || PAIR_OUT, "the unpaired kernel is pass_kernel_late");
     using G = Geo<T>;
     static_assert(WaveStaged<P, T>::value, "late rows: the wave-staged passes");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t item = blockIdx.x;
-
-    Thr c;
-    c.lane = threadIdx.x & 63;
-    c.w = uni(threadIdx.x >> 6);
-    c.qt = c.lane % G::Q;
-    c.s = c.w * G::HWS + c.lane / G::Q;
-    c.ql = c.qt % Rnd<P, T>::QL;
-    c.round = c.qt / Rnd<P, T>::QL;
-
-    uint32_t tile, slab;
-    set_item(c, a, item, G::Q, tile, slab);
-
-    bool first_stripe = true;
-    if (a.stripe_tiles) {
-        const uint32_t st = uni(fast_div(tile, a.stripe_mul, a.stripe_one));
-        first_stripe = st == 0;
-        tile -= st * a.stripe_tiles;
-        stripe_displace(a, st);
-    }
-    tile += a.tile_base;
-    c.b_low = tile & ((1u << a.lo) - 1);
-    c.b_high = tile >> a.lo;
-    RcvCount<P, T> rcn;
-    rcn.issue(a, c, slab == 0 && first_stripe);
-    RS16_STAMP(a, 0);
-    // (load-issue order by workgroup slot, as pass_kernel)
-    const uint32_t slot = (__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 16) & 15u;
-    if (slot == 0) __builtin_amdgcn_s_setprio(3);
-    else if (slot == 1) __builtin_amdgcn_s_setprio(2);
-    else if (slot == 2) __builtin_amdgcn_s_setprio(1);
-    TileStage<P, T> st;
-    st.issue(a, c);
-    ItemRegs<P, T> cur;
-    cur.zrow = cur.zmask = 0;
-    cur.ztile = false;
-    const LateRows<P, T, PAIR_IN> rq(a, c);
-    rq.prologue(cur.L, cur.H);
-    RS16_STAMP(a, 1);
-    prio<0>();
-    st.template finish<false>(a, c, smem);
-    rcn.count();
-    RS16_STAMP(a, 2);
-    process_item<P, T, NV, LateRows<P, T, PAIR_IN>, PAIR_OUT>(a, c, tile, cur, smem, rq);
-    rcn.store(a, c);
+    RS16_PASS_HEAD(P, T)
+    using RQ = LateRows<P, T, PAIR_IN>;
+    RS16_LATE_BODY(P, T, NV, RQ, PAIR_OUT, false)
 }
 
 // The paired kernels of a sequence that keeps Z in tower form (DESIGN.md
-// section 3.1; rs16_pass_tower.hip instantiates them).  The rows' requests and
-// stores are the paired kernels'; ENC_FIRST and ENC_LAST carry B's pools (read
-// from the padding of the twiddle table's entry 0, uniform) beside their row
-// requests, ENC_MID needs none: its twiddle table is the tower one
-// (PassArgs::skew_tab, the engine's choice per launch).
+// section 3.1; rs16_pass_tower.hip instantiates them).  ENC_FIRST and ENC_LAST
+// carry B's pools (read from the padding of the twiddle table's entry 0,
+// uniform) beside their row requests; ENC_MID needs none: its twiddle table
+// is the tower one (PassArgs::skew_tab, the engine's choice per launch).
 template <int P, int T, bool PAIR> struct LateRowsTower : LateRows<P, T, PAIR> {
     TowerB tb;
     __device__ __forceinline__ LateRowsTower(const PassArgs& a, const Thr& c) : LateRows<P, T, PAIR>(a, c) {
@@ -2270,51 +2166,8 @@ template <int P, int T, int NV> __global__ void __launch_bounds__(Geo<T>::THREAD
     using G = Geo<T>;
     using RQ = typename std::conditional<P == ENC_MID, LateRows<P, T, PAIR_IN>, LateRowsTower<P, T, PAIR_IN>>::type;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t item = blockIdx.x;
-
-    Thr c;
-    c.lane = threadIdx.x & 63;
-    c.w = uni(threadIdx.x >> 6);
-    c.qt = c.lane % G::Q;
-    c.s = c.w * G::HWS + c.lane / G::Q;
-    c.ql = c.qt % Rnd<P, T>::QL;
-    c.round = c.qt / Rnd<P, T>::QL;
-
-    uint32_t tile, slab;
-    set_item(c, a, item, G::Q, tile, slab);
-
-    bool first_stripe = true;
-    if (a.stripe_tiles) {
-        const uint32_t st = uni(fast_div(tile, a.stripe_mul, a.stripe_one));
-        first_stripe = st == 0;
-        tile -= st * a.stripe_tiles;
-        stripe_displace(a, st);
-    }
-    tile += a.tile_base;
-    c.b_low = tile & ((1u << a.lo) - 1);
-    c.b_high = tile >> a.lo;
-    RcvCount<P, T> rcn;
-    rcn.issue(a, c, slab == 0 && first_stripe);
-    RS16_STAMP(a, 0);
-    // (load-issue order by workgroup slot, as pass_kernel)
-    const uint32_t slot = (__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 16) & 15u;
-    if (slot == 0) __builtin_amdgcn_s_setprio(3);
-    else if (slot == 1) __builtin_amdgcn_s_setprio(2);
-    else if (slot == 2) __builtin_amdgcn_s_setprio(1);
-    TileStage<P, T> st;
-    st.issue(a, c);
-    ItemRegs<P, T> cur;
-    cur.zrow = cur.zmask = 0;
-    cur.ztile = false;
-    const RQ rq(a, c);
-    rq.prologue(cur.L, cur.H);
-    RS16_STAMP(a, 1);
-    prio<0>();
-    st.template finish<false>(a, c, smem);
-    rcn.count();
-    RS16_STAMP(a, 2);
-    process_item<P, T, NV, RQ, PAIR_OUT, true>(a, c, tile, cur, smem, rq);
-    rcn.store(a, c);
+    RS16_PASS_HEAD(P, T)
+    RS16_LATE_BODY(P, T, NV, RQ, PAIR_OUT, true)
 }
 
 // ---------------------------------------------------------------------------
@@ -2335,7 +2188,7 @@ template <int P, int T, int NV = 0> PassKernel pass_entry() {
     using PT = ProgTraits<P>;
     return {pass_kernel<P, T, NV>, Smem<P, T>::BYTES, Geo<T>::THREADS, Geo<T>::Q,
             !PT::IFFT ? Geo<T>::SHB : 0, (!PT::FFT && T > 4) ? Geo<T>::SHB : 0, Geo<T>::R,
-            late_entry<P, T, NV>(), PT::LOAD == LD_GATHER_ENC ? 1 : 0};
+            PT::LOAD == LD_GATHER_ENC ? 1 : 0, {late_entry<P, T, NV>(), nullptr, nullptr}};
 }
 // the 12-lookup kernels of program P at T = 0 .. 8
 template <int P> PassKernel pass_row(int T) {

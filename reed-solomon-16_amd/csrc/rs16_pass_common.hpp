@@ -22,20 +22,16 @@ struct PassKernel {
     // registers are 1 << lo rows apart), else B (1 << (lo + SHB)): SHB
     int load_shb, store_shb;
     int reg_bits;  // Geo<T>::R, row bits held in registers (2^R rows per thread)
-    // The late-rows variant of a wave-staged pass (rs16_pass.hpp
-    // pass_kernel_late; nullptr: none), and whether the pass gathers its rows
-    // below the row limit a_count (ENC_FIRST).
-    PassFn late;
+    // Whether the pass gathers its rows below the row limit a_count (ENC_FIRST).
     int gather;
-    // The paired-rows flavour of the late-rows variant (pass_kernel_late with
-    // PAIR_IN / PAIR_OUT; nullptr: none): ENC_FIRST writes the work buffer's
-    // rows in the paired form, ENC_MID reads and writes them, ENC_LAST reads
-    // them.  Only the kernels a paired sequence can launch exist.
-    PassFn paired = nullptr;
-    // The paired flavour that keeps the work buffer's rows in tower form
-    // (pass_kernel_late_tower, rs16_pass_tower.hip; nullptr: none).  Filled in
-    // by launch_pass's kernel table: the tower kernels are a unit of their own.
-    PassFn tower = nullptr;
+    // The late-rows variants of a wave-staged pass (rs16_pass.hpp) by ZForm
+    // (nullptr: none).  Z_SHARD: pass_kernel_late.  Z_PAIRED:
+    // pass_kernel_late_paired -- ENC_FIRST writes the work buffer's rows in
+    // the paired form, ENC_MID reads and writes them, ENC_LAST reads them;
+    // only the kernels a paired sequence can launch exist.  Z_TOWER:
+    // pass_kernel_late_tower, the same in tower form.  The last two are
+    // filled in by launch_pass's kernel table, each from its own lookup.
+    PassFn late[3];
 };
 // The launch constants that decide a launch's address forms (the PassArgs
 // fields of the same names), as launch_pass sets them from the kernel's
@@ -59,6 +55,7 @@ constexpr int NARROW_VARIANTS = 4;
 // One lookup per instantiation unit, each covering the programs named in its
 // file; prog in [0, NUM_PROGS), T in [0, 8], nv in [0, NARROW_VARIANTS).
 PassKernel pass_kernels_enc(int prog, int T, int nv);  // rs16_pass_enc.hip: GEN_*, ENC_*
+PassFn pass_kernels_paired(int prog, int T, int nv);   // rs16_pass_enc.hip: the paired flavours (nullptr: none)
 PassKernel pass_kernels_dec(int prog, int T, int nv);  // rs16_pass_dec.hip: DEC_*
 PassFn pass_kernels_tower(int prog, int T, int nv);    // rs16_pass_tower.hip: the tower flavours (nullptr: none)
 

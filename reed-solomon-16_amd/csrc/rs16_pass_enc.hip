@@ -10,7 +10,7 @@ namespace rs16 {
 // The paired-rows flavours (pass_kernel_late with PAIR_IN / PAIR_OUT), only
 // for the kernels a paired sequence can launch: three late-rows passes exist
 // for chunks of 2^14 rows (T = 7 / 7 / 7) and 2^15 rows (7 / 8 / 7).
-static PassFn paired_kernel(int prog, int T, int nv) {
+PassFn pass_kernels_paired(int prog, int T, int nv) {
     if (prog == ENC_FIRST && T == 7 && nv == 0) return paired_entry<ENC_FIRST, 7>();
     if (prog == ENC_LAST && T == 7 && nv == 0) return paired_entry<ENC_LAST, 7>();
     if (prog == ENC_MID && T == 7) {
@@ -28,7 +28,7 @@ static PassFn paired_kernel(int prog, int T, int nv) {
     return nullptr;
 }
 
-static PassKernel unpaired_kernels_enc(int prog, int T, int nv) {
+PassKernel pass_kernels_enc(int prog, int T, int nv) {
     if (prog == ENC_MID) {
         switch (nv) {
             case 0: return pass_row<ENC_MID>(T);
@@ -49,12 +49,6 @@ static PassKernel unpaired_kernels_enc(int prog, int T, int nv) {
         case ENC_SINGLE: return pass_row<ENC_SINGLE>(T);
         default: return {};
     }
-}
-
-PassKernel pass_kernels_enc(int prog, int T, int nv) {
-    PassKernel k = unpaired_kernels_enc(prog, T, nv);
-    if (k.fn) k.paired = paired_kernel(prog, T, nv);
-    return k;
 }
 
 }  // namespace rs16

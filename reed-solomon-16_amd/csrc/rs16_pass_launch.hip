@@ -1,7 +1,7 @@
 // rs16_pass_launch.hip -- launch_pass: which pass kernel a launch takes and
 // how it is launched.  The kernels themselves are instantiated in
-// rs16_pass_enc.hip and rs16_pass_dec.hip (template: rs16_pass.hpp); this
-// unit sees them through the PassKernel lookups only.
+// rs16_pass_enc.hip, rs16_pass_dec.hip and rs16_pass_tower.hip (template:
+// rs16_pass.hpp); this unit sees them through the PassKernel lookups only.
 #include <algorithm>
 
 #include "rs16_pass_common.hpp"
@@ -16,9 +16,11 @@ struct KernelTable {
         for (int prog = 0; prog < NUM_PROGS; prog++)
             for (int T = 0; T <= 8; T++)
                 for (int nv = 0; nv < NARROW_VARIANTS; nv++) {
-                    const PassKernel e = pass_kernels_enc(prog, T, nv);
-                    k[prog][T][nv] = e.fn ? e : pass_kernels_dec(prog, T, nv);
-                    if (k[prog][T][nv].paired) k[prog][T][nv].tower = pass_kernels_tower(prog, T, nv);
+                    PassKernel& e = k[prog][T][nv];
+                    e = pass_kernels_enc(prog, T, nv);
+                    if (!e.fn) e = pass_kernels_dec(prog, T, nv);
+                    e.late[Z_PAIRED] = pass_kernels_paired(prog, T, nv);
+                    e.late[Z_TOWER] = pass_kernels_tower(prog, T, nv);
                 }
     }
 };
@@ -88,24 +90,22 @@ PassConsts pass_launch_consts(const PassKernel& k, int T, const PassArgs& a) {
         const uint64_t wave_span = (hws << k.reg_bits) << a.lo;
         const bool whole = !k.gather || a.a_count % wave_span == 0;
         const bool strides = c.rs_in < ((uint64_t)1 << 28) && c.rs_seg < ((uint64_t)1 << 28);
-        c.late_rows = k.late && c.voff32 && a.in_rows_mask == 0 && whole && strides && !(a.diag & DIAG_NO_LATE_ROWS)
-                          ? 1u
-                          : 0u;
+        const bool on = k.late[Z_SHARD] && !(a.diag & DIAG_NO_LATE_ROWS);
+        c.late_rows = on && c.voff32 && a.in_rows_mask == 0 && whole && strides ? 1u : 0u;
     }
     return c;
 }
 
-// The three launches of a sequence as rs16_engine plans them (encode_high_fused,
-// the identity branch of decode_passes): L / 2 contiguous row bits gathered
-// from the caller's rows (stride S_user), L - L / 2 strided ones on the work
-// buffer, L / 2 contiguous ones stored to the caller's rows.
-bool paired_rows_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count, uint32_t seg_chunk,
-                          uint32_t row_base_in, int diag) {
-    if (diag & DIAG_NO_PAIRED_ROWS) return false;
-    if (chunk_rows < 512 || (chunk_rows & (chunk_rows - 1)) || S == 0 || S % 8 || S / 8 > 0xFFFFFFFFu) return false;
-    int L = 0;
-    while (((uint32_t)1 << L) < chunk_rows) L++;
-    const int lo = L / 2, hi = L - lo;
+// The three launches of a sequence (encode_high_fused, the identity branch of
+// decode_passes): lo contiguous row bits (row_split) gathered from the caller's
+// rows (stride S_user), hi strided ones on the work buffer, lo contiguous ones
+// stored to the caller's rows.  Tower form goes with the paired form: the same
+// gate, its own switch, and a tower flavour of each of the three kernels.
+ZForm z_form_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count, uint32_t seg_chunk,
+                      uint32_t row_base_in, int diag) {
+    if (diag & DIAG_NO_PAIRED_ROWS) return Z_SHARD;
+    if (chunk_rows < 512 || (chunk_rows & (chunk_rows - 1)) || S == 0 || S % 8 || S / 8 > 0xFFFFFFFFu) return Z_SHARD;
+    const RowSplit sp = row_split(__builtin_ctz(chunk_rows));  // (a power of two)
     PassArgs a{};
     a.S_in = a.S_out = a.S_rest = S;
     a.S_seg = S_user;
@@ -113,29 +113,18 @@ bool paired_rows_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint
     a.a_count = a_count, a.chunk = seg_chunk, a.row_base_in = row_base_in;
     a.diag = (uint32_t)diag;
     const struct { int prog, T; uint32_t lo; uint64_t S_out; } seq[3] = {
-        {ENC_FIRST, lo, 0, S}, {ENC_MID, hi, (uint32_t)lo, S}, {ENC_LAST, lo, 0, S_user}};
+        {ENC_FIRST, sp.lo, 0, S}, {ENC_MID, sp.hi, (uint32_t)sp.lo, S}, {ENC_LAST, sp.lo, 0, S_user}};
+    bool tower = !(diag & DIAG_NO_TOWER_ROWS);
     for (const auto& p : seq) {
-        if (p.T > 8) return false;
+        if (p.T > 8) return Z_SHARD;
         // (the geometry and the flavours of (prog, T) are those of every narrow variant)
         const PassKernel& k = find_kernel(p.prog, p.T, 0);
         a.lo = p.lo, a.S_out = p.S_out;
         const PassConsts c = pass_launch_consts(k, p.T, a);
-        if (!k.fn || !k.paired || !c.late_rows || !c.full_lanes) return false;
+        if (!k.fn || !k.late[Z_PAIRED] || !c.late_rows || !c.full_lanes) return Z_SHARD;
+        tower = tower && k.late[Z_TOWER];
     }
-    return true;
-}
-
-// Tower form goes with the paired form: the same gate, the diagnostic switch,
-// and a tower flavour of each of the three kernels (every narrow variant of
-// the middle pass has one where the 12-lookup kernel has).
-bool tower_rows_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count, uint32_t seg_chunk,
-                         uint32_t row_base_in, int diag) {
-    if (diag & DIAG_NO_TOWER_ROWS) return false;
-    if (!paired_rows_sequence(chunk_rows, S, S_user, a_count, seg_chunk, row_base_in, diag)) return false;
-    int L = 0;
-    while (((uint32_t)1 << L) < chunk_rows) L++;
-    const int lo = L / 2, hi = L - lo;
-    return find_kernel(ENC_FIRST, lo, 0).tower && find_kernel(ENC_MID, hi, 0).tower && find_kernel(ENC_LAST, lo, 0).tower;
+    return tower ? Z_TOWER : Z_PAIRED;
 }
 
 hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles, hipStream_t s) {
@@ -164,16 +153,15 @@ hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles
     a.nslab_mul = dn.mul, a.nslab_one = dn.one;
     a.stripe_mul = ds.mul, a.stripe_one = ds.one;
     const size_t lds = (size_t)k.lds;
-    PassFn fn = pc.late_rows ? k.late : k.fn;
-    if (a.paired) {
-        // Paired rows are the sequence's choice (paired_rows_sequence): a
-        // launch that cannot keep it is an error, never the other form --
-        // its neighbour pass would read or write the rows the other way.
-        const bool tower = (a.paired & PAIRED_TOWER) != 0;
-        if ((a.paired & ~(uint32_t)PAIRED_TOWER) != paired_sides_of(prog) || !k.paired || !pc.late_rows ||
-            !pc.full_lanes || (tower && !k.tower))
+    PassFn fn = pc.late_rows ? k.late[Z_SHARD] : k.fn;
+    if (a.z_form != Z_SHARD) {
+        // The form is the sequence's choice (z_form_sequence): a launch that
+        // cannot keep it is an error, never another form -- its neighbour
+        // pass would read or write the rows the other way.
+        const bool in_sequence = prog == ENC_FIRST || prog == ENC_MID || prog == ENC_LAST;
+        if (a.z_form > Z_TOWER || !in_sequence || !pc.late_rows || !pc.full_lanes || !k.late[a.z_form])
             return hipErrorInvalidValue;
-        fn = tower ? k.tower : k.paired;
+        fn = k.late[a.z_form];
     }
     if (lds > 65536) {
         // (per kernel variant: each is a function of its own)

@@ -2,7 +2,7 @@
 // kernels (pass_kernel_late_tower, rs16_pass.hpp): the kernels of a sequence
 // that keeps the work buffer's rows in tower form.
 // One for every kernel a paired sequence can launch (rs16_pass_enc.hip,
-// paired_kernel).  A unit of its own: the kernels of the other units compile
+// pass_kernels_paired).  A unit of its own: the kernels of the other units compile
 // to the code they had without it (Makefile).
 #include "rs16_pass.hpp"
 

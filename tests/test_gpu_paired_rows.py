@@ -4,7 +4,7 @@ identity decode the engine may keep a quad's low and high dword next to each
 other in its work buffer Z, so that a lane moves a row with one 8-byte access.
 The form is a property of the sequence -- the pass that writes Z and the pass
 that reads it must agree -- and one host function decides it
-(paired_rows_sequence, shown here as rs16_host_paired_rows): paired exactly
+(z_form_sequence, shown here as rs16_host_paired_rows): paired exactly
 when all three launches report late_rows and full_lanes and
 RS16_DIAG_NO_PAIRED_ROWS is not set.  Results are the same bits either way.
 
