@@ -692,16 +692,24 @@ int rs16_host_paired_rows(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint
  * rs16_host_tower_conv: out[] = in[] switched between the two forms (the
  * kernels' lookups, v_perm emulated; its own inverse), `bytes` a multiple of 64.
  * rs16_host_tower_twiddle: the 20-dword table of skew index `index` in tower
- * coordinates, as the middle pass of a tower sequence stages it (0: out of range).
+ * coordinates, as the passes of a tower sequence stage it (0: out of range).
  * rs16_host_mul_tower: out[] = that table applied to in[] (tower form in and
- * out), with the 12-lookup multiply or, `narrow` != 0, the 6-lookup one of the
- * layers whose twiddles are subfield elements. */
+ * out); `form` = 0: the 12-lookup multiply, 1: the 6-lookup one of the layers
+ * whose twiddles are subfield elements, 2: the 9-lookup wide multiply of the
+ * T = 7 passes, 3: the one for twiddles s ^ v_8, s in the subfield (the middle
+ * pass's wide layer).
+ * rs16_host_tower_sweep: the same for the `n` skew indices index[]: the tower
+ * table of index[i] applied to in[] (`bytes`, tower form) in form `form`,
+ * converted to the shards' coordinates and compared with want[i * bytes ..);
+ * returns the number of elements that differ over all i. */
 int rs16_host_tower_rows(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t a_count, uint32_t seg_chunk,
                          uint32_t row_base_in, int diag);
 uint32_t rs16_host_tower_basis(uint32_t i);
 void rs16_host_tower_conv(const void* in, void* out, size_t bytes);
 int rs16_host_tower_twiddle(uint32_t index, uint32_t* table20);
-void rs16_host_mul_tower(const void* in, void* out, size_t bytes, uint32_t index, int narrow);
+void rs16_host_mul_tower(const void* in, void* out, size_t bytes, uint32_t index, int form);
+uint64_t rs16_host_tower_sweep(const uint32_t* index, size_t n, int form, const void* in, const void* want,
+                               size_t bytes);
 /* The shape of the launch by which rs16_update_device updates `rows` recovery
  * rows of `shard_bytes` from `n` deltas, as the launcher computes it (one host
  * function, which every update calls; no device needed):

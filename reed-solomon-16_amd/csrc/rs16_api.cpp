@@ -3,7 +3,10 @@
 // helpers.  The rest of the C ABI: rs16_api_coders.cpp (rs16_encoder /
 // rs16_decoder), rs16_api_device.cpp and rs16_api_host.cpp (the one-shot
 // codec on device / host shards), rs16_api_update.cpp (the delta update).
+#include <algorithm>
 #include <atomic>
+#include <thread>
+#include <vector>
 #include <rccl/rccl.h>
 
 #include <cstdio>
@@ -181,9 +184,40 @@ extern "C" int rs16_host_tower_twiddle(uint32_t index, uint32_t* table20) {
     if (table20) memcpy(table20, &host_tables().skew_tab_tower[(size_t)index * TAB_DWORDS], 20 * sizeof(uint32_t));
     return 1;
 }
-extern "C" void rs16_host_mul_tower(const void* in, void* out, size_t bytes, uint32_t index, int narrow) {
+// (form: 0 the 12-lookup multiply, 1 the 6-lookup narrow one, 2 the 9-lookup wide one, 3 the wide one with c1 = 1)
+static void host_mul_tower(const void* in, void* out, size_t bytes, uint32_t index, int form) {
     const uint32_t* t = &host_tables().skew_tab_tower[(size_t)(index < GF_MODULUS ? index : GF_MODULUS) * TAB_DWORDS];
-    host_mul_table(in, out, bytes, t, narrow ? mul_xor_tower_narrow : mul_xor);
+    if (form == 2) host_mul_table(in, out, bytes, t, mul_xor_tower_wide);
+    else if (form == 3) host_mul_table(in, out, bytes, t, mul_xor_tower_beta);
+    else host_mul_table(in, out, bytes, t, form == 1 ? mul_xor_tower_narrow : mul_xor);
+}
+extern "C" void rs16_host_mul_tower(const void* in, void* out, size_t bytes, uint32_t index, int form) {
+    host_mul_tower(in, out, bytes, index, form);
+}
+extern "C" uint64_t rs16_host_tower_sweep(const uint32_t* index, size_t n, int form, const void* in, const void* want,
+                                          size_t bytes) {
+    // (index i on its own: multiply, convert, compare; the indices shared out over a few threads)
+    std::atomic<uint64_t> bad{0};
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        std::vector<uint8_t> prod(bytes), shard(bytes);
+        for (size_t i; (i = next.fetch_add(1)) < n;) {
+            host_mul_tower(in, prod.data(), bytes, index[i], form);
+            rs16_host_tower_conv(prod.data(), shard.data(), bytes);
+            const uint8_t* w = (const uint8_t*)want + i * bytes;
+            uint64_t b = 0;
+            for (size_t blk = 0; blk < bytes / 64; blk++)
+                for (size_t e = 0; e < 32; e++)
+                    b += shard[blk * 64 + e] != w[blk * 64 + e] || shard[blk * 64 + 32 + e] != w[blk * 64 + 32 + e];
+            bad += b;
+        }
+    };
+    const size_t nthr = std::min<size_t>({n, 16, std::max(1u, std::thread::hardware_concurrency())});
+    std::vector<std::thread> thr;
+    for (size_t i = 1; i < nthr; i++) thr.emplace_back(work);
+    work();
+    for (auto& th : thr) th.join();
+    return bad.load();
 }
 extern "C" int rs16_host_update_consts(uint32_t rows, uint64_t shard_bytes, uint32_t n, uint32_t* quads_per_lane,
                                        uint32_t* nslab, uint32_t* rows_per_wave, uint64_t* blocks) {

@@ -306,11 +306,11 @@ int rs16_engine::col_multi(size_t k, size_t m, size_t S, size_t S_user, const ui
     return profiled(PROF_COL_ENC, s, err, [&](uint64_t*) { return launch_col_multi(c, high, s); });
 }
 
-// A launch of program prog in a sequence that keeps the work buffer in form f:
-// the form, and its twiddle table (a tower middle pass: in tower coordinates).
-void rs16_engine::z_form_args(PassArgs& a, int prog, ZForm f) const {
+// The three launches of a sequence that keeps the work buffer in form f: the
+// form, and their twiddle table (a tower sequence: in tower coordinates).
+void rs16_engine::z_form_args(PassArgs& a, ZForm f) const {
     a.z_form = f;
-    a.skew_tab = prog == ENC_MID && f == Z_TOWER ? d_skew_tab_tower : d_skew_tab;
+    a.skew_tab = f == Z_TOWER ? d_skew_tab_tower : d_skew_tab;
 }
 
 // Engine::fft over 2^L rows: L <= 8 in one pass; otherwise the high
@@ -407,17 +407,15 @@ int rs16_engine::encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, 
     const ZForm zf = z_form_sequence((uint32_t)chunk, S, S_user, a.a_count, a.chunk, a.row_base_in, diag);
     a.out = Z;
     a.lo = 0;
-    z_form_args(a, ENC_FIRST, zf);
+    z_form_args(a, zf);
     RS16_PASS(ENC_FIRST, lo, a, batch(1u << hi, 0, zs, bs_orig), s);
     a.in = Z;
     a.lo = lo;
-    z_form_args(a, ENC_MID, zf);
     RS16_PASS(ENC_MID, hi, a, batch(1u << lo, zs, zs, 0), s);
     a.in = Z;
     a.out = d_rec;
     a.S_out = S_user;
     a.lo = 0;
-    z_form_args(a, ENC_LAST, zf);
     const uint32_t tiles = (uint32_t)((m + ((size_t)1 << lo) - 1) >> lo);
     RS16_PASS(ENC_LAST, lo, a, batch(tiles, zs, bs_rec, 0), s);
     return RS16_OK;
@@ -665,18 +663,16 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
             const ZForm zf = z_form_sequence(half, S, S_user, a.a_count, a.chunk, a.row_base_in, diag);
             a.lo = 0;
             a.out = Z;
-            z_form_args(a, ENC_FIRST, zf);
+            z_form_args(a, zf);
             RS16_PASS_AS(PROF_DEC_HALF_FIRST, ENC_FIRST, lo, a, batch(1u << hi, 0, 0, zs), s);
             a.rcount = nullptr;
             a.lo = lo;
             a.in = Z;
-            z_form_args(a, ENC_MID, zf);
             RS16_PASS_AS(PROF_DEC_HALF_MID, ENC_MID, hi, a, batch(1u << lo, zs, 0, zs), s);
             a.lo = 0;
             a.out = rest;
             a.S_out = S_user;
             a.out_rows = orig;
-            z_form_args(a, ENC_LAST, zf);
             a.rcount = rcount;
             a.cnt_flags = g.high ? flags_b : flags_a;
             a.cnt_base = dst;

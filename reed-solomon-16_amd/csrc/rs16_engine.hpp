@@ -77,7 +77,7 @@ struct rs16_engine {
     // diagnostic switches of this engine (rs16::DiagFlags, rs16_engine_set_diagnostics)
     int diag = 0;
     uint32_t* d_skew_tab = nullptr;  // v_perm table per twiddle index (8 MiB)
-    uint32_t* d_skew_tab_tower = nullptr;  // the same in tower coordinates: the middle pass of a tower sequence
+    uint32_t* d_skew_tab_tower = nullptr;  // the same in tower coordinates: the passes of a tower sequence
     uint32_t* d_mul_tab = nullptr;
     uint32_t* d_col_img = nullptr;   // column codec table images (HostTables::col_img)
     uint32_t* d_col_v = nullptr;     // column codec eval_poly tables (HostTables::col_v)
@@ -221,8 +221,8 @@ struct rs16_engine {
     int prof_collect(rs16_error* err);
 
     // Engine ops on device shard arrays (validated by the C ABI layer).
-    // the form field and twiddle table of one launch of a three-pass sequence (z_form_sequence)
-    void z_form_args(rs16::PassArgs& a, int prog, rs16::ZForm f) const;
+    // the form field and twiddle table of the launches of a three-pass sequence (z_form_sequence)
+    void z_form_args(rs16::PassArgs& a, rs16::ZForm f) const;
     int fft(uint8_t* data, size_t S, size_t pos, size_t size, size_t skew_delta, hipStream_t s, rs16_error* err);
     int ifft(uint8_t* data, size_t S, size_t pos, size_t size, size_t skew_delta, hipStream_t s, rs16_error* err);
 

@@ -190,6 +190,46 @@ RS16_HD void mul_xor_tower_narrow_sel(uint32_t& xL, uint32_t& xH, const MulSel& 
 RS16_HD void mul_xor_tower_narrow(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const uint32_t* t) {
     mul_xor_tower_narrow_sel(xL, xH, mul_selectors(yL, yH), t);
 }
+// A wide constant c = c0 + c1 beta in tower form.  beta^2 = beta + v_7, so
+//   (a + b beta) c = (a c0 + b c1 v_7) + (a c1 + b c0 + b c1) beta,
+// and the constant's tower table holds four byte maps: L -> lo = M_{c0}
+// (dwords 0, 1, 4, 5, 16), H -> lo = M_{c1 v_7} (8, 9, 12, 13, 18), L -> hi =
+// M_{c1} (2, 3, 6, 7, 17), H -> hi = M_{c0 ^ c1} (10, 11, 14, 15, 19).  Three
+// of them do (Karatsuba): with P1 = M_{c0}(a), Q = M_{c1 v_7}(b), P3 = M_{c0 ^
+// c1}(a ^ b) the product is (P1 ^ Q, P3 ^ P1).  The selectors of a ^ b are
+// sel(a) ^ sel(b) -- the maps are linear, no shift or mask -- and P1's partial
+// XOR serves both bytes: 9 v_perm and 25 instructions per quad against 12 and
+// 26.  rs16_tables.cpp checks the three-map product at table build.
+RS16_HD void mul_xor_tower_wide_sel(uint32_t& xL, uint32_t& xH, const MulSel& y, const uint32_t* t) {
+    const uint32_t u0 = y.s0 ^ y.s3, u1 = y.s1 ^ y.s4, u2 = y.s2 ^ y.s5;
+    const uint32_t p0 = perm(t[1], t[0], y.s0), p1 = perm(t[5], t[4], y.s1), p2 = perm(t[16], t[16], y.s2);
+    const uint32_t q0 = perm(t[9], t[8], y.s3), q1 = perm(t[13], t[12], y.s4), q2 = perm(t[18], t[18], y.s5);
+    const uint32_t r0 = perm(t[11], t[10], u0), r1 = perm(t[15], t[14], u1), r2 = perm(t[19], t[19], u2);
+    const uint32_t p = xor3(p0, p1, p2);
+    xL = xor3(xor3(xL, p, q0), q1, q2);
+    xH = xor3(xor3(xH, p, r0), r1, r2);
+}
+RS16_HD void mul_xor_tower_wide(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const uint32_t* t) {
+    mul_xor_tower_wide_sel(xL, xH, mul_selectors(yL, yH), t);
+}
+// The same with c1 = 1 (the one wide layer of a 2^15-row chunk's middle pass:
+// its twiddles are s ^ v_8 with s in the subfield): M_{c1} is the identity and
+// M_{c0 ^ c1}(b) = M_{c0}(b) ^ b, so the product is (M_{c0}(a) ^ M_{v_7}(b),
+// M_{c0}(b) ^ a ^ b) -- the narrow multiply's six lookups, three of b's
+// selectors in the H -> lo pools, and two plain XORs: 9 v_perm and 23
+// instructions per quad.
+RS16_HD void mul_xor_tower_beta_sel(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const MulSel& y,
+                                    const uint32_t* t) {
+    const uint32_t l0 = perm(t[1], t[0], y.s0), h0 = perm(t[1], t[0], y.s3);
+    const uint32_t l1 = perm(t[5], t[4], y.s1), h1 = perm(t[5], t[4], y.s4);
+    const uint32_t l2 = perm(t[16], t[16], y.s2), h2 = perm(t[16], t[16], y.s5);
+    const uint32_t q0 = perm(t[9], t[8], y.s3), q1 = perm(t[13], t[12], y.s4), q2 = perm(t[18], t[18], y.s5);
+    xL = xor3(xor3(xL, l0, l1), xor3(l2, q0, q1), q2);
+    xH = xor3(xor3(xH, h0, h1), h2, yL) ^ yH;
+}
+RS16_HD void mul_xor_tower_beta(uint32_t& xL, uint32_t& xH, uint32_t yL, uint32_t yH, const uint32_t* t) {
+    mul_xor_tower_beta_sel(xL, xH, yL, yH, mul_selectors(yL, yH), t);
+}
 
 // Ones'-complement add/sub on logs (reference add_mod/sub_mod,
 // src/engine.rs:90-100), in 32-bit arithmetic.

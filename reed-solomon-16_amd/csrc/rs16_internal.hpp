@@ -93,6 +93,24 @@ inline int first_narrow_layer(uint32_t lo, int T, uint32_t skew, uint32_t bh_max
     return k;
 }
 
+// The wide twiddles nearest the subfield: s ^ v_8 with s in the subfield, i.e.
+// tower coordinates (c0, c1) = (s, 1), are the twiddles of the indices with
+// 2^(b+8) <= x < 2^(b+9) (x, b as above) -- the layer's span gains v_8 alone.
+// Their tower-form multiply is the narrow one plus x beta (mul_xor_tower_beta,
+// rs16_gf.hpp).  rs16_tables.cpp checks the rule against the tables as well.
+RS16_HD bool twiddle_beta(uint32_t i) {
+    const uint32_t x = i + 1;
+    return (x >> 8) >= (x & (0u - x)) && (x >> 9) < (x & (0u - x));
+}
+// Whether every twiddle of layer kb of a launch's direction (as above) is one.
+inline bool layer_beta(uint32_t lo, int kb, int T, uint32_t skew, uint32_t bh_max) {
+    const uint64_t d = (uint64_t)1 << (lo + kb);
+    const uint64_t xmin = d + skew, xmax = (((uint64_t)bh_max + 1) << (lo + T)) - d + skew;
+    const uint64_t low = (d + skew) & (2 * d - 1);
+    // (low == 0: the lowest set bit differs between the groups)
+    return low != 0 && xmin >= ((low & (0 - low)) << 8) && xmax < ((low & (0 - low)) << 9);
+}
+
 // ---------------------------------------------------------------------------
 // Pass kernels.  A "pass" applies a contiguous range of FFT/IFFT layers to
 // tiles of 2^T rows (T <= 8) x Q quads (Q = 32 for T > 4, else 64; a quad is
@@ -390,8 +408,8 @@ inline RowSplit row_split(int L) { return {L / 2, L - L / 2}; }
 // The form of the work buffer's rows between the passes of a sequence
 // ENC_FIRST -> ENC_MID -> ENC_LAST (the three-pass encode, the identity
 // decode): the shards' own; a quad's two dwords adjacent (DESIGN.md section
-// 2); or paired and in tower coordinates (section 3.1), where the middle pass
-// gets the tower twiddle table (HostTables::skew_tab_tower) as its skew_tab.
+// 2); or paired and in tower coordinates (section 3.1), where the three passes
+// get the tower twiddle table (HostTables::skew_tab_tower) as their skew_tab.
 // A property of the sequence: the pass that writes the buffer and the pass
 // that reads it must agree.
 enum ZForm : uint32_t { Z_SHARD = 0, Z_PAIRED, Z_TOWER };

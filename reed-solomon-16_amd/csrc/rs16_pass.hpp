@@ -780,6 +780,17 @@ template <int NV> struct NarrowVar {
     static constexpr int FFT_FROM = NV == 0 ? NONE : (NV == 3 ? 1 : 0);
 };
 
+// The form of the rows in a block's layers (GroupLoop's TW): shard
+// coordinates, or tower form, there with the wide multiplies by 12 lookups
+// or by three byte maps.
+enum { TW_NONE = 0, TW_ROWS, TW_WIDE3 };
+// A wide multiply on a tower table: by three byte maps, or with 12 lookups.
+template <bool WIDE3> __device__ __forceinline__ void mul_xor_tower_sel(uint32_t& xL, uint32_t& xH, const MulSel& y,
+                                                                      const uint32_t (&t)[20]) {
+    if constexpr (WIDE3) mul_xor_tower_wide_sel(xL, xH, y, t);
+    else mul_xor_sel<false>(xL, xH, y, t);
+}
+
 // NK: the direction's first narrow layer -- the layers kb >= NK multiply
 // with mul_xor_narrow (every twiddle of theirs in this launch is a subfield
 // constant: launch_pass picks the kernel variant from first_narrow_layer).
@@ -787,12 +798,18 @@ template <int NV> struct NarrowVar {
 // of the block's first layer -- the q-th pair of that layer, counted over its
 // groups -- and requests the rows of a later pair.
 // TW (the tower kernels, pass_kernel_late_tower): the rows are in tower form
-// where the pass keeps them so -- ENC_MID throughout, its narrow layers with
-// the 6-lookup multiply of one byte map; ENC_LAST's rows as loaded, converted
-// in its first layer (pre.tb: B's pools), the multiplicand ahead of its low
-// selectors, which it shares its high ones with.
+// in every layer, and every twiddle table is the tower one.  ENC_MID: its
+// narrow layers with the 6-lookup multiply of one byte map, the wide layer of
+// a narrow variant with the c1 = 1 form (mul_xor_tower_beta; launch_pass
+// checks the layer's indices).  ENC_FIRST and ENC_LAST convert at the caller's
+// rows: ENC_FIRST in its first layer (pre.tb: B's pools) -- y ^= x in shard
+// coordinates, then the multiplicand y ahead of its low selectors, which it
+// shares its high ones with, then x -- and ENC_LAST in its last (fin.tb), x
+// after the multiply and y from the selectors the multiply took, ahead of y
+// ^= x (conv is linear).  TW_WIDE3: they multiply by three byte maps in every
+// layer (mul_xor_tower_wide), TW_ROWS: with 12 lookups on the same table.
 template <int P, int T, int NK, bool LB, int KB0, int KB1, bool FFT, bool IN_TAB2, int PRUNE, int G, class FIN = NoFin,
-          class PRE = NoPre, bool TW = false>
+          class PRE = NoPre, int TW = TW_NONE>
 struct GroupLoop {
     static __device__ __forceinline__ void run(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR], const Thr& c,
                                                const PassArgs& a, const uint4* tab1, const uint4* tab2,
@@ -835,14 +852,41 @@ struct GroupLoop {
             for (int j = 0; j < (1 << rb); j++) {
                 const int m = (gi << (rb + 1)) + j, m2 = m + (1 << rb);
                 if constexpr (!std::is_same<PRE, NoPre>::value && s == 0) pre(L, H, (gi << rb) + j);
-                if constexpr (TW && P == ENC_LAST && LB && FFT && s == 0) {
+                if constexpr (TW && P == ENC_FIRST && !LB && kb == 0) {
+                    L[m2] ^= L[m];
+                    H[m2] ^= H[m];
                     MulSel y = high_selectors(H[m2]);
                     tower_conv_sel(L[m2], y, pre.tb);
                     y = low_selectors(L[m2], y);
                     tower_conv(L[m], H[m], pre.tb);
-                    mul_xor_sel<false>(L[m], H[m], y, cur);
+                    mul_xor_tower_sel<TW == TW_WIDE3>(L[m], H[m], y, cur);
+                } else if constexpr (TW && P == ENC_LAST && !LB && kb == 0) {
+                    const MulSel y = mul_selectors(L[m2], H[m2]);
+                    mul_xor_tower_sel<TW == TW_WIDE3>(L[m], H[m], y, cur);
+                    tower_conv_sel(L[m2], y, fin.tb);
+                    tower_conv(L[m], H[m], fin.tb);
                     L[m2] ^= L[m];
                     H[m2] ^= H[m];
+                } else if constexpr (TW && P != ENC_MID) {
+                    if (FFT) {
+                        mul_xor_tower_sel<TW == TW_WIDE3>(L[m], H[m], mul_selectors(L[m2], H[m2]), cur);
+                        L[m2] ^= L[m];
+                        H[m2] ^= H[m];
+                    } else {
+                        L[m2] ^= L[m];
+                        H[m2] ^= H[m];
+                        mul_xor_tower_sel<TW == TW_WIDE3>(L[m], H[m], mul_selectors(L[m2], H[m2]), cur);
+                    }
+                } else if constexpr (TW && P == ENC_MID && !NARROW && NK != NarrowVar<0>::NONE) {
+                    if (FFT) {
+                        mul_xor_tower_beta(L[m], H[m], L[m2], H[m2], cur);
+                        L[m2] ^= L[m];
+                        H[m2] ^= H[m];
+                    } else {
+                        L[m2] ^= L[m];
+                        H[m2] ^= H[m];
+                        mul_xor_tower_beta(L[m], H[m], L[m2], H[m2], cur);
+                    }
                 } else if constexpr (TW && P == ENC_MID && NARROW) {
                     if (FFT) {
                         mul_xor_tower_narrow(L[m], H[m], L[m2], H[m2], cur);
@@ -900,7 +944,7 @@ __device__ __forceinline__ const uint4* lds_vgpr(const uint4* p) {
 
 // Apply the layers for k-bits [KB0, KB1) held in registers of layout LB.
 template <int P, int T, int NK, bool LB, int KB0, int KB1, bool FFT, bool IN_TAB2, int PRUNE = PR_NONE,
-          class FIN = NoFin, class PRE = NoPre, bool TW = false>
+          class FIN = NoFin, class PRE = NoPre, int TW = TW_NONE>
 __device__ __forceinline__ void layers(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR], const Thr& c,
                                        const PassArgs& a, const uint4* tab1, const uint4* tab2,
                                        uint32_t zmask = 0, const FIN& fin = FIN(), const PRE& pre = PRE()) {
@@ -1582,6 +1626,12 @@ template <int P, int T, bool PAIR = false> struct EarlyStore {
     }
 };
 
+// EarlyStore of the tower form's last pass, with B's pools for the conversion
+// in the layer ahead of the stores (GroupLoop).
+template <int P, int T, bool PAIR> struct EarlyStoreTower : EarlyStore<P, T, PAIR> {
+    TowerB tb;
+};
+
 // The same for a pass that ends with its IFFT in layout B (ENC_FIRST, the
 // decoders' first pass, GEN_IFFT): the rows with register bit 0 clear and
 // those with it set go through the block's layers separately -- the layer of
@@ -1611,14 +1661,12 @@ template <int T> struct HalfSeq {
         return g;
     }
 };
-// TB = TowerB: the tower kernels' form of the block (ENC_FIRST writing Z in
-// tower form).  In each half's last layer (kb = T - 1, which every row passes
-// once) both rows of a butterfly are final and are converted there -- the
-// multiplicand from the high selectors its multiply extracted, the product's
-// row from its own.
+// TB = TowerMul<WIDE3>: the tower kernels' form of the block (ENC_FIRST, its
+// rows in tower form since its first layer): the multiply on a tower table,
+// WIDE3 by three byte maps.
 struct NoTower {};
+template <bool WIDE3> struct TowerMul {};
 template <int T, int G, class FIN, class TB = NoTower> struct HalfLoop {
-    static_assert(std::is_same<TB, NoTower>::value || HalfSeq<T>::SH < Geo<T>::R, "a row's last layer: kb = T - 1");
     static __device__ __forceinline__ void run(uint32_t (&L)[Geo<T>::NR], uint32_t (&H)[Geo<T>::NR],
                                                const uint4* tab1, const uint32_t (&cur)[20], const FIN& fin,
                                                const TB& tb = TB()) {
@@ -1637,11 +1685,8 @@ template <int T, int G, class FIN, class TB = NoTower> struct HalfLoop {
             const int m = (gi << (rb + 1)) + j, m2 = m + (1 << rb);
             L[m2] ^= L[m];
             H[m2] ^= H[m];
-            if constexpr (!std::is_same<TB, NoTower>::value && kb == T - 1) {
-                const MulSel y = mul_selectors(L[m2], H[m2]);
-                mul_xor_sel<false>(L[m], H[m], y, cur);
-                tower_conv_sel(L[m2], y, tb);
-                tower_conv(L[m], H[m], tb);
+            if constexpr (std::is_same<TB, TowerMul<true>>::value) {
+                mul_xor_tower_wide(L[m], H[m], L[m2], H[m2], cur);
             } else {
                 mul_xor(L[m], H[m], L[m2], H[m2], cur);
             }
@@ -1686,14 +1731,17 @@ template <int P, int T, bool PAIR = false> struct EvenStore {
 // workgroup calls it for the same item).
 // (PRE: the late-rows kernels' requests inside the first layer block, LateRows;
 // PAIR_OUT: the stores write paired rows, FastStore; TOWER: Z's rows are in
-// tower form -- ENC_FIRST converts its rows in its last layer, ENC_MID works in
-// that form, ENC_LAST converts in its first layer; pre.tb holds B's pools)
+// tower form and so are the rows in every layer -- ENC_FIRST converts its rows
+// in its first layer, ENC_LAST in its last; pre.tb holds B's pools)
 template <int P, int T, int NV, class PRE = NoPre, bool PAIR_OUT = false, bool TOWER = false>
 __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, uint32_t tile, ItemRegs<P, T>& d,
                                              uint8_t* smem, const PRE& pre = PRE()) {
     using PT = ProgTraits<P>;
-    constexpr int NKI = NarrowVar<NV>::IFFT_FROM, NKF = NarrowVar<NV>::FFT_FROM;
-    static_assert(NV == 0 || (PT::IFFT && PT::FFT && T > 4), "narrow variants: two-direction passes only");
+    // (a one-direction tower pass has no narrow layers: its NV is the wide multiply, pass_kernel_late_tower)
+    constexpr bool WIDE3 = TOWER && !(PT::IFFT && PT::FFT) && NV == 1;
+    constexpr int TWF = !TOWER ? TW_NONE : (WIDE3 ? TW_WIDE3 : TW_ROWS);
+    constexpr int NKI = NarrowVar<(WIDE3 ? 0 : NV)>::IFFT_FROM, NKF = NarrowVar<(WIDE3 ? 0 : NV)>::FFT_FROM;
+    static_assert(NV == 0 || WIDE3 || (PT::IFFT && PT::FFT && T > 4), "narrow variants: two-direction passes only");
     using SM = Smem<P, T>;
     using G = Geo<T>;
     constexpr int NR = G::NR;
@@ -1774,7 +1822,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
         if constexpr (ZERO_SKIP) skip_a = __all(d.zrow == (1u << NR) - 1);
         if constexpr (WaveStaged<P, T>::value) RS16_STAMP_ROWS(a, 6, L, H, 0, 1);
         if constexpr (!std::is_same<PRE, NoPre>::value)
-            layers<P, T, NKI, false, 0, R, false, false, PR_NONE, NoFin, PRE, TOWER>(L, H, c, a, tab1, tab2, 0, NoFin(),
+            layers<P, T, NKI, false, 0, R, false, false, PR_NONE, NoFin, PRE, TWF>(L, H, c, a, tab1, tab2, 0, NoFin(),
                                                                                      pre);
         else if (!skip_a) layers<P, T, NKI, false, 0, R, false, false>(L, H, c, a, tab1, tab2);
         RS16_STAMP(a, 3);
@@ -1808,12 +1856,12 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
                 Thr cs = c;
                 asm volatile("" : "+v"(cs.offL));
                 const EvenStore<P, T, PAIR_OUT> even{a, cs, FastStore<P, T, PAIR_OUT>(a, cs)};
-                if constexpr (TOWER) ifft_b_halves<T>(L, H, tab1, even, pre.tb);  // (B's pools: LateRowsTower)
+                if constexpr (TOWER) ifft_b_halves<T>(L, H, tab1, even, TowerMul<WIDE3>());
                 else ifft_b_halves<T>(L, H, tab1, even);
             } else {
                 // (SHARED: the layout-B tables t >= TSPLIT sit beside the image)
                 const uint4* tab1b = SM::SHARED ? (const uint4*)(smem + SM::TABB_OFF) - G::TSPLIT * 5 : tab1;
-                layers<P, T, NKI, true, R, T, false, false, (ZERO_SKIP ? PR_ZERO : PR_NONE), NoFin, NoPre, TOWER>(
+                layers<P, T, NKI, true, R, T, false, false, (ZERO_SKIP ? PR_ZERO : PR_NONE), NoFin, NoPre, TWF>(
                     L, H, c, a, tab1b, tab2, d.zmask);
             }
             in_b = true;
@@ -1837,10 +1885,10 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
         if constexpr (T > 4) {
             if constexpr (WaveStaged<P, T>::value && !PT::IFFT) RS16_STAMP_ROWS(a, 6, L, H, 0, NR / 2);
             if constexpr (!std::is_same<PRE, NoPre>::value && !PT::IFFT)
-                layers<P, T, NKF, true, R, T, true, TWO, PR_NONE, NoFin, PRE, TOWER>(L, H, c, a, tab1, tab2, 0, NoFin(),
+                layers<P, T, NKF, true, R, T, true, TWO, PR_NONE, NoFin, PRE, TWF>(L, H, c, a, tab1, tab2, 0, NoFin(),
                                                                                      pre);
             else
-                layers<P, T, NKF, true, R, T, true, TWO, (P == DEC_MID ? PR_OUT : PR_NONE), NoFin, NoPre, TOWER>(
+                layers<P, T, NKF, true, R, T, true, TWO, (P == DEC_MID ? PR_OUT : PR_NONE), NoFin, NoPre, TWF>(
                     L, H, c, a, tab1, tab2);
             if constexpr (SPLIT_FD) {
                 // the layout-A bits' derivative terms (fd_image) join the
@@ -1903,11 +1951,18 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
             need = any != 0;
         }
         // second direction's layout-A tables: restaged into tab1 (T > 4), else in tab2
-        if constexpr (EARLY) {
+        if constexpr (EARLY && TOWER && P == ENC_LAST) {
+            // (the last layer converts the rows it stores: B's pools ride in the functor)
+            Thr cs = c;
+            asm volatile("" : "+v"(cs.offL));
+            layers<P, T, NKF, false, 0, R, true, false, PR_NONE, EarlyStoreTower<P, T, PAIR_OUT>, NoPre, TWF>(
+                L, H, c, a, tab1, tab2, 0,
+                EarlyStoreTower<P, T, PAIR_OUT>{{a, cs, rvt, lostf, FastStore<P, T, PAIR_OUT>(a, cs)}, pre.tb});
+        } else if constexpr (EARLY) {
             Thr cs = c;
             asm volatile("" : "+v"(cs.offL));
             layers<P, T, NKF, false, 0, R, true, (TWO && !(SM::RESTAGE)), PR_NONE, EarlyStore<P, T, PAIR_OUT>, NoPre,
-                   TOWER>(L, H, c, a, tab1, tab2, 0,
+                   TWF>(L, H, c, a, tab1, tab2, 0,
                           EarlyStore<P, T, PAIR_OUT>{a, cs, rvt, lostf, FastStore<P, T, PAIR_OUT>(a, cs)});
         } else if (need) {
             layers<P, T, NKF, false, 0, R, true, (TWO && !(SM::RESTAGE))>(L, H, c, a, tab1, tab2);
@@ -2150,8 +2205,12 @@ __global__ void __launch_bounds__(Geo<T>::THREADS, 4) pass_kernel_late_paired(Pa
 // The paired kernels of a sequence that keeps Z in tower form (DESIGN.md
 // section 3.1; rs16_pass_tower.hip instantiates them).  ENC_FIRST and ENC_LAST
 // carry B's pools (read from the padding of the twiddle table's entry 0,
-// uniform) beside their row requests; ENC_MID needs none: its twiddle table
-// is the tower one (PassArgs::skew_tab, the engine's choice per launch).
+// uniform) beside their row requests; ENC_MID needs none.  The twiddle table
+// of all three is the tower one (PassArgs::skew_tab, the engine's choice per
+// sequence).  NV is ENC_MID's narrow variant; ENC_FIRST and ENC_LAST have no
+// narrow layer, and their NV names the wide multiply of every layer instead:
+// 0 the 12 lookups, 1 the three byte maps (process_item's WIDE3; launch_pass
+// finds that kernel through PassKernel::wide3, not as a narrow variant).
 template <int P, int T, bool PAIR> struct LateRowsTower : LateRows<P, T, PAIR> {
     TowerB tb;
     __device__ __forceinline__ LateRowsTower(const PassArgs& a, const Thr& c) : LateRows<P, T, PAIR>(a, c) {
@@ -2188,7 +2247,7 @@ template <int P, int T, int NV = 0> PassKernel pass_entry() {
     using PT = ProgTraits<P>;
     return {pass_kernel<P, T, NV>, Smem<P, T>::BYTES, Geo<T>::THREADS, Geo<T>::Q,
             !PT::IFFT ? Geo<T>::SHB : 0, (!PT::FFT && T > 4) ? Geo<T>::SHB : 0, Geo<T>::R,
-            PT::LOAD == LD_GATHER_ENC ? 1 : 0, {late_entry<P, T, NV>(), nullptr, nullptr}};
+            PT::LOAD == LD_GATHER_ENC ? 1 : 0, {late_entry<P, T, NV>(), nullptr, nullptr}, nullptr};
 }
 // the 12-lookup kernels of program P at T = 0 .. 8
 template <int P> PassKernel pass_row(int T) {

@@ -32,6 +32,11 @@ struct PassKernel {
     // pass_kernel_late_tower, the same in tower form.  The last two are
     // filled in by launch_pass's kernel table, each from its own lookup.
     PassFn late[3];
+    // The tower flavour that multiplies by three byte maps in every layer
+    // (ENC_FIRST / ENC_LAST; nullptr: none): what a
+    // tower sequence launches instead of late[Z_TOWER], which keeps the 12
+    // lookups (RS16_DIAG_WIDE_TWIDDLES).  Filled in like late[1 ..].
+    PassFn wide3;
 };
 // The launch constants that decide a launch's address forms (the PassArgs
 // fields of the same names), as launch_pass sets them from the kernel's
@@ -58,6 +63,7 @@ PassKernel pass_kernels_enc(int prog, int T, int nv);  // rs16_pass_enc.hip: GEN
 PassFn pass_kernels_paired(int prog, int T, int nv);   // rs16_pass_enc.hip: the paired flavours (nullptr: none)
 PassKernel pass_kernels_dec(int prog, int T, int nv);  // rs16_pass_dec.hip: DEC_*
 PassFn pass_kernels_tower(int prog, int T, int nv);    // rs16_pass_tower.hip: the tower flavours (nullptr: none)
+PassFn pass_kernel_tower_wide3(int prog, int T);       // rs16_pass_tower.hip: PassKernel::wide3 (nullptr: none)
 
 #if defined(__HIPCC__) || defined(__HIP__)
 // ---------------------------------------------------------------------------

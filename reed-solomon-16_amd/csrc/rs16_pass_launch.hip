@@ -21,6 +21,7 @@ struct KernelTable {
                     if (!e.fn) e = pass_kernels_dec(prog, T, nv);
                     e.late[Z_PAIRED] = pass_kernels_paired(prog, T, nv);
                     e.late[Z_TOWER] = pass_kernels_tower(prog, T, nv);
+                    e.wide3 = nv == 0 ? pass_kernel_tower_wide3(prog, T) : nullptr;
                 }
     }
 };
@@ -32,14 +33,13 @@ static const PassKernel& find_kernel(int prog, int T, int nv) {
 // The kernel of a launch: among the variants that exist for (prog, T), the
 // one that uses the narrow multiply in the most layers the launch allows
 // (ni / nf: first_narrow_layer of its IFFT / FFT direction).
-static const PassKernel& pick_kernel(int prog, int T, int ni, int nf) {
+static int pick_variant(int prog, int T, int ni, int nf) {
     for (int nv = 1; nv < NARROW_VARIANTS; nv++) {
         const int vi = nv == 2 ? 1 : 0, vf = nv == 3 ? 1 : 0;  // NarrowVar<nv>::IFFT_FROM / FFT_FROM
         if (ni > vi || nf > vf) continue;
-        const PassKernel& k = find_kernel(prog, T, nv);
-        if (k.fn) return k;
+        if (find_kernel(prog, T, nv).fn) return nv;
     }
-    return find_kernel(prog, T, 0);
+    return 0;
 }
 
 const PassKernel& pass_kernel_of(int prog, int T) { return find_kernel(prog, T, 0); }
@@ -134,12 +134,20 @@ hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles
     // Narrow twiddles: the launch's tiles are tile_base + [0, tiles of one
     // stripe), b_high = tile >> lo (RS16_DIAG_WIDE_TWIDDLES: never)
     int ni = T, nf = T;
+    const uint32_t bh_max = (a.tile_base + (a.stripe_tiles ? a.stripe_tiles : num_tiles) - 1) >> a.lo;
     if (!(a.diag & DIAG_WIDE_TWIDDLES)) {
-        const uint32_t bh_max = (a.tile_base + (a.stripe_tiles ? a.stripe_tiles : num_tiles) - 1) >> a.lo;
         ni = first_narrow_layer(a.lo, T, a.skew_ifft, bh_max);
         nf = first_narrow_layer(a.lo, T, a.skew_fft, bh_max);
     }
-    const PassKernel& k = pick_kernel(prog, T, ni, nf);
+    int nv = pick_variant(prog, T, ni, nf);
+    // The tower middle pass of variant 2 / 3 multiplies in its one wide layer
+    // (layer 0 of the IFFT / FFT) by twiddles s ^ v_8, s in the subfield
+    // (mul_xor_tower_beta): a launch whose layer has any other twiddle takes
+    // the 12-lookup kernel.
+    if (a.z_form == Z_TOWER && ((nv == 2 && !layer_beta(a.lo, 0, T, a.skew_ifft, bh_max)) ||
+                                (nv == 3 && !layer_beta(a.lo, 0, T, a.skew_fft, bh_max))))
+        nv = 0;
+    const PassKernel& k = find_kernel(prog, T, nv);
     const PassConsts pc = pass_launch_consts(k, T, a);
     a.nslab = pc.nslab;
     a.ntiles = num_tiles;
@@ -162,6 +170,10 @@ hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles
         if (a.z_form > Z_TOWER || !in_sequence || !pc.late_rows || !pc.full_lanes || !k.late[a.z_form])
             return hipErrorInvalidValue;
         fn = k.late[a.z_form];
+        // The first and last pass of a tower sequence multiply by three byte
+        // maps, in every layer and for every twiddle: the same kernel but for
+        // the multiply (RS16_DIAG_WIDE_TWIDDLES: the 12 lookups of late[]).
+        if (a.z_form == Z_TOWER && k.wide3 && !(a.diag & DIAG_WIDE_TWIDDLES)) fn = k.wide3;
     }
     if (lds > 65536) {
         // (per kernel variant: each is a function of its own)

@@ -26,4 +26,12 @@ PassFn pass_kernels_tower(int prog, int T, int nv) {
     return nullptr;
 }
 
+// The first and last pass with the wide multiply by three byte maps (their
+// third template argument is that choice, not a narrow variant: rs16_pass.hpp).
+PassFn pass_kernel_tower_wide3(int prog, int T) {
+    if (prog == ENC_FIRST && T == 7) return pass_kernel_late_tower<ENC_FIRST, 7, 1>;
+    if (prog == ENC_LAST && T == 7) return pass_kernel_late_tower<ENC_LAST, 7, 1>;
+    return nullptr;
+}
+
 }  // namespace rs16

@@ -170,7 +170,7 @@ void build(HostTables& t) {
         if (v < 4) t.tower_b[4] |= (tower_conv(t, (uint16_t)(v << 14)) & 0xFFu) << (8 * v);
     }
     // The twiddle tables in tower coordinates: conv . M_c . conv for every
-    // skew index, in the layout of skew_tab.  The middle passes of a tower
+    // skew index, in the layout of skew_tab.  The passes of a tower
     // sequence stage these; a subfield twiddle's table must then map both
     // bytes by one byte map and cross nothing between them -- checked here,
     // once, as the narrow rule above.
@@ -197,6 +197,48 @@ void build(HostTables& t) {
             fprintf(stderr, "rs16: tower table of subfield twiddle %u %s\n", i,
                     cross ? "crosses between the bytes" : "maps the two bytes differently");
             abort();
+        }
+    }
+    // The wide multiply of the T = 7 passes (mul_xor_tower_wide, rs16_gf.hpp)
+    // reads three of a tower table's four byte maps as M_{c0}, M_{c1 v_7} and
+    // M_{c0 ^ c1}, (c0, c1) the constant's tower coordinates.  That rests on
+    // beta^2 = beta + v_7 and shows in the table as L -> hi = (L -> lo) ^ (H ->
+    // hi), pool by pool.  Checked here, once: the identity, the pools of every
+    // twiddle, and the three-map product itself on 16 elements that take every
+    // selector value in every bit group of a, b and a ^ b.
+    {
+        const uint16_t beta = 1u << 8, v7 = 1u << 7;
+        if (gf_mul(t, beta, t.log[beta]) != (beta ^ v7)) {
+            fprintf(stderr, "rs16: v_8^2 is not v_8 + v_7: no three-map wide multiply in tower form\n");
+            abort();
+        }
+        for (uint32_t i = 0; i < GF_MODULUS; i++) {
+            const uint32_t lm = t.skew_entry[i];
+            if (lm == ZERO_ENTRY) continue;
+            const uint32_t* e = &t.skew_tab_tower[(size_t)i * TAB_DWORDS];
+            bool ok = (e[0] ^ e[10]) == e[2] && (e[1] ^ e[11]) == e[3] && (e[4] ^ e[14]) == e[6] &&
+                      (e[5] ^ e[15]) == e[7] && (e[16] ^ e[19]) == e[17];
+            for (uint32_t j = 0; j < 16 && ok; j++) {
+                const uint32_t a = (j & 7) | (((j + 3) & 7) << 3) | ((j & 3) << 6);
+                const uint32_t b = j < 8 ? ((j + 5) & 7) | (((j * 3) & 7) << 3) | (((j + 1) & 3) << 6) : 0;
+                const uint16_t x = (uint16_t)(a | (b << 8));
+                const uint16_t want = tower_conv(t, gf_mul(t, tower_conv(t, x), lm));
+                uint32_t xl = 0, xh = 0;  // (a quad of four times x)
+                mul_xor_tower_wide(xl, xh, a * 0x01010101u, b * 0x01010101u, e);
+                ok = xl == (want & 0xFFu) * 0x01010101u && xh == (uint32_t)(want >> 8) * 0x01010101u;
+            }
+            if (!ok) {
+                fprintf(stderr, "rs16: tower table of twiddle %u does not multiply by three byte maps\n", i);
+                abort();
+            }
+            // c1 = 1 (L -> hi is the identity) for exactly the indices of twiddle_beta
+            const bool one = e[2] == 0x03020100u && e[3] == 0x07060504u && e[6] == 0x18100800u &&
+                             e[7] == 0x38302820u && e[17] == 0xC0804000u;
+            if (one != twiddle_beta(i)) {
+                fprintf(stderr, "rs16: twiddle %u is %s s + v_8 with s in the subfield, against the index rule\n", i,
+                        one ? "" : "not");
+                abort();
+            }
         }
     }
     // The conversion's pools ride in the padding of entry 0 of both twiddle

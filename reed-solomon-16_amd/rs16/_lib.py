@@ -49,6 +49,7 @@ SIGNATURES = {
     "rs16_host_tower_conv": (None, [_p, _p, _sz]),
     "rs16_host_tower_twiddle": (_i, [_u32, C.POINTER(_u32)]),
     "rs16_host_mul_tower": (None, [_p, _p, _sz, _u32, _i]),
+    "rs16_host_tower_sweep": (_u64, [C.POINTER(_u32), _sz, _i, _p, _p, _sz]),
     "rs16_host_update_consts": (_i, [_u32, _u64, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32),
                                      C.POINTER(_u64)]),
     "rs16_engine_set_profiling": (_i, [_p, _i, _e]),

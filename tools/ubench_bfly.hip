@@ -3,6 +3,7 @@
 // waves per SIMD.  Reports cycles per wave-butterfly at 2.4 GHz.
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstring>
 #include "../reed-solomon-16_amd/csrc/rs16_gf.hpp"
 using namespace rs16;
 // mul_xor with the selectors of L and H taken by two 64-bit shifts of the
@@ -92,6 +93,12 @@ __global__ void __launch_bounds__(256) k(unsigned* out, const unsigned* tab, uns
                 } else if (MODE == 5) {  // IFFT butterfly, subfield twiddle
                     L[m2] ^= L[m]; H[m2] ^= H[m];
                     mul_xor_narrow(L[m], H[m], L[m2], H[m2], t);
+                } else if (MODE == 6) {  // FFT butterfly, tower form, wide twiddle by three byte maps (9 lookups)
+                    mul_xor_tower_wide(L[m], H[m], L[m2], H[m2], t);
+                    L[m2] ^= L[m]; H[m2] ^= H[m];
+                } else if (MODE == 7) {  // IFFT butterfly, the same
+                    L[m2] ^= L[m]; H[m2] ^= H[m];
+                    mul_xor_tower_wide(L[m], H[m], L[m2], H[m2], t);
                 } else {          // IFFT butterfly
                     L[m2] ^= L[m]; H[m2] ^= H[m];
                     mul_xor(L[m], H[m], L[m2], H[m2], t);
@@ -124,12 +131,33 @@ template <int MODE> float run(unsigned* d, const unsigned* tab, int blocks) {
     g_ghz = c[1] ? (double)c[0] / ((double)c[1] * 10.0) : 2.4;
     return ms;
 }
-int main() {
+template <int MODE> double cycles(unsigned* d, const unsigned* tab, int blocks) {
+    const float ms = run<MODE>(d, tab, blocks);
+    return ms * 1e-3 * g_ghz * 1e9 * 1024 / ((double)blocks * 4 * ITER * 32);
+}
+// `ubench_bfly kara`: the 12-lookup wide butterfly beside the 9-lookup one of
+// the tower form, FFT and IFFT, at 2, 4 and 8 waves per SIMD, three
+// repetitions each (cycles per wave-butterfly per SIMD)
+static void kara(unsigned* d, const unsigned* tab) {
+    for (int wps = 2; wps <= 8; wps *= 2)
+        for (int rep = 1; rep <= 3; rep++) {
+            const int blocks = 256 * wps;
+            const double w0 = cycles<0>(d, tab, blocks), w1 = cycles<1>(d, tab, blocks);
+            const double k0 = cycles<6>(d, tab, blocks), k1 = cycles<7>(d, tab, blocks);
+            printf("waves/SIMD %d rep %d: wide (12 lookups) FFT %.1f IFFT %.1f   tower wide (9 lookups) FFT %.1f IFFT %.1f\n",
+                   wps, rep, w0, w1, k0, k1);
+        }
+}
+int main(int argc, char** argv) {
     unsigned* d; unsigned* tab;
     hipMalloc(&d, 256 * 16 * 256 * 4);
     hipMalloc(&tab, 8 * 32 * 4);
     hipMalloc(&g_clk, 16);
     hipMemset(tab, 0x5a, 8 * 32 * 4);
+    if (argc > 1 && !strcmp(argv[1], "kara")) {
+        kara(d, tab);
+        return 0;
+    }
     for (int wps = 1; wps <= 8; wps *= 2) {
         int blocks = 256 * wps;  // 256-thread blocks = 1 wave per SIMD each
         float ms0 = run<0>(d, tab, blocks), ms1 = run<1>(d, tab, blocks);
