@@ -300,6 +300,61 @@ int rs16_decode_device_batch_varied(rs16_engine* eng, size_t original_count, siz
                                     const uint8_t* d_recovery_received, size_t recovery_received_stride,
                                     const size_t* original_received_counts, const size_t* recovery_received_counts,
                                     void* stream, rs16_error* err);
+/* Repair: rs16_decode_device with d_recovery writable.  Lost originals are
+ * restored in place, and lost recovery shards are regenerated in place, equal
+ * to what rs16_encode_device writes for the full stripe -- the stripe is back
+ * at full redundancy without a decode followed by an encode of everything.
+ * Received slots of both arrays are not written.  Rate selection, flag bytes
+ * (0 = lost, any other value = received), the 64-byte alignment, asynchrony on
+ * `stream`, the ordering on the engine's scratch and the discard of a pending
+ * rs16_decode_prepare are those of rs16_decode_device; the counts MUST equal
+ * the flags, as there.
+ * Errors, in this order: UnsupportedShardCount / InvalidShardSize as
+ * rs16_validate gives them; InvalidArgument for a NULL or misaligned array
+ * (the flag arrays included) and, in the batch form, a bad stride; InvalidArgument
+ * for a count above its shard count, NotEnoughShards (with the decode's
+ * payload) for fewer than original_count received.  Everything received:
+ * RS16_OK, nothing launched.
+ * Three paths (rs16_host_repair_path):
+ *   1  no recovery shard lost: rs16_decode_device itself, every form of it.
+ *   2  no original lost: the engine's encode into a buffer of its own
+ *      (recovery_count x shard_bytes per stripe, kept by the engine) and one
+ *      copy kernel for the rows whose flag is 0.  Costs the encode plus the
+ *      copy, about half a general decode.
+ *   3  both kinds lost: the general decode's passes, the last one revealing
+ *      and storing the lost rows of both segments (each workgroup of it
+ *      returns at once when its tile holds no lost row).  Always the pass
+ *      codec: stripes of up to 2048 work rows, which rs16_decode_device runs in
+ *      the one-launch column codec, take three launches here.
+ * When to prefer it (measured on one MI355X at 1 KiB shards, DESIGN.md 3.16,
+ * profiles/r16_repair.txt): at 32768:32768 with both kinds lost it beats
+ * rs16_decode_device + rs16_encode_device at every pattern tried -- 177
+ * against 206 us with 1 % of each kind lost at random, 134 against 146 with
+ * one shard of each, 184 against 202 at 25 %, 143 against 150 with clustered
+ * losses (where the decode alone has faster kernels the repair does not
+ * take).  At 1000:1000 it LOSES, 30.0-31.6 against 26.1-27.6 us: stripes of up
+ * to 2048 work rows decode in one launch of the column codec and the repair
+ * takes eval_poly plus three passes, so there decode + encode is the faster
+ * way to a whole stripe.  Sizes in between are not measured.  Recovery only:
+ * the encode plus 2.4-5.3 us for the copy, and only the lost rows are
+ * written.  With no recovery shard lost it IS the decode.
+ * rs16_decode_check covers paths 1 and 3 as it covers the decode; after path
+ * 2 (no kernel read the originals' flags) it reports RS16_OK.
+ * Column slices (rs16_engine_set_slices) apply to path 1 only: paths 2 and 3
+ * run one slice whatever the setting (results are the same). */
+int rs16_repair_device(rs16_engine* eng, size_t original_count, size_t recovery_count, size_t shard_bytes,
+                       void* d_original, const uint8_t* d_original_received, void* d_recovery,
+                       const uint8_t* d_recovery_received, size_t original_received_count,
+                       size_t recovery_received_count, void* stream, rs16_error* err);
+/* rs16_repair_device for `nstripes` stripes that lost the same shards (a failed
+ * device holds the same index of every stripe): one shared pattern, arrays and
+ * strides as for rs16_decode_device_batch.  Every stripe's result equals
+ * rs16_repair_device on it alone. */
+int rs16_repair_device_batch(rs16_engine* eng, size_t original_count, size_t recovery_count, size_t shard_bytes,
+                             size_t nstripes, void* d_original, size_t original_stride,
+                             const uint8_t* d_original_received, void* d_recovery, size_t recovery_stride,
+                             const uint8_t* d_recovery_received, size_t original_received_count,
+                             size_t recovery_received_count, void* stream, rs16_error* err);
 /* Checked mode of the engine's last decode: waits for `stream` and compares
  * the received counts that decode was given with the rows the device flags
  * mark received (the eval_poly kernels count them per 64-row chunk as they
@@ -542,7 +597,9 @@ void rs16_host_free(rs16_engine* eng, void* h_ptr);
 /* Diagnostics: per-kernel timing.  When enabled, every HBM pass (and the
  * eval_poly kernel group) is bracketed by hipEvents on its launch stream.
  * rs16_engine_profile_read synchronizes and returns, for pass program
- * `prog` (0 .. rs16_prog_count()-1; the last id is eval_poly), the summed
+ * `prog` (0 .. rs16_prog_count()-1, named by rs16_prog_name: the pass programs,
+ * then the ids of kernel groups such as EVAL_POLY, COL_ENC or REPAIR_COPY; new
+ * ids are appended, so look an id up by its name), the summed
  * milliseconds and the number of launches since the last reset. */
 int rs16_engine_set_profiling(rs16_engine* eng, int enable, rs16_error* err);
 int rs16_engine_profile_read(rs16_engine* eng, int prog, double* total_ms, uint64_t* launches, rs16_error* err);
@@ -632,7 +689,8 @@ uint64_t rs16_host_fast_div_check(uint32_t divisor, uint32_t n0, uint32_t count,
 /* The launch constants by which a pass launch picks its address forms, as
  * the launcher computes them (one host function, which every launch calls;
  * no device needed), and the geometry of the kernel of pass program `prog`
- * (rs16_prog_name; the profiling-only ids have no kernel) at tile bits T:
+ * (rs16_prog_name: the ids below DEC_HALF_FIRST; the ids from there on are
+ * profiling ids, not covered here) at tile bits T:
  *   voff32      1: every lane's byte offset below its wave's row base fits 32
  *               bits (SGPR base + 32-bit lane offset), 0: 64-bit lane offsets
  *   full_lanes  1: the launch's waves may take the full-item fast path
@@ -723,6 +781,22 @@ uint64_t rs16_host_tower_sweep(const uint32_t* index, size_t n, int form, const 
  * 0, no multiple of 64 or too large, n = 0 or above RS16_UPDATE_MAX_SHARDS). */
 int rs16_host_update_consts(uint32_t rows, uint64_t shard_bytes, uint32_t n, uint32_t* quads_per_lane,
                             uint32_t* nslab, uint32_t* rows_per_wave, uint64_t* blocks);
+/* The path rs16_repair_device takes, as the entry points decide it (one host
+ * function; no device needed): 0 nothing to do, 1 = rs16_decode_device (no
+ * recovery shard lost), 2 = encode + copy of the lost recovery rows (no
+ * original lost), 3 = general repair; -1 where the call fails (unsupported
+ * counts, a count above its shard count, fewer than original_count received).
+ * *lo / *first_tile / *tiles (any may be NULL): for path 3 the last pass's
+ * tiles of 2^lo rows.  *tiles tiles are launched in all.  Whole tiles that lie
+ * between the two segments are not launched: then the launches are segment A's
+ * tiles [0, ceil(a_count / 2^lo)) and segment B's from tile *first_tile =
+ * chunk / 2^lo on (the rest of *tiles).  Where the two ranges touch or overlap
+ * they are one range and *first_tile = 0.  One tile at lo = 0 when the stripe
+ * has at most 2^8 work rows (the one-pass kernel).  0, 0, 0 on every other
+ * path.  (Segment A: the recovery shards at the high rate, the originals at
+ * the low rate; chunk = a_count rounded up to a power of two.) */
+int rs16_host_repair_path(size_t original_count, size_t recovery_count, size_t original_received_count,
+                          size_t recovery_received_count, uint32_t* lo, uint32_t* first_tile, uint32_t* tiles);
 
 /* Library/build identification, e.g. "rs16-mi355x gfx950". */
 const char* rs16_version(void);

@@ -312,7 +312,8 @@ extern "C" const char* rs16_prog_name(int prog) {
                                   "ENC_LAST",  "ENC_SINGLE", "DEC_FIRST",     "DEC_MID",
                                   "DEC_LAST",  "DEC_SINGLE", "DEC_HALF_LAST", "DEC_HALF_SINGLE",
                                   "DEC_HALF_FIRST", "DEC_HALF_MID", "EVAL_POLY", "COL_ENC", "COL_DEC",
-                                  "DEC_MID_DIRECT", "DEC_TILE_LAST"};
+                                  "DEC_MID_DIRECT", "DEC_TILE_LAST",
+                                  "DEC_LAST_ALL", "DEC_SINGLE_ALL", "REPAIR_COPY"};
     static_assert(sizeof names / sizeof names[0] == NUM_PROF, "profiling names");
     return (prog >= 0 && prog < NUM_PROF) ? names[prog] : "?";
 }
@@ -451,6 +452,7 @@ extern "C" void rs16_engine_free(rs16_engine* e) {
     e->ev_main.release();
     for (auto& l : e->ev_lane) l.release();
     e->ws_flags.release();
+    e->ws_rep.release();
     e->hp_flags.release();
     for (auto& sl : e->hslot) {
         if (sl.s) (void)hipStreamSynchronize(sl.s), (void)hipStreamDestroy(sl.s);

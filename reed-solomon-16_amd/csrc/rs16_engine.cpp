@@ -85,6 +85,20 @@ DecodeGeom decode_geom(bool high, size_t k, size_t m) {
     return g;
 }
 
+RepairTiles repair_tiles(const DecodeGeom& g) {
+    const int L = ilog2(g.n);
+    if (L <= 8) return {0, 0, 0, 1};
+    RepairTiles t;
+    t.lo = (uint32_t)(L / 2);
+    const uint32_t tile = 1u << t.lo;
+    t.a_tiles = (g.a_count + tile - 1) >> t.lo;
+    t.b_first = g.chunk >> t.lo;
+    const uint32_t b_end = (uint32_t)(((size_t)g.chunk + g.b_count + tile - 1) >> t.lo);
+    if (t.b_first <= t.a_tiles) t.a_tiles = 0, t.b_first = 0;  // one range from tile 0
+    t.b_tiles = b_end - t.b_first;
+    return t;
+}
+
 static PassArgs base_args(const rs16_engine* e, size_t S) {
     PassArgs a;
     std::memset(&a, 0, sizeof a);
@@ -487,6 +501,7 @@ int rs16_engine::decode_eval(const DecodeGeom& g, const uint8_t* flags_a, const 
     es.lostpart = prune ? (uint32_t*)evset->lost.p : nullptr;
     es.lostrange = prune ? (uint32_t*)evset->lost.p + 512 : nullptr;
     es.orig_b = g.high ? 1 : 0;
+    es.lost_all = g.repair ? 1 : 0;  // (the repair stores the lost rows of both segments)
     es.rcount = (uint32_t*)evset->rcount.p;
     es.diag = (uint32_t)diag;
     last_dec = g;
@@ -514,8 +529,9 @@ int rs16_engine::decode_eval(const DecodeGeom& g, const uint8_t* flags_a, const 
     // High-rate half decodes of 2^9 / 2^10-row halves through the column
     // codec: it evaluates the polynomial itself (an n-point XOR convolution,
     // rs16_col.hip) and writes rcount; no kernel here.
-    eval_in_col = S && (half_decode(g) ? g.high && col_ok(ilog2(g.n) - 1, S, nstripes)
-                                       : col_ok(ilog2(g.n), S, nstripes, true));
+    // (the repair takes the pass codec at every size: COL_DEC_GEN restores originals only)
+    eval_in_col = S && !g.repair && (half_decode(g) ? g.high && col_ok(ilog2(g.n) - 1, S, nstripes)
+                                                    : col_ok(ilog2(g.n), S, nstripes, true));
     if (eval_in_col) return RS16_OK;
     es.stamps = stamp_prof == PROF_EVAL_POLY ? (uint64_t*)stamp_buf : nullptr;
     hipEvent_t pev;
@@ -551,6 +567,7 @@ int rs16_engine::decode_eval(const DecodeGeom& g, const uint8_t* flags_a, const 
 // decode is an encode-shaped pipeline on n/2 rows: gather x e -> IFFT ->
 // FFT -> reveal, with no formal derivative.
 bool rs16_engine::half_decode(const DecodeGeom& g) {
+    if (g.repair) return false;  // (a lost recovery shard: the other half's input is not whole, DecodeGeom::repair)
     const bool orig_lost = g.high ? g.b_recv == 0 : g.a_recv == 0;
     return orig_lost && g.n >= 2 && g.n == 2 * (size_t)g.chunk;
 }
@@ -598,7 +615,7 @@ int rs16_engine::mid_tables(int L, const uint32_t** out, rs16_error* err) {
 int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, const uint8_t* seg_a, const uint8_t* flags_a,
                                const uint8_t* seg_b, const uint8_t* flags_b, uint8_t* rest, uint8_t* Z, uint8_t* U,
                                uint32_t* rcount, hipStream_t s, rs16_error* err, size_t nst, size_t bs_a, size_t bs_b,
-                               size_t bs_rest) {
+                               size_t bs_rest, uint8_t* rest_b, size_t bs_rest_b) {
     PassArgs a = base_args(this, S);
     a.S_seg = a.S_rest = S_user;
     a.seg_a = seg_a;
@@ -632,6 +649,8 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
     a.bs_seg = bs_a;
     a.bs_seg_b = bs_b;
     a.bs_rest = bs_rest;
+    a.rest_b = rest_b;
+    a.bs_rest_b = bs_rest_b;
     auto batch = [&](uint32_t tiles, size_t bs_in, size_t bs_in2, size_t bs_out) {
         a.stripe_tiles = ns > 1 ? tiles : 0;
         a.bs_in = bs_in;
@@ -763,7 +782,7 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
         return col(c, L, COL_DEC_GEN, s, err);
     }
     if (L <= 8) {
-        RS16_PASS(DEC_SINGLE, L, a, batch(1, 0, 0, 0), s);
+        RS16_PASS(g.repair ? DEC_SINGLE_ALL : DEC_SINGLE, L, a, batch(1, 0, 0, 0), s);
         return RS16_OK;
     }
     const int lo = L / 2, hi = L - lo;
@@ -786,6 +805,31 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
     a.out = Z;
     RS16_PASS(DEC_FIRST, lo, a, batch(t1z - t0z, 0, 0, zs), s);
     a.tile_base = 0;
+    if (g.repair) {
+        // The repair: the last pass's tiles of both segments are consumed, so
+        // DEC_MID keeps the U rows of tiles [0, end of segment B) (narrowed on
+        // the device by the lost rows' interval, lostrange -- of both segments,
+        // ErasureSpec::lost_all); no direct middle pass, no tile_last kernel
+        // (mid_direct = tl_max = 0).  The last pass is DEC_LAST_ALL over the
+        // tiles of both segments (repair_tiles); each workgroup returns at
+        // once when its tile holds no lost row.
+        const RepairTiles rt = repair_tiles(g);
+        a.lo = lo;
+        a.in = Z;
+        a.out = U;
+        a.need_lo = 0;
+        a.need_hi = rt.b_first + rt.b_tiles;
+        RS16_PASS(DEC_MID, hi, a, batch(1u << lo, zs, 0, zs), s);
+        a.need_lo = a.need_hi = 0;
+        a.lo = 0;
+        a.in = Z;
+        a.in2 = U;
+        a.out = nullptr;
+        if (rt.a_tiles) RS16_PASS(DEC_LAST_ALL, lo, a, batch(rt.a_tiles, zs, zs, 0), s);
+        a.tile_base = rt.b_first;
+        RS16_PASS(DEC_LAST_ALL, lo, a, batch(rt.b_tiles, zs, zs, 0), s);
+        return RS16_OK;
+    }
     // Only tiles that contain original rows are needed in the last pass,
     // so DEC_MID computes and stores only U rows of those tiles (its tile
     // row k is row bits [lo, L) = the last pass's tile index).

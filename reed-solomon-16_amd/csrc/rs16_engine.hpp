@@ -61,8 +61,24 @@ struct DecodeGeom {
     // Received shard counts of the two segments when the caller knows them
     // (0: the whole segment is lost, so its first-pass tiles need no launch).
     size_t a_recv = 1, b_recv = 1;
+    // The repair (rs16_repair_device, general path): the lost rows of both
+    // segments are restored, each to its own array.  The pass codec at every
+    // size -- no half-transform or identity decode (a recovery shard is lost,
+    // so the transform's input is not zero on a half even when every original
+    // is lost), no column codec, no mid_direct / tile_last kernels.
+    bool repair = false;
 };
 DecodeGeom decode_geom(bool high, size_t k, size_t m);
+// The last pass of the general repair (DEC_LAST_ALL, 2^lo-row tiles, lo = L / 2
+// of the n = 2^L > 2^8 work rows): segment A's tiles [0, a_tiles) and segment
+// B's [b_first, b_first + b_tiles), whole tiles between them left out -- one
+// launch when the two ranges touch or overlap (then a_tiles = 0 and B's range
+// starts at tile 0), else two.  n <= 2^8: lo = 0 and one tile, the one-pass
+// kernel's.  Host arithmetic only (rs16_host_repair_path shows it to tests).
+struct RepairTiles {
+    uint32_t lo, a_tiles, b_first, b_tiles;
+};
+RepairTiles repair_tiles(const DecodeGeom& g);
 
 }  // namespace rs16
 
@@ -85,6 +101,9 @@ struct rs16_engine {
     uint8_t* d_zero_sink = nullptr;  // zero page (PassArgs::zero, ColArgs::zero)
     // scratch
     rs16::DevBuf ws_z, ws_u, ws_fd, ws_flags;
+    // the repair's recovery-only path: the re-encoded recovery shards of the
+    // call's stripes (recovery_count x shard_bytes each), reserved on first use
+    rs16::DevBuf ws_rep;
     // the general decode's middle pass as v_perm tables of its matrix, per
     // transform size L (mid_tables; built on first use)
     rs16::DevBuf mid_tab[17];
@@ -267,7 +286,9 @@ struct rs16_engine {
     int decode_passes(const rs16::DecodeGeom& g, size_t S, size_t S_user, const uint8_t* seg_a, const uint8_t* flags_a,
                       const uint8_t* seg_b, const uint8_t* flags_b, uint8_t* rest, uint8_t* Z, uint8_t* U,
                       uint32_t* rcount, hipStream_t s, rs16_error* err, size_t nstripes = 1, size_t bs_a = 0,
-                      size_t bs_b = 0, size_t bs_rest = 0);
+                      size_t bs_b = 0, size_t bs_rest = 0, uint8_t* rest_b = nullptr, size_t bs_rest_b = 0);
+    // (g.repair: rest / bs_rest are segment A's array and stripe stride, rest_b
+    // / bs_rest_b segment B's; the lost rows of both are restored)
     // The half-transform decode applies (every original lost, originals
     // segment = one half of the work rows).
     static bool half_decode(const rs16::DecodeGeom& g);

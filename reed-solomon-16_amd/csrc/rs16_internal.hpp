@@ -147,8 +147,16 @@ enum ProfId : int {
     PROF_COL_DEC,  // one-launch codec: half-transform decode
     PROF_DEC_MID_DIRECT,  // the general decode's middle pass as a direct product (mid_direct_kernel)
     PROF_DEC_TILE_LAST,   // the general decode's last pass, one wave per quad column (tile_last_kernel)
+    // The repair's programs (rs16_repair_device; rs16_pass_repair.hip), appended
+    // so that every earlier id keeps its value.  The first two are pass
+    // programs with kernels (launch_pass takes them), the third is the copy
+    // kernel of the recovery-only path (rs16_repair_copy.hip).
+    DEC_LAST_ALL,         // u + L(z) -> FFT -> reveal the lost rows of both segments -> store each to its array
+    DEC_SINGLE_ALL,       // gather*e -> IFFT -> formal derivative -> FFT -> reveal both segments -> store
+    PROF_REPAIR_COPY,     // rows of the re-encoded recovery whose flag is 0 -> the caller's recovery array
     NUM_PROF
 };
+constexpr bool repair_prog(int prog) { return prog == DEC_LAST_ALL || prog == DEC_SINGLE_ALL; }
 
 struct PassArgs {
     uint8_t* out;              // plain store base (row 0 of the transform)
@@ -282,6 +290,13 @@ struct PassArgs {
     // (In what was padding: the struct's size and every offset stay.)
     uint32_t z_form;
     uint64_t nslab_mul, stripe_mul;
+    // The repair's programs (DEC_LAST_ALL / DEC_SINGLE_ALL) restore the lost
+    // rows of both segments: a lost row r < a_count goes to rest + r S_rest
+    // (segment A's array), a lost row r in [chunk, chunk + b_count) to rest_b +
+    // (r - chunk) S_rest (segment B's; stripe s at + s bs_rest_b).  Read by no
+    // other program.
+    uint8_t* rest_b;
+    uint64_t bs_rest_b;
 };
 
 // n / d for any 32-bit n without a division or a branch: the high 64 bits of
@@ -447,6 +462,12 @@ hipError_t launch_xor(uint8_t* x, const uint8_t* y, size_t bytes, hipStream_t s)
 hipError_t launch_xor_chunks(uint8_t* w, size_t chunk_bytes, uint32_t nch, hipStream_t s);
 hipError_t launch_copy_chunks(uint8_t* w, size_t chunk_bytes, uint32_t nch, hipStream_t s);
 hipError_t launch_formal_derivative(uint8_t* out, const uint8_t* in, size_t shard_count, size_t S, hipStream_t s);
+// The repair's recovery-only path (rs16_repair_copy.hip): row r < rows of src
+// (stride S, stripe stride bs_src) -> row r of dst (stride S, stripe stride
+// bs_dst) for every r whose flag byte flags[r] is 0 (any other value: the row
+// was received and is not written), for nstripes stripes sharing the flags.
+hipError_t launch_repair_copy(uint8_t* dst, const uint8_t* src, const uint8_t* flags, uint32_t rows, uint64_t S,
+                              uint64_t bs_dst, uint64_t bs_src, uint32_t nstripes, hipStream_t s);
 
 // Delta update of recovery shards (rs16_update.hip): rec[r] ^= sum over
 // e < n of delta[e] * (table of entry idx[(row0 + r) n + e]) for r < rows.
@@ -490,6 +511,9 @@ struct ErasureSpec {           // builds the erasure vector of rate_{high,low}.r
     uint32_t* lostpart;
     uint32_t* lostrange;
     uint32_t orig_b;
+    // 1 (the repair): lostpart / lostrange cover the rows of both segments
+    // without a received flag, not the originals' alone.  Default 0.
+    uint32_t lost_all;
     // Received rows per 64-row chunk of rows [0, n), by segment:
     // rcount[2 c] = rows of segment A, rcount[2 c + 1] = rows of segment B
     // (rs16_decode_check compares their sums with the caller's counts).

@@ -162,7 +162,9 @@ __device__ __forceinline__ bool received_at(const ErasureSpec& e, uint32_t i) {
     return false;
 }
 // Row i lies in the originals' segment (B for the high rate, A for the low).
+// (ErasureSpec::lost_all, the repair: a row of either segment)
 __device__ __forceinline__ bool orig_row(const ErasureSpec& e, uint32_t i) {
+    if (e.lost_all) return i < e.a_count || (i >= e.chunk && i - e.chunk < e.b_count);
     return e.orig_b ? (i >= e.chunk && i - e.chunk < e.b_count) : i < e.a_count;
 }
 // First / one past the last lost-original row of block blk (rows base +
@@ -396,7 +398,7 @@ __global__ void __launch_bounds__(256) eval_fused_kernel(ErasureSpec e, uint32_t
                 acc = __builtin_amdgcn_sdot4((int)nz80(w[c]), (int)(((wm >> (4 * i + c)) & 1) ? sm : sp), acc, false);
         }
         if (j == 0 && e.lostrange) {  // (uniform: workgroup 0 of a general decode)
-            const bool want = e.orig_b ? reg == 2 : reg == 0;
+            const bool want = e.lost_all || (e.orig_b ? reg == 2 : reg == 0);  // (fl: reg is 0 or 2)
 #pragma unroll
             for (int i = 0; i < 16; i++) {
                 const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};

@@ -6,7 +6,8 @@
 //
 // Included only by the units that instantiate pass_kernel<P, T, NV>
 // (rs16_pass_enc.hip, rs16_pass_dec.hip; rs16_pass_tower.hip for the tower
-// flavours pass_kernel_late_tower); launch_pass (rs16_pass_launch.hip)
+// flavours pass_kernel_late_tower; rs16_pass_repair.hip for the repair's
+// programs, pass_kernel_repair); launch_pass (rs16_pass_launch.hip)
 // reaches the kernels through their PassKernel lookups.
 //
 // Structure of one pass
@@ -76,7 +77,10 @@
 namespace rs16 {
 
 enum LoadMode { LD_PLAIN = 0, LD_GATHER_ENC, LD_GATHER_DEC, LD_DEC_LAST };
-enum StoreMode { ST_PLAIN = 0, ST_RECOVERY, ST_RESTORE };
+// ST_RESTORE_ALL (the repair's programs): ST_RESTORE for the lost rows of both
+// segments, each stored to its own segment's array (PassArgs::rest / rest_b).
+enum StoreMode { ST_PLAIN = 0, ST_RECOVERY, ST_RESTORE, ST_RESTORE_ALL };
+constexpr bool st_restores(int st) { return st == ST_RESTORE || st == ST_RESTORE_ALL; }
 
 // Store cache policy: non-temporal stores in the single-direction passes,
 // plain stores in the two-direction passes (same-box A/B, CHANGELOG.md round 3:
@@ -103,6 +107,8 @@ RS16_PROG(DEC_LAST, LD_DEC_LAST, false, false, true, ST_RESTORE)
 RS16_PROG(DEC_SINGLE, LD_GATHER_DEC, true, true, true, ST_RESTORE)
 RS16_PROG(DEC_HALF_LAST, LD_PLAIN, false, false, true, ST_RESTORE)
 RS16_PROG(DEC_HALF_SINGLE, LD_GATHER_DEC, true, false, true, ST_RESTORE)
+RS16_PROG(DEC_LAST_ALL, LD_DEC_LAST, false, false, true, ST_RESTORE_ALL)
+RS16_PROG(DEC_SINGLE_ALL, LD_GATHER_DEC, true, true, true, ST_RESTORE_ALL)
 #undef RS16_PROG
 
 // Row bits in registers: 4 (16 rows per thread) from T = 6 on; 3 at T = 5
@@ -179,14 +185,14 @@ template <int P, int T, int QL> struct SmemL {
     // by then) in tab1 between its barriers.
     static constexpr bool RESTAGE = TWO && T > 4;
     static constexpr int TAB2_BYTES = TWO ? (RESTAGE ? Geo<T>::NTAB - Geo<T>::TSPLIT : Geo<T>::NTAB) * 80 : 0;
-    static constexpr int RVT_BYTES = PT::STORE == ST_RESTORE ? (1 << T) * 80 : 0;
-    static constexpr int LOST_BYTES = PT::STORE == ST_RESTORE ? (1 << T) * 4 : 0;
+    static constexpr int RVT_BYTES = st_restores(PT::STORE) ? (1 << T) * 80 : 0;
+    static constexpr int LOST_BYTES = st_restores(PT::STORE) ? (1 << T) * 4 : 0;
     static constexpr int TAB1_OFF = SHARED ? 0 : ERT_OFF + ERT_BYTES;
     static constexpr int TAB2_OFF = SHARED ? TABB_OFF + (Geo<T>::NTAB - Geo<T>::TSPLIT) * 80 : TAB1_OFF + TAB1_BYTES;
     static constexpr int RVT_OFF = TAB2_OFF + TAB2_BYTES;
     static constexpr int LOST_OFF = RVT_OFF + RVT_BYTES;
     // erasure logs of the tile's rows when the pass finishes eval_poly (ework)
-    static constexpr int ELOG_BYTES = (PT::LOAD == LD_GATHER_DEC || PT::STORE == ST_RESTORE) ? 256 * 4 : 0;
+    static constexpr int ELOG_BYTES = (PT::LOAD == LD_GATHER_DEC || st_restores(PT::STORE)) ? 256 * 4 : 0;
     static constexpr int ELOG_OFF = LOST_OFF + LOST_BYTES;
     static constexpr int BYTES = ELOG_OFF + ELOG_BYTES;
 };
@@ -654,13 +660,14 @@ template <int T> struct TwiddleEntry {
 //
 // REVEAL ERASURES (rate_high.rs:236-242 / rate_low.rs:236-242): lost
 // original row r -> work[r] * (GF_MODULUS - e[r]).
-template <int T> struct RevealEntry {
+// (ALL: the repair's programs reveal the lost rows of both segments, row_wanted)
+template <int T, bool ALL = false> struct RevealEntry {
     const PassArgs& a;
     const Thr& c;
     const uint32_t* el;
     __device__ __forceinline__ uint32_t operator()(int k) const {
         const uint32_t r = row_rel<T>(c, a, (uint32_t)k) + a.row_base_out;
-        return row_lost_original(a, r) ? GF_MODULUS - (el ? el[k] : a.elog[r]) : ZERO_ENTRY;
+        return row_wanted<ALL>(a, r) ? GF_MODULUS - (el ? el[k] : a.elog[r]) : ZERO_ENTRY;
     }
 };
 
@@ -1339,19 +1346,20 @@ __device__ __forceinline__ void load_item(const PassArgs& a, const Thr& c, uint3
 // the tile; programs with a last layout switch stage them there
 // (LateReveal), off the load phase -- they are read only by the stores.
 template <int P, int T> struct LateReveal {
-    static constexpr bool value = ProgTraits<P>::STORE == ST_RESTORE && ProgTraits<P>::FFT && T > 4;
+    static constexpr bool value = st_restores(ProgTraits<P>::STORE) && ProgTraits<P>::FFT && T > 4;
 };
 template <int P, int T> struct RevealStage {
     using SM = Smem<P, T>;
     using G = Geo<T>;
+    static constexpr bool ALL = ProgTraits<P>::STORE == ST_RESTORE_ALL;
     Stager<T, (1 << T)> sr;
     uint32_t lost[((1 << T) + G::THREADS - 1) / G::THREADS];
     __device__ __forceinline__ void issue(const PassArgs& a, const Thr& c, const uint32_t* el) {
-        sr.issue(a.mul_tab, RevealEntry<T>{a, c, el});
+        sr.issue(a.mul_tab, RevealEntry<T, ALL>{a, c, el});
 #pragma unroll
         for (int i = 0; i < (int)(sizeof lost / sizeof lost[0]); i++) {
             const uint32_t k = threadIdx.x + i * G::THREADS;
-            lost[i] = k < (1u << T) && row_lost_original(a, row_rel<T>(c, a, k) + a.row_base_out);
+            lost[i] = k < (1u << T) && row_wanted<ALL>(a, row_rel<T>(c, a, k) + a.row_base_out);
         }
     }
     __device__ __forceinline__ void commit(uint8_t* smem) const {
@@ -1383,7 +1391,7 @@ template <int P, int T> struct TileStage {
     // workgroup the layout-A ones (s1).
     static constexpr bool WS = WaveStaged<P, T>::value;
     static constexpr bool WS_A = WS && PT::IFFT, WS_B = WS && !PT::IFFT;
-    static_assert(!WS || (T > 4 && G::R == 4 && PT::LOAD != LD_GATHER_DEC && PT::STORE != ST_RESTORE),
+    static_assert(!WS || (T > 4 && G::R == 4 && PT::LOAD != LD_GATHER_DEC && !st_restores(PT::STORE)),
                   "wave-private staging: 16-row sets, twiddle tables only");
     static constexpr int N1 = WS_A ? 0 : (SM::SHARED || WS_B ? G::TSPLIT : G::NTAB);
     static constexpr int N1B = SM::SHARED || WS_A ? G::NTAB - G::TSPLIT : 0;
@@ -1493,7 +1501,7 @@ template <int P, int T> struct TileStage {
     __device__ __forceinline__ void finish(const PassArgs& a, const Thr& c, uint8_t* smem) {
         if constexpr (!GATHERED) gather(a, c, smem);
         if constexpr (PT::LOAD == LD_GATHER_DEC) se.commit((uint4*)(smem + SM::ERT_OFF));
-        if constexpr (PT::STORE == ST_RESTORE && !LateReveal<P, T>::value) {
+        if constexpr (st_restores(PT::STORE) && !LateReveal<P, T>::value) {
             RevealStage<P, T> rs;
             rs.issue(a, c, el);
             rs.commit(smem);
@@ -1559,6 +1567,26 @@ template <int P, int T> struct RcvCount {
     }
 };
 
+// ST_RESTORE_ALL (the repair's programs): where work row rw + lr of a lane is
+// stored -- the row's own segment's array, rest + r S_rest below `chunk`,
+// rest_b + (r - chunk) S_rest from there on.  rw: the wave's row of the row
+// register, lr: the lane's rows below it, lo: the lane's byte offset.  With
+// 32-bit lane offsets the base is one scalar choice by the wave's row: voff32
+// is set only when chunk % 2^(T + lo) == 0 (pass_launch_consts, `aligned`), so
+// every row of the tile lies on the wave's side of `chunk`.  Else the lane's
+// own row chooses (3000:5 at 2^6-row tiles: chunk = 8 lies inside tile 0).
+template <bool V32>
+__device__ __forceinline__ gbyte* restore_all_ptr(const PassArgs& a, const Thr& cs, uint32_t rw, uint32_t lr,
+                                                  const LaneOff<V32>& lo) {
+    if constexpr (V32) {
+        return lo.at(sgpr_ptr(rw >= a.chunk ? a.rest_b + (uint64_t)(rw - a.chunk) * a.S_rest
+                                            : a.rest + (uint64_t)rw * a.S_rest));
+    } else {
+        const uint32_t r = rw + lr;
+        return (gbyte*)((r >= a.chunk ? a.rest_b + (uint64_t)(r - a.chunk) * a.S_rest : a.rest + (uint64_t)r * a.S_rest) +
+                        cs.offL);
+    }
+}
 // The store of row register m of an item (the counterpart of load_rows): recovery / work rows as they are, lost originals revealed
 // (x (65535 - e), rate_high.rs:236-242) into the caller's original array.
 template <int P, int T, bool V32>
@@ -1591,7 +1619,11 @@ __device__ __forceinline__ void store_row(const PassArgs& a, const Thr& cs, uint
             load_table_lds(tt, rvt + k * 5);
             uint32_t ol = 0, oh = 0;
             mul_xor(ol, oh, L, H, tt);
-            st_ptr<NT>(lo.at(sgpr_ptr(a.rest + ((int64_t)ur + shift) * (int64_t)a.S_rest)), true, ol, oh);
+            if constexpr (PT::STORE == ST_RESTORE_ALL) {
+                st_ptr<NT>(restore_all_ptr<V32>(a, cs, ur + a.row_base_out, lr, lo), true, ol, oh);
+            } else {
+                st_ptr<NT>(lo.at(sgpr_ptr(a.rest + ((int64_t)ur + shift) * (int64_t)a.S_rest)), true, ol, oh);
+            }
         }
     }
 }
@@ -1752,7 +1784,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
     constexpr bool ZERO_SKIP = P == DEC_MID && T > 4 && G::R == 4;
     // stores inside the last FFT block (16 rows per lane, not the
     // output-pruned DEC_MID; the reveal stores measured slower inside it)
-    constexpr bool EARLY = LayerSeq<T, false, 0, R, true>::DF && P != DEC_MID && PT::STORE != ST_RESTORE && PT::FFT &&
+    constexpr bool EARLY = LayerSeq<T, false, 0, R, true>::DF && P != DEC_MID && !st_restores(PT::STORE) && PT::FFT &&
                            T > 4;
     // the IFFT-only passes: early stores of the even rows (ifft_b_halves;
     // against all stores after the last block: profiles/r05_early_b_ab.txt)
@@ -1939,7 +1971,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
         }
         bool need = true;
         if constexpr (P == DEC_MID) need = (c.s << R) < a.need_hi && ((c.s + 1) << R) > a.need_lo;
-        if constexpr (PT::STORE == ST_RESTORE && T > 4) {
+        if constexpr (st_restores(PT::STORE) && T > 4) {
             // a row set without a lost original stores nothing: its
             // layout-A FFT layers are skipped (a wave whose two row sets
             // both have none skips them -- most waves of a decode that lost

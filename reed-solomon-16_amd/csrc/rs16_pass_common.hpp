@@ -64,6 +64,7 @@ PassFn pass_kernels_paired(int prog, int T, int nv);   // rs16_pass_enc.hip: the
 PassKernel pass_kernels_dec(int prog, int T, int nv);  // rs16_pass_dec.hip: DEC_*
 PassFn pass_kernels_tower(int prog, int T, int nv);    // rs16_pass_tower.hip: the tower flavours (nullptr: none)
 PassFn pass_kernel_tower_wide3(int prog, int T);       // rs16_pass_tower.hip: PassKernel::wide3 (nullptr: none)
+PassKernel pass_kernels_repair(int prog, int T);       // rs16_pass_repair.hip: DEC_LAST_ALL, DEC_SINGLE_ALL (no narrow variants)
 
 #if defined(__HIPCC__) || defined(__HIP__)
 // ---------------------------------------------------------------------------
@@ -100,6 +101,7 @@ __device__ __forceinline__ void stripe_displace(PassArgs& a, uint32_t st) {
     a.seg_a += st * a.bs_seg;
     a.seg_b += st * a.bs_seg_b;
     a.rest += st * a.bs_rest;
+    a.rest_b += st * a.bs_rest_b;
     if (a.flags_a) a.flags_a += st * a.bs_fa;
     if (a.flags_b) a.flags_b += st * a.bs_fb;
     if (a.elog) a.elog += st * a.bs_elog;
@@ -146,6 +148,13 @@ __device__ __forceinline__ bool row_lost_original(const PassArgs& a, uint32_t r)
     const uint32_t cnt = a.rest_seg_b ? a.b_count : a.a_count;
     const uint8_t* fl = a.rest_seg_b ? a.flags_b : a.flags_a;
     return r >= base && r - base < cnt && fl && !fl[r - base];
+}
+// A row the pass reveals and stores: a lost original, or (ALL, the repair's
+// programs) a row of either segment without a received flag.
+template <bool ALL> __device__ __forceinline__ bool row_wanted(const PassArgs& a, uint32_t r) {
+    if constexpr (!ALL) return row_lost_original(a, r);
+    if (r < a.a_count) return a.flags_a && !a.flags_a[r];
+    return r >= a.chunk && r - a.chunk < a.b_count && a.flags_b && !a.flags_b[r - a.chunk];
 }
 #endif
 

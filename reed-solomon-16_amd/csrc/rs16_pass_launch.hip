@@ -25,7 +25,21 @@ struct KernelTable {
                 }
     }
 };
+// The repair's programs (ids behind the profiling ids; rs16_pass_repair.hip):
+// one kernel per (prog, T), no narrow variants, no late-rows flavours.
+struct RepairTable {
+    PassKernel k[2][9], none{};
+    RepairTable() {
+        static_assert(DEC_SINGLE_ALL == DEC_LAST_ALL + 1, "the table's rows");
+        for (int p = 0; p < 2; p++)
+            for (int T = 0; T <= 8; T++) k[p][T] = pass_kernels_repair(DEC_LAST_ALL + p, T);
+    }
+};
 static const PassKernel& find_kernel(int prog, int T, int nv) {
+    if (repair_prog(prog)) {
+        static const RepairTable repair;
+        return nv == 0 ? repair.k[prog - DEC_LAST_ALL][T] : repair.none;
+    }
     static const KernelTable table;
     return table.k[prog][T][nv];
 }
@@ -128,7 +142,8 @@ ZForm z_form_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t
 }
 
 hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles, hipStream_t s) {
-    if (prog < 0 || prog >= NUM_PROGS || T < 0 || T > 8) return hipErrorInvalidValue;
+    if (prog < 0 || (prog >= NUM_PROGS && !repair_prog(prog)) || T < 0 || T > 8) return hipErrorInvalidValue;
+    if (repair_prog(prog) && !find_kernel(prog, T, 0).fn) return hipErrorInvalidValue;  // (DEC_LAST_ALL: T >= 4, DEC_SINGLE_ALL: T >= 1)
     if (num_tiles == 0 || args.qrow == 0) return hipSuccess;
     PassArgs a = args;
     // Narrow twiddles: the launch's tiles are tile_base + [0, tiles of one

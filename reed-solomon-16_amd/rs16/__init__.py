@@ -31,6 +31,7 @@ __all__ = [
     "DIAG_FORCE_VOFF64", "DIAG_EVAL_TWO_KERNEL", "DIAG_EVAL_FULL", "DIAG_NO_COLUMN", "DIAG_FORCE_COLUMN",
     "DIAG_TILE_LAST", "DIAG_NO_TILE_LAST", "DIAG_FD_LDS", "DIAG_COL_RADIX4", "DIAG_NO_IDENTITY", "DIAG_NO_MID_DIRECT", "DIAG_WIDE_TWIDDLES", "DIAG_NO_LATE_ROWS", "DIAG_NO_PAIRED_ROWS", "DIAG_NO_TOWER_ROWS", "encode_host", "decode_host",
     "encode_host_batch", "decode_host_batch", "decode_prepare", "decode_device_prepared",
+    "repair_device", "repair_device_batch", "repair_path",
     "UpdatePlan", "update_recovery_device", "UPDATE_MAX_SHARDS",
     "encode_host_multi", "decode_host_multi", "Comm", "column_slice", "scatter_columns", "gather_columns",
 ]
@@ -697,6 +698,45 @@ def decode_device(original_count, recovery_count, shard_bytes, d_original, d_ori
                                     recovery_received_count, stream, C.byref(err)), err)
     if check:
         _check(lib().rs16_decode_check(eng.h, stream, C.byref(err)), err)
+
+
+def repair_device(original_count, recovery_count, shard_bytes, d_original, d_original_received, d_recovery,
+                  d_recovery_received, original_received_count, recovery_received_count, stream=None,
+                  engine: Optional[Engine] = None, check: bool = False):
+    """rs16_repair_device: decode_device with d_recovery writable -- lost
+    originals restored and lost recovery shards regenerated, both in place;
+    received slots are not written.  check=True: rs16_decode_check afterwards."""
+    eng = engine or default_engine()
+    err = RS16Error()
+    _check(lib().rs16_repair_device(eng.h, original_count, recovery_count, shard_bytes, Engine._ptr(d_original),
+                                    Engine._ptr(d_original_received), Engine._ptr(d_recovery),
+                                    Engine._ptr(d_recovery_received), original_received_count,
+                                    recovery_received_count, stream, C.byref(err)), err)
+    if check:
+        _check(lib().rs16_decode_check(eng.h, stream, C.byref(err)), err)
+
+
+def repair_device_batch(original_count, recovery_count, shard_bytes, nstripes, d_original, original_stride,
+                        d_original_received, d_recovery, recovery_stride, d_recovery_received,
+                        original_received_count, recovery_received_count, stream=None,
+                        engine: Optional[Engine] = None):
+    """rs16_repair_device_batch: nstripes stripes with one shared erasure pattern."""
+    eng = engine or default_engine()
+    err = RS16Error()
+    _check(lib().rs16_repair_device_batch(eng.h, original_count, recovery_count, shard_bytes, nstripes,
+                                          Engine._ptr(d_original), original_stride, Engine._ptr(d_original_received),
+                                          Engine._ptr(d_recovery), recovery_stride, Engine._ptr(d_recovery_received),
+                                          original_received_count, recovery_received_count, stream, C.byref(err)), err)
+
+
+def repair_path(original_count, recovery_count, original_received_count, recovery_received_count):
+    """rs16_host_repair_path: (path, lo, first_tile, tiles) of a repair -- path 0
+    nothing to do, 1 the decode, 2 encode + copy, 3 the general repair, -1 the
+    call fails; host arithmetic, no device."""
+    lo, t0, nt = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    p = lib().rs16_host_repair_path(original_count, recovery_count, original_received_count,
+                                    recovery_received_count, C.byref(lo), C.byref(t0), C.byref(nt))
+    return p, lo.value, t0.value, nt.value
 
 
 def decode_prepare(original_count, recovery_count, shard_bytes, d_original_received, d_recovery_received,
