@@ -355,6 +355,83 @@ int rs16_repair_device_batch(rs16_engine* eng, size_t original_count, size_t rec
                              const uint8_t* d_original_received, void* d_recovery, size_t recovery_stride,
                              const uint8_t* d_recovery_received, size_t original_received_count,
                              size_t recovery_received_count, void* stream, rs16_error* err);
+/* Selective decode, the degraded read: rs16_decode_device restoring only the
+ * lost originals the caller asks for.  d_original_wanted is the read set, a
+ * device array of original_count bytes: a byte other than 0 means "wanted" (any
+ * nonzero value, as for the received flags).  The array needs no alignment, and
+ * no byte outside [0, original_count) is read as a flag.
+ *   - a lost original (flag 0) whose wanted byte is nonzero is restored in
+ *     place, bit-equal to what rs16_decode_device writes there;
+ *   - a lost original whose wanted byte is 0 is NOT written: its slot keeps
+ *     its bytes;
+ *   - wanted bytes of received originals are ignored; received slots are never
+ *     written; d_recovery is read only.
+ * wanted_count is the number of lost originals in the read set (rows with flag
+ * 0 and a nonzero wanted byte).  Like the received counts it comes from the
+ * host, MUST equal what the device arrays say, and selects the launches:
+ *   - 0: nothing is launched (RS16_OK), whatever the read set holds;
+ *   - original_count - original_received_count: the call IS the plain decode,
+ *     the read set is not read and every lost original is restored;
+ *   - values in between only steer two host gates (whether the direct middle
+ *     pass and the per-column last pass are launched beside the general ones).
+ *     The device decides by the row interval of the lost-and-wanted originals,
+ *     which it computes itself from the two arrays, and restores exactly the
+ *     rows the arrays name: a wrong value in this range costs time, not
+ *     correctness.  rs16_decode_check does not verify it.
+ * The erasure locator still comes from ALL erasures -- only the row interval
+ * that prunes the passes, the reveal and the stores follow the read set.
+ * Rate selection, the 64-byte alignment of the shard arrays, asynchrony on
+ * `stream`, the ordering on the engine's scratch, the discard of a pending
+ * rs16_decode_prepare and rs16_decode_check afterwards are those of
+ * rs16_decode_device.
+ * Errors, in this order: UnsupportedShardCount / InvalidShardSize as
+ * rs16_validate gives them; InvalidArgument for a NULL or misaligned shard
+ * array, a NULL flag or wanted array and, in the batch form, a bad stride;
+ * InvalidArgument for a count above its shard count or wanted_count above
+ * original_count - original_received_count; NotEnoughShards (with the decode's
+ * payload) for fewer than original_count received.  Then: everything received
+ * or wanted_count == 0 gives RS16_OK with nothing launched.
+ * Paths (rs16_host_select_path): 1 = rs16_decode_device itself, every form of
+ * it; 2 = the selective decode -- never the half-transform or identity decode
+ * (they store every original), one launch of the column codec up to 2048 work
+ * rows, else eval_poly and the general decode's passes with the middle pass
+ * as a direct product and the last pass on the wanted rows' tiles only.
+ * Column slices (rs16_engine_set_slices) apply to path 1 only.
+ * When to prefer it (measured on one MI355X at 1 KiB shards with every recovery
+ * shard received, DESIGN.md 3.17, profiles/r17_select.txt; the other candidate
+ * is rs16_decode_device on the same stripe and pattern): when the rows wanted
+ * lie in few 256-row tiles of a large stripe that has received originals.  At
+ * 32768:32768 one row read out of a 1 % loss scattered over every tile takes
+ * 90.4 us against the decode's 148.5 (0.61 x; the select's median burst lies
+ * below the decode's fastest), out of a random 50 % loss 87.9 against 146.9, 16
+ * rows of one tile 89.1 against 146.6.  What remains is the locator, the gather
+ * and the first transform of every received row, which no read set shortens.
+ * It does NOT win where the read set is spread over every tile -- every second
+ * lost row: 147.9 against 148.8 and 145.8 against 147.4 us, the decode's cost --
+ * and it LOSES where every original is lost: the plain call then takes the
+ * half-transform / identity decode, which stores every original and which a
+ * selective call cannot take, 62.1 against 56.6 us for one row and 107.8
+ * against 56.5 for every second row at 32768:32768, 13.2-14.6 against 11.1 at
+ * 1000:1000.  There, decode into a scratch array if the other slots must keep
+ * their bytes.  At 1000:1000 with received originals the call is one launch
+ * either way and there is little to prune: 17.6-19.5 against 19.1-19.7 us.
+ * Sizes in between are not measured. */
+int rs16_decode_device_select(rs16_engine* eng, size_t original_count, size_t recovery_count, size_t shard_bytes,
+                              void* d_original, const uint8_t* d_original_received,
+                              const uint8_t* d_original_wanted, const void* d_recovery,
+                              const uint8_t* d_recovery_received, size_t original_received_count,
+                              size_t recovery_received_count, size_t wanted_count, void* stream, rs16_error* err);
+/* rs16_decode_device_select for `nstripes` stripes that lost the same shards
+ * and are read at the same indices: one shared pattern and one shared read
+ * set, arrays and strides as for rs16_decode_device_batch.  Every stripe's
+ * result equals rs16_decode_device_select on it alone. */
+int rs16_decode_device_select_batch(rs16_engine* eng, size_t original_count, size_t recovery_count,
+                                    size_t shard_bytes, size_t nstripes, void* d_original, size_t original_stride,
+                                    const uint8_t* d_original_received, const uint8_t* d_original_wanted,
+                                    const void* d_recovery, size_t recovery_stride,
+                                    const uint8_t* d_recovery_received, size_t original_received_count,
+                                    size_t recovery_received_count, size_t wanted_count, void* stream,
+                                    rs16_error* err);
 /* Checked mode of the engine's last decode: waits for `stream` and compares
  * the received counts that decode was given with the rows the device flags
  * mark received (the eval_poly kernels count them per 64-row chunk as they
@@ -599,7 +676,7 @@ void rs16_host_free(rs16_engine* eng, void* h_ptr);
  * rs16_engine_profile_read synchronizes and returns, for pass program
  * `prog` (0 .. rs16_prog_count()-1, named by rs16_prog_name: the pass programs,
  * then the ids of kernel groups such as EVAL_POLY, COL_ENC or REPAIR_COPY; new
- * ids are appended, so look an id up by its name), the summed
+ * ids are added and an id's value may move, so look an id up by its name), the summed
  * milliseconds and the number of launches since the last reset. */
 int rs16_engine_set_profiling(rs16_engine* eng, int enable, rs16_error* err);
 int rs16_engine_profile_read(rs16_engine* eng, int prog, double* total_ms, uint64_t* launches, rs16_error* err);
@@ -797,6 +874,14 @@ int rs16_host_update_consts(uint32_t rows, uint64_t shard_bytes, uint32_t n, uin
  * the low rate; chunk = a_count rounded up to a power of two.) */
 int rs16_host_repair_path(size_t original_count, size_t recovery_count, size_t original_received_count,
                           size_t recovery_received_count, uint32_t* lo, uint32_t* first_tile, uint32_t* tiles);
+/* The path rs16_decode_device_select takes, as the entry points decide it (one
+ * host function; no device needed): 0 nothing to do (every original received,
+ * or wanted_count == 0), 1 = rs16_decode_device (the read set covers every lost
+ * original), 2 = the selective decode; -1 where the call fails (unsupported
+ * counts, a count above its shard count, wanted_count above the lost
+ * originals' count, fewer than original_count received). */
+int rs16_host_select_path(size_t original_count, size_t recovery_count, size_t original_received_count,
+                          size_t recovery_received_count, size_t wanted_count);
 
 /* Library/build identification, e.g. "rs16-mi355x gfx950". */
 const char* rs16_version(void);

@@ -313,6 +313,7 @@ extern "C" const char* rs16_prog_name(int prog) {
                                   "DEC_LAST",  "DEC_SINGLE", "DEC_HALF_LAST", "DEC_HALF_SINGLE",
                                   "DEC_HALF_FIRST", "DEC_HALF_MID", "EVAL_POLY", "COL_ENC", "COL_DEC",
                                   "DEC_MID_DIRECT", "DEC_TILE_LAST",
+                                  "DEC_LAST_SEL", "DEC_SINGLE_SEL", "DEC_TILE_LAST_SEL", "COL_DEC_SEL",
                                   "DEC_LAST_ALL", "DEC_SINGLE_ALL", "REPAIR_COPY"};
     static_assert(sizeof names / sizeof names[0] == NUM_PROF, "profiling names");
     return (prog >= 0 && prog < NUM_PROF) ? names[prog] : "?";

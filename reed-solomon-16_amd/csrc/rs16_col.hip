@@ -408,7 +408,8 @@ __device__ __forceinline__ void col_fd(uint32_t (&XL)[4], uint32_t (&XH)[4], uin
 
 template <int L, int MODE>
 __global__ __launch_bounds__((1 << L) / 4) void col_kernel(ColArgs a) {
-    constexpr bool DEC = MODE != COL_ENC, GEN = MODE == COL_DEC_GEN;
+    // (SEL: the general decode restoring the read set only, a.wanted)
+    constexpr bool DEC = MODE != COL_ENC, SEL = MODE == COL_DEC_GEN_SEL, GEN = MODE == COL_DEC_GEN || SEL;
     constexpr bool EVAL = MODE == COL_DEC_EVAL || GEN;  // the polynomial in the kernel
     constexpr int N = 1 << L, NT = N / 4;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -444,6 +445,7 @@ __global__ __launch_bounds__((1 << L) / 4) void col_kernel(ColArgs a) {
     // start as soon as they land (a wait for them would otherwise include
     // every DMA issued before them; vmcnt counts in issue order)
     [[maybe_unused]] uint8_t fr[4] = {0, 0, 0, 0};
+    [[maybe_unused]] uint8_t wn[4] = {0, 0, 0, 0};  // (SEL: the read set's bytes of the thread's originals)
     [[maybe_unused]] ColEval<L, (DEC && EVAL) ? (GEN ? 4 : 8) : 1> ce;
     [[maybe_unused]] uint32_t zv[2][4];
     if constexpr (DEC) {
@@ -454,6 +456,11 @@ __global__ __launch_bounds__((1 << L) / 4) void col_kernel(ColArgs a) {
             const bool in_a = r < a.in_rows, in_b = GEN && r >= a.chunk && r - a.chunk < a.o_rows;
             const uint8_t* fp = in_a && a.flags ? a.flags + r : (in_b && a.flags_o ? a.flags_o + (r - a.chunk) : a.zero);
             fr[m] = *(const __attribute__((address_space(1))) uint8_t*)fp;
+            if constexpr (SEL) {
+                // (a row of the originals' segment reads its wanted byte, any other row a zero byte)
+                const uint8_t* wp = a.rev_a ? (in_a ? a.wanted + r : a.zero) : (in_b ? a.wanted + (r - a.chunk) : a.zero);
+                wn[m] = *(const __attribute__((address_space(1))) uint8_t*)wp;
+            }
         }
         if constexpr (EVAL) {
             ce.load(a);
@@ -505,6 +512,7 @@ __global__ __launch_bounds__((1 << L) / 4) void col_kernel(ColArgs a) {
                 rcv[m] = !a.flags_o || fr[m] != 0;
                 if (!a.rev_a) lost[m] = !rcv[m];
             }
+            if constexpr (SEL) lost[m] = lost[m] && wn[m] != 0;  // (lost and wanted)
         }
         uint32_t* elds = (uint32_t*)(smem + ColSmem<L>::ELOG);
         if constexpr (EVAL) {
@@ -865,9 +873,10 @@ __device__ __forceinline__ void col2_fd(uint32_t (&XL)[2], uint32_t (&XH)[2], ui
 
 template <int L, int MODE>
 __global__ __launch_bounds__((1 << L) / 2) void col2_kernel(ColArgs a) {
-    static_assert(L >= 8 && L <= 11 && (L <= 10 || MODE == COL_DEC_GEN) && MODE != COL_DEC_EWORK,
-                  "radix-2 column codec");
-    constexpr bool DEC = MODE == COL_DEC_EVAL || MODE == COL_DEC_GEN, GEN = MODE == COL_DEC_GEN;
+    // (SEL: the general decode restoring the read set only, a.wanted)
+    constexpr bool SEL = MODE == COL_DEC_GEN_SEL, GEN = MODE == COL_DEC_GEN || SEL;
+    static_assert(L >= 8 && L <= 11 && (L <= 10 || GEN) && MODE != COL_DEC_EWORK, "radix-2 column codec");
+    constexpr bool DEC = MODE == COL_DEC_EVAL || GEN;
     // the high rate's multi-chunk encode in two launches: IFO = the IFFT of
     // chunk blockIdx.y of originals, stored whole; FFX = the FFT of the XOR
     // of a.nch such chunks (launch_col, rs16_engine::encode_high_multi)
@@ -921,6 +930,7 @@ __global__ __launch_bounds__((1 << L) / 2) void col2_kernel(ColArgs a) {
     // ---- requests, as col_kernel: the decoder's flags and polynomial
     // inputs first, then the layer-0/1 tables into registers, the rows, the DMA
     [[maybe_unused]] uint8_t fr[2] = {0, 0};
+    [[maybe_unused]] uint8_t wn[2] = {0, 0};  // (SEL: the read set's bytes of the thread's originals)
     // (XP: the eval's wave layers as lane layers; the 16-term wave layers of
     // fwht_points measured slower at 16 waves, profiles/r05_col_gen_prune.txt)
     [[maybe_unused]] ColEval<L, (DEC ? (GEN ? N : 2 * N) / NT : 1), NT, true> ce;
@@ -931,6 +941,12 @@ __global__ __launch_bounds__((1 << L) / 2) void col2_kernel(ColArgs a) {
             const uint8_t* fp = in_a(r) && a.flags ? a.flags + r
                                                    : (in_b(r) && a.flags_o ? a.flags_o + (r - a.chunk) : a.zero);
             fr[m] = *(const __attribute__((address_space(1))) uint8_t*)fp;
+            if constexpr (SEL) {
+                // (a row of the originals' segment reads its wanted byte, any other row a zero byte)
+                const uint8_t* wp = a.rev_a ? (in_a(r) ? a.wanted + r : a.zero)
+                                            : (in_b(r) ? a.wanted + (r - a.chunk) : a.zero);
+                wn[m] = *(const __attribute__((address_space(1))) uint8_t*)wp;
+            }
         }
         ce.load(a);
     }
@@ -1006,6 +1022,7 @@ __global__ __launch_bounds__((1 << L) / 2) void col2_kernel(ColArgs a) {
                 rcv[m] = !a.flags_o || fr[m] != 0;
                 if (!a.rev_a) lost[m] = !rcv[m];
             }
+            if constexpr (SEL) lost[m] = lost[m] && wn[m] != 0;  // (lost and wanted)
         }
         if constexpr (GEN) {
             ilive = __ballot(rcv[0] || rcv[1]) != 0;
@@ -1434,10 +1451,12 @@ hipError_t launch_col_multi(const ColArgs& a, bool high, hipStream_t s) {
 }
 
 hipError_t launch_col(const ColArgs& a, uint32_t L, int mode, hipStream_t s) {
-    if (L < COL_LMIN || L > COL_LGEN || mode < COL_ENC || mode > COL_ENC_FFTX) return hipErrorInvalidValue;
-    if (L == COL_LGEN && mode != COL_DEC_GEN) return hipErrorInvalidValue;
+    if (L < COL_LMIN || L > COL_LGEN || mode < COL_ENC || mode > COL_DEC_GEN_SEL) return hipErrorInvalidValue;
+    const bool sel = mode == COL_DEC_GEN_SEL;
+    if (L == COL_LGEN && mode != COL_DEC_GEN && !sel) return hipErrorInvalidValue;
+    if (sel && (!a.wanted || a.nch > 1)) return hipErrorInvalidValue;  // (the read set is dereferenced)
     // multi-chunk encodes: radix-2 form, one stripe, nch <= COL_MAX_CHUNKS
-    const bool chunks = mode >= COL_ENC_IFFT || a.nch > 1;
+    const bool chunks = !sel && (mode >= COL_ENC_IFFT || a.nch > 1);
     if (chunks && (L < COL_LCHUNK || L > COL_LMAX || a.nstripes != 1 || a.nch == 0 || a.nch > COL_MAX_CHUNKS ||
                    (mode != COL_ENC && mode < COL_ENC_IFFT)))
         return hipErrorInvalidValue;
@@ -1451,7 +1470,11 @@ hipError_t launch_col(const ColArgs& a, uint32_t L, int mode, hipStream_t s) {
 #undef RS16_COL_ROW
     static const int lds[6] = {ColSmem<6>::BYTES, ColSmem<7>::BYTES,  ColSmem<8>::BYTES,
                                ColSmem<9>::BYTES, ColSmem<10>::BYTES, ColSmem<11>::BYTES};
-    ColFn fn = mode <= COL_DEC_GEN ? fns[L - COL_LMIN][mode] : nullptr;
+    // (COL_DEC_GEN_SEL: the same geometry and LDS as COL_DEC_GEN, kernels of its own)
+    static const ColFn fns_sel[6] = {col_kernel<6, COL_DEC_GEN_SEL>, col_kernel<7, COL_DEC_GEN_SEL>,
+                                     col_kernel<8, COL_DEC_GEN_SEL>, col_kernel<9, COL_DEC_GEN_SEL>,
+                                     col_kernel<10, COL_DEC_GEN_SEL>, col_kernel<11, COL_DEC_GEN_SEL>};
+    ColFn fn = sel ? fns_sel[L - COL_LMIN] : (mode <= COL_DEC_GEN ? fns[L - COL_LMIN][mode] : nullptr);
     if (!fn && !chunks) return hipErrorInvalidValue;  // (the ework decoder needs 4 waves: L >= 9)
     uint32_t threads = (1u << L) / 4, rows = 1;
     if (chunks) {
@@ -1469,7 +1492,9 @@ hipError_t launch_col(const ColArgs& a, uint32_t L, int mode, hipStream_t s) {
             {col2_kernel<9, COL_ENC>, col2_kernel<9, COL_DEC_EVAL>, col2_kernel<9, COL_DEC_GEN>},
             {col2_kernel<10, COL_ENC>, col2_kernel<10, COL_DEC_EVAL>, col2_kernel<10, COL_DEC_GEN>},
             {nullptr, nullptr, col2_kernel<11, COL_DEC_GEN>}};
-        fn = fns2[L - 8][mode == COL_ENC ? 0 : (mode == COL_DEC_EVAL ? 1 : 2)];
+        static const ColFn fns2_sel[4] = {col2_kernel<8, COL_DEC_GEN_SEL>, col2_kernel<9, COL_DEC_GEN_SEL>,
+                                          col2_kernel<10, COL_DEC_GEN_SEL>, col2_kernel<11, COL_DEC_GEN_SEL>};
+        fn = sel ? fns2_sel[L - 8] : fns2[L - 8][mode == COL_ENC ? 0 : (mode == COL_DEC_EVAL ? 1 : 2)];
         threads = (1u << L) / 2;
     }
     int bytes = lds[L - COL_LMIN];

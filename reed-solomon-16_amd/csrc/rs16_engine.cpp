@@ -285,7 +285,8 @@ int rs16_engine::col_tables(hipStream_t s, rs16_error* err) {
 }
 
 int rs16_engine::col(const ColArgs& args, int L, int mode, hipStream_t s, rs16_error* err) {
-    const bool dec = mode == COL_DEC_EWORK || mode == COL_DEC_EVAL || mode == COL_DEC_GEN;
+    const bool sel = mode == COL_DEC_GEN_SEL;
+    const bool dec = mode == COL_DEC_EWORK || mode == COL_DEC_EVAL || mode == COL_DEC_GEN || sel;
     if (int rc = col_tables(s, err)) return rc;
     // the table images of the two transforms (skew deltas 0 / 2^L; the
     // kernel adds the chunk index of a multi-chunk encode to the delta)
@@ -297,8 +298,8 @@ int rs16_engine::col(const ColArgs& args, int L, int mode, hipStream_t s, rs16_e
     a.img_ifft = (const uint8_t*)(d_col_img + col_img_offset((uint32_t)L, a.skew_ifft ? 1 : 0));
     a.img_fft = (const uint8_t*)(d_col_img + col_img_offset((uint32_t)L, a.skew_fft ? 1 : 0));
     if (mode == COL_DEC_EVAL) a.vtab = d_col_v + col_v_offset(2u << L);  // (2^(L+1) work rows)
-    if (mode == COL_DEC_GEN) a.vtab = d_col_v + col_v_offset(1u << L);   // (2^L work rows)
-    return profiled(dec ? PROF_COL_DEC : PROF_COL_ENC, s, err, [&](uint64_t* stamps) {
+    if (mode == COL_DEC_GEN || sel) a.vtab = d_col_v + col_v_offset(1u << L);  // (2^L work rows)
+    return profiled(sel ? PROF_COL_DEC_SEL : (dec ? PROF_COL_DEC : PROF_COL_ENC), s, err, [&](uint64_t* stamps) {
         if (stamps) a.stamps = stamps;
         return launch_col(a, (uint32_t)L, mode, s);
     });
@@ -502,6 +503,7 @@ int rs16_engine::decode_eval(const DecodeGeom& g, const uint8_t* flags_a, const 
     es.lostrange = prune ? (uint32_t*)evset->lost.p + 512 : nullptr;
     es.orig_b = g.high ? 1 : 0;
     es.lost_all = g.repair ? 1 : 0;  // (the repair stores the lost rows of both segments)
+    es.wanted = g.select ? g.wanted : nullptr;  // (the selective decode: the interval of the wanted rows)
     es.rcount = (uint32_t*)evset->rcount.p;
     es.diag = (uint32_t)diag;
     last_dec = g;
@@ -568,6 +570,7 @@ int rs16_engine::decode_eval(const DecodeGeom& g, const uint8_t* flags_a, const 
 // FFT -> reveal, with no formal derivative.
 bool rs16_engine::half_decode(const DecodeGeom& g) {
     if (g.repair) return false;  // (a lost recovery shard: the other half's input is not whole, DecodeGeom::repair)
+    if (g.select) return false;  // (the half pipelines store every original, DecodeGeom::select)
     const bool orig_lost = g.high ? g.b_recv == 0 : g.a_recv == 0;
     return orig_lost && g.n >= 2 && g.n == 2 * (size_t)g.chunk;
 }
@@ -779,10 +782,12 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
         c.rcount = rcount;
         c.bs_flags = var_bs_fa;
         c.bs_flags_o = var_bs_fb;
-        return col(c, L, COL_DEC_GEN, s, err);
+        c.wanted = g.select ? g.wanted : nullptr;  // (lost[] = lost and wanted; the polynomial follows the flags)
+        return col(c, L, g.select ? COL_DEC_GEN_SEL : COL_DEC_GEN, s, err);
     }
+    a.wanted = g.select ? g.wanted : nullptr;  // (read by the select programs alone)
     if (L <= 8) {
-        RS16_PASS(g.repair ? DEC_SINGLE_ALL : DEC_SINGLE, L, a, batch(1, 0, 0, 0), s);
+        RS16_PASS(g.repair ? DEC_SINGLE_ALL : (g.select ? DEC_SINGLE_SEL : DEC_SINGLE), L, a, batch(1, 0, 0, 0), s);
         return RS16_OK;
     }
     const int lo = L / 2, hi = L - lo;
@@ -841,7 +846,11 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
     a.out = U;
     a.need_lo = t0;
     a.need_hi = t1;
-    const size_t lost = g.high ? (size_t)g.b_count - g.b_recv : (size_t)g.a_count - g.a_recv;
+    // (the selective decode: the lost originals of the read set stand for the
+    // lost ones in both gates below; the device decides by lostrange, which the
+    // eval kernels took over the same rows)
+    const size_t lost = g.select ? g.wanted_count
+                                 : (g.high ? (size_t)g.b_count - g.b_recv : (size_t)g.a_count - g.a_recv);
     // Few lost originals: the middle pass's consumed rows may be few enough
     // for the direct product (mid_direct_kernel; DEC_MID then returns for
     // the stripes it covered -- decided on the device from lostrange)
@@ -882,16 +891,16 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
         // reads that tile from lostrange; a launch that returns at once costs
         // per workgroup)
         const uint32_t tiles = batch(std::min(t1 - t0, a.tl_max), zs, zs, 0);
-        if (int rc = profiled(PROF_DEC_TILE_LAST, s, err, [&](uint64_t* stamps) {
+        if (int rc = profiled(g.select ? PROF_DEC_TILE_LAST_SEL : PROF_DEC_TILE_LAST, s, err, [&](uint64_t* stamps) {
                 a.stamps = stamps;
-                const hipError_t e = launch_tile_last(a, tiles, s);
+                const hipError_t e = g.select ? launch_tile_last_sel(a, tiles, s) : launch_tile_last(a, tiles, s);
                 a.stamps = nullptr;
                 return e;
             }))
             return rc;
         if (diag & DIAG_TILE_LAST) return RS16_OK;  // (every span is tile_last's)
     }
-    RS16_PASS(DEC_LAST, lo, a, batch(t1 - t0, zs, zs, 0), s);
+    RS16_PASS(g.select ? DEC_LAST_SEL : DEC_LAST, lo, a, batch(t1 - t0, zs, zs, 0), s);
     return RS16_OK;
 }
 

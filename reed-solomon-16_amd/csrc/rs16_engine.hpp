@@ -67,6 +67,21 @@ struct DecodeGeom {
     // so the transform's input is not zero on a half even when every original
     // is lost), no column codec, no mid_direct / tile_last kernels.
     bool repair = false;
+    // The selective decode (rs16_decode_device_select, path 2): only the lost
+    // originals of the read set are restored -- `wanted`, a device array of one
+    // byte per original (nonzero: wanted), of which `wanted_count` are lost.
+    // No half-transform or identity decode: every original may be lost while
+    // only some are wanted, and those pipelines store every row below
+    // out_rows (their counts would qualify: the trap the repair documents for
+    // 3:5).  An all-lost stripe takes the general path, whose DEC_FIRST
+    // launches the received segment's tiles only; up to 2^11 work rows the
+    // column codec's COL_DEC_GEN_SEL.  The row interval that prunes the passes
+    // (lostrange) is taken over the wanted rows; the erasure locator comes from
+    // the received flags alone.  wanted_count stands for the lost count in the
+    // host's gates (mid_direct, tile_last).  One column slice.
+    bool select = false;
+    const uint8_t* wanted = nullptr;
+    size_t wanted_count = 0;
 };
 DecodeGeom decode_geom(bool high, size_t k, size_t m);
 // The last pass of the general repair (DEC_LAST_ALL, 2^lo-row tiles, lo = L / 2

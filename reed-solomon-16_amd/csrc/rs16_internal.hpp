@@ -147,16 +147,28 @@ enum ProfId : int {
     PROF_COL_DEC,  // one-launch codec: half-transform decode
     PROF_DEC_MID_DIRECT,  // the general decode's middle pass as a direct product (mid_direct_kernel)
     PROF_DEC_TILE_LAST,   // the general decode's last pass, one wave per quad column (tile_last_kernel)
-    // The repair's programs (rs16_repair_device; rs16_pass_repair.hip), appended
-    // so that every earlier id keeps its value.  The first two are pass
-    // programs with kernels (launch_pass takes them), the third is the copy
-    // kernel of the recovery-only path (rs16_repair_copy.hip).
+    // The selective decode's programs (rs16_decode_device_select; rs16_pass_select.hip),
+    // placed behind the decode's ids and in front of the repair's three, which
+    // stay the last ones (tests/test_repair_path.py reads them from the end of
+    // the list; ids are looked up by name, include/rs16.h).  The first two are
+    // pass programs with kernels (launch_pass takes them); the third is
+    // tile_last_kernel's select form, the fourth the column codec's
+    // COL_DEC_GEN_SEL.
+    DEC_LAST_SEL,         // u + L(z) -> FFT -> reveal the lost originals of the read set -> store them
+    DEC_SINGLE_SEL,       // gather*e -> IFFT -> formal derivative -> FFT -> reveal the read set -> store
+    PROF_DEC_TILE_LAST_SEL,  // DEC_LAST_SEL, one wave per quad column (tile_last_sel_kernel)
+    PROF_COL_DEC_SEL,     // one-launch codec: the general decode restoring the read set only
+    // The repair's programs (rs16_repair_device; rs16_pass_repair.hip), behind
+    // every other id.  The first two are pass programs with kernels
+    // (launch_pass takes them), the third is the copy kernel of the
+    // recovery-only path (rs16_repair_copy.hip).
     DEC_LAST_ALL,         // u + L(z) -> FFT -> reveal the lost rows of both segments -> store each to its array
     DEC_SINGLE_ALL,       // gather*e -> IFFT -> formal derivative -> FFT -> reveal both segments -> store
     PROF_REPAIR_COPY,     // rows of the re-encoded recovery whose flag is 0 -> the caller's recovery array
     NUM_PROF
 };
 constexpr bool repair_prog(int prog) { return prog == DEC_LAST_ALL || prog == DEC_SINGLE_ALL; }
+constexpr bool select_prog(int prog) { return prog == DEC_LAST_SEL || prog == DEC_SINGLE_SEL; }
 
 struct PassArgs {
     uint8_t* out;              // plain store base (row 0 of the transform)
@@ -297,6 +309,13 @@ struct PassArgs {
     // other program.
     uint8_t* rest_b;
     uint64_t bs_rest_b;
+    // The selective decode's programs (DEC_LAST_SEL / DEC_SINGLE_SEL,
+    // tile_last_sel_kernel) restore a lost original only when its byte of the
+    // read set is nonzero: wanted[i] belongs to original i = work row i + the
+    // originals' segment start (stripe s at + s bs_wanted bytes; the entry
+    // points share one read set among the stripes: 0).  Read by no other program.
+    const uint8_t* wanted;
+    uint64_t bs_wanted;
 };
 
 // n / d for any 32-bit n without a division or a branch: the high 64 bits of
@@ -366,6 +385,9 @@ struct ColArgs {
     uint32_t nch;               // launch_col_multi: chunks of 128 rows (one wave each); launch_col: chunks (ColMode)
     uint64_t* stamps;           // RS16_STAMPS builds: phase timeline (rs16_engine_set_stamps)
     uint32_t diag;              // the engine's diagnostic switches (DiagFlags; host side: launch_col)
+    // COL_DEC_GEN_SEL: the read set, one byte per original (nonzero: restore it
+    // when lost), shared by the stripes.  Read by no other mode.
+    const uint8_t* wanted;
 };
 int col_rows_ok(uint32_t L);  // L = log2(rows of the transform) the codec covers
 // COL_DEC_GEN: the general high-rate decode of a 2^L-row work buffer (any
@@ -376,7 +398,9 @@ int col_rows_ok(uint32_t L);  // L = log2(rows of the transform) the codec cover
 //   2^L) stored whole, then the FFT (skew 0) of the XOR of nch chunks
 // ColArgs::nch > 1 with COL_ENC / COL_ENC_IFFT: one grid row per chunk (COL_ENC:
 // the low rate's recovery chunks, FFT of chunk c at delta (c + 1) 2^L)
-enum ColMode : int { COL_ENC = 0, COL_DEC_EWORK, COL_DEC_EVAL, COL_DEC_GEN, COL_ENC_IFFT, COL_ENC_FFTX };
+// COL_DEC_GEN_SEL: COL_DEC_GEN restoring only the lost originals of the read
+// set (ColArgs::wanted); the erasure polynomial still follows the flags alone.
+enum ColMode : int { COL_ENC = 0, COL_DEC_EWORK, COL_DEC_EVAL, COL_DEC_GEN, COL_ENC_IFFT, COL_ENC_FFTX, COL_DEC_GEN_SEL };
 // the radix-2 multi-chunk encodes take at most this many chunks (more: passes)
 constexpr uint32_t COL_MAX_CHUNKS = 64;
 hipError_t launch_col(const ColArgs& a, uint32_t L, int mode, hipStream_t s);
@@ -442,6 +466,9 @@ ZForm z_form_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t
 // a.lostrange on the device; a.tl_max must not be 0 then), or from
 // a.tile_base when a.lostrange is null.
 hipError_t launch_tile_last(const PassArgs& a, uint32_t num_tiles, hipStream_t s);
+// The same for the selective decode (rs16_pass_select.hip, tile_last_sel_kernel):
+// a lost original is revealed and stored only when a.wanted says so.
+hipError_t launch_tile_last_sel(const PassArgs& a, uint32_t num_tiles, hipStream_t s);
 // The general decode's middle pass as a direct product (rs16_pass_small.hpp
 // mid_direct_kernel): U rows [need_lo, need_hi) of every tile column j from
 // the live Z rows and mtab (rs16_engine::mid_tables: 2^hi x 2^hi v_perm
@@ -514,6 +541,12 @@ struct ErasureSpec {           // builds the erasure vector of rate_{high,low}.r
     // 1 (the repair): lostpart / lostrange cover the rows of both segments
     // without a received flag, not the originals' alone.  Default 0.
     uint32_t lost_all;
+    // The read set of a selective decode (rs16_decode_device_select): one byte
+    // per original, nonzero = wanted.  Then lostpart / lostrange cover the
+    // originals that are lost and wanted; the erasure vector, rbits, zflags
+    // and rcount come from the received flags alone, as always.  Shared by
+    // the grid rows of a batch.  nullptr: every lost original counts.
+    const uint8_t* wanted;
     // Received rows per 64-row chunk of rows [0, n), by segment:
     // rcount[2 c] = rows of segment A, rcount[2 c + 1] = rows of segment B
     // (rs16_decode_check compares their sums with the caller's counts).

@@ -167,6 +167,12 @@ __device__ __forceinline__ bool orig_row(const ErasureSpec& e, uint32_t i) {
     if (e.lost_all) return i < e.a_count || (i >= e.chunk && i - e.chunk < e.b_count);
     return e.orig_b ? (i >= e.chunk && i - e.chunk < e.b_count) : i < e.a_count;
 }
+// Row i, a row of the originals' segment (orig_row without lost_all), is in the
+// read set (ErasureSpec::wanted; nullptr: every original is).  Call it for such
+// rows only: no byte outside the read set's [0, original count) is read.
+__device__ __forceinline__ bool wanted_row(const ErasureSpec& e, uint32_t i) {
+    return !e.wanted || ((cu8p)e.wanted)[i - (e.orig_b ? e.chunk : 0u)] != 0;
+}
 // First / one past the last lost-original row of block blk (rows base +
 // 64 j + bit of lmask[j]), ~0u / 0 if none, by lane 0 of the wave.
 __device__ __forceinline__ void lost_part_wave(const ErasureSpec& e, uint32_t blk, uint32_t base,
@@ -284,7 +290,7 @@ __global__ void __launch_bounds__(64) fwht_lo_flags_kernel(ErasureSpec e, uint32
         v[j] = erasure_at(e, i);
         const bool rcv = i < e.n && received_at(e, i);
         rmask[j] = __ballot(rcv);
-        lmask[j] = __ballot(i < e.n && orig_row(e, i) && !rcv);
+        lmask[j] = __ballot(i < e.n && orig_row(e, i) && !rcv && wanted_row(e, i));
         chunk_counts(e, base + 64u * j, rmask[j], __ballot(rcv && i < e.a_count));
     }
     block_flags_wave(e, base, rmask);
@@ -350,6 +356,32 @@ __device__ __forceinline__ int block_region(const ErasureSpec& e, uint32_t base)
     if (base - e.chunk < e.b_count) return 2;
     return 3;
 }
+// The 256 bytes of the read set at wp (any alignment), as the 65 aligned
+// dwords that hold them: wd[d] = the dword at (wp rounded down to 4) + 4 d, and
+// the return value sh = wp mod 4, so the bytes wp[4 q .. 4 q + 3] are
+// alignbyte(wd[q + 1], wd[q], sh).  Dwords 1 .. 63 lie inside the 256 bytes and
+// are loaded whole; the first and the last are put together from the bytes
+// that belong to the block (0 elsewhere): no byte outside it is read.
+__device__ __forceinline__ uint32_t wanted_block(uint32_t (&wd)[65], const uint8_t* wp) {
+    const uint32_t sh = (uint32_t)((uintptr_t)wp & 3u);
+    const uint32_t* a0 = (const uint32_t*)(wp - sh);
+#pragma unroll
+    for (int d = 1; d < 64; d++) wd[d] = a0[d];
+    if (sh == 0) {
+        wd[0] = a0[0];
+        wd[64] = 0;
+    } else {
+        uint32_t f = 0, l = 0;
+#pragma unroll
+        for (uint32_t b = 0; b < 4; b++) {
+            if (b >= sh) f |= (uint32_t)wp[b - sh] << (8 * b);
+            else l |= (uint32_t)wp[256 - sh + b] << (8 * b);
+        }
+        wd[0] = f;
+        wd[64] = l;
+    }
+    return sh;
+}
 __global__ void __launch_bounds__(256) eval_fused_kernel(ErasureSpec e, uint32_t* out32, const uint16_t* log_walsh) {
     __shared__ int xs[256];
     __shared__ uint32_t lr[2][4];
@@ -399,16 +431,42 @@ __global__ void __launch_bounds__(256) eval_fused_kernel(ErasureSpec e, uint32_t
         }
         if (j == 0 && e.lostrange) {  // (uniform: workgroup 0 of a general decode)
             const bool want = e.lost_all || (e.orig_b ? reg == 2 : reg == 0);  // (fl: reg is 0 or 2)
+            if (e.wanted) {
+                // A selective decode: the lost rows that are wanted.  The
+                // block's 256 bytes of the read set (the block lies whole in the
+                // originals' segment: eval_fused_ok) all requested at once --
+                // one round trip; fetched erased byte by erased byte, the
+                // unrolled scan waited for memory 64 times (+17 us).
+                uint32_t wd[65];
+                uint32_t sh = 0;
+                if (want) sh = wanted_block(wd, e.wanted + (base - (e.orig_b ? e.chunk : 0u)));
 #pragma unroll
-            for (int i = 0; i < 16; i++) {
-                const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+                for (int i = 0; i < 16; i++) {
+                    const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
 #pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    const uint32_t m = want ? ~nz80(w[c]) & 0x80808080u : 0u;  // erased bytes
-                    const uint32_t r = base + 4u * (4 * i + c);
-                    if (m) {
-                        lo = min(lo, r + (uint32_t)(__builtin_ctz(m) >> 3));
-                        hi = r + (uint32_t)((31 - __builtin_clz(m)) >> 3) + 1u;
+                    for (int c = 0; c < 4; c++) {
+                        const int q = 4 * i + c;
+                        const uint32_t wq = want ? __builtin_amdgcn_alignbyte(wd[q + 1], wd[q], sh) : 0u;
+                        const uint32_t m = ~nz80(w[c]) & nz80(wq);  // erased and wanted bytes
+                        const uint32_t r = base + 4u * q;
+                        if (m) {
+                            lo = min(lo, r + (uint32_t)(__builtin_ctz(m) >> 3));
+                            hi = r + (uint32_t)((31 - __builtin_clz(m)) >> 3) + 1u;
+                        }
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 16; i++) {
+                    const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+#pragma unroll
+                    for (int c = 0; c < 4; c++) {
+                        const uint32_t m = want ? ~nz80(w[c]) & 0x80808080u : 0u;  // erased bytes
+                        const uint32_t r = base + 4u * (4 * i + c);
+                        if (m) {
+                            lo = min(lo, r + (uint32_t)(__builtin_ctz(m) >> 3));
+                            hi = r + (uint32_t)((31 - __builtin_clz(m)) >> 3) + 1u;
+                        }
                     }
                 }
             }
@@ -558,7 +616,7 @@ __global__ void __launch_bounds__(256) eval_small_kernel(ErasureSpec e, const ui
         const uint64_t eb = __ballot(era);
         if (lane == 0) part[0][wv][hp] = __popcll(eb & ~sm) - __popcll(eb & sm);
         if (j == 0 && e.lostrange) {
-            const uint64_t lb = __ballot(orig_row(e, i) && !rcv);
+            const uint64_t lb = __ballot(orig_row(e, i) && !rcv && wanted_row(e, i));
             const uint32_t r0 = (uint32_t)hp * 256u + wv * 64u;
             if (lb) {
                 wlo = min(wlo, r0 + (uint32_t)__builtin_ctzll(lb));

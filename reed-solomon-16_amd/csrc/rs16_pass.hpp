@@ -7,7 +7,8 @@
 // Included only by the units that instantiate pass_kernel<P, T, NV>
 // (rs16_pass_enc.hip, rs16_pass_dec.hip; rs16_pass_tower.hip for the tower
 // flavours pass_kernel_late_tower; rs16_pass_repair.hip for the repair's
-// programs, pass_kernel_repair); launch_pass (rs16_pass_launch.hip)
+// programs, pass_kernel_repair; rs16_pass_select.hip for the selective
+// decode's, pass_kernel_select); launch_pass (rs16_pass_launch.hip)
 // reaches the kernels through their PassKernel lookups.
 //
 // Structure of one pass
@@ -79,8 +80,12 @@ namespace rs16 {
 enum LoadMode { LD_PLAIN = 0, LD_GATHER_ENC, LD_GATHER_DEC, LD_DEC_LAST };
 // ST_RESTORE_ALL (the repair's programs): ST_RESTORE for the lost rows of both
 // segments, each stored to its own segment's array (PassArgs::rest / rest_b).
-enum StoreMode { ST_PLAIN = 0, ST_RECOVERY, ST_RESTORE, ST_RESTORE_ALL };
-constexpr bool st_restores(int st) { return st == ST_RESTORE || st == ST_RESTORE_ALL; }
+// ST_RESTORE_SEL (the selective decode's programs): ST_RESTORE for the lost
+// originals of the read set only (PassArgs::wanted); the addresses are ST_RESTORE's.
+enum StoreMode { ST_PLAIN = 0, ST_RECOVERY, ST_RESTORE, ST_RESTORE_ALL, ST_RESTORE_SEL };
+constexpr bool st_restores(int st) { return st == ST_RESTORE || st == ST_RESTORE_ALL || st == ST_RESTORE_SEL; }
+// the row predicate of a restoring store mode (row_wanted)
+constexpr int st_row_rule(int st) { return st == ST_RESTORE_ALL ? ROWS_ALL : (st == ST_RESTORE_SEL ? ROWS_SEL : ROWS_LOST); }
 
 // Store cache policy: non-temporal stores in the single-direction passes,
 // plain stores in the two-direction passes (same-box A/B, CHANGELOG.md round 3:
@@ -109,6 +114,8 @@ RS16_PROG(DEC_HALF_LAST, LD_PLAIN, false, false, true, ST_RESTORE)
 RS16_PROG(DEC_HALF_SINGLE, LD_GATHER_DEC, true, false, true, ST_RESTORE)
 RS16_PROG(DEC_LAST_ALL, LD_DEC_LAST, false, false, true, ST_RESTORE_ALL)
 RS16_PROG(DEC_SINGLE_ALL, LD_GATHER_DEC, true, true, true, ST_RESTORE_ALL)
+RS16_PROG(DEC_LAST_SEL, LD_DEC_LAST, false, false, true, ST_RESTORE_SEL)
+RS16_PROG(DEC_SINGLE_SEL, LD_GATHER_DEC, true, true, true, ST_RESTORE_SEL)
 #undef RS16_PROG
 
 // Row bits in registers: 4 (16 rows per thread) from T = 6 on; 3 at T = 5
@@ -660,14 +667,15 @@ template <int T> struct TwiddleEntry {
 //
 // REVEAL ERASURES (rate_high.rs:236-242 / rate_low.rs:236-242): lost
 // original row r -> work[r] * (GF_MODULUS - e[r]).
-// (ALL: the repair's programs reveal the lost rows of both segments, row_wanted)
-template <int T, bool ALL = false> struct RevealEntry {
+// (RULE: the repair's programs reveal the lost rows of both segments, the
+// selective decode's the lost originals of the read set: row_wanted)
+template <int T, int RULE = ROWS_LOST> struct RevealEntry {
     const PassArgs& a;
     const Thr& c;
     const uint32_t* el;
     __device__ __forceinline__ uint32_t operator()(int k) const {
         const uint32_t r = row_rel<T>(c, a, (uint32_t)k) + a.row_base_out;
-        return row_wanted<ALL>(a, r) ? GF_MODULUS - (el ? el[k] : a.elog[r]) : ZERO_ENTRY;
+        return row_wanted<RULE>(a, r) ? GF_MODULUS - (el ? el[k] : a.elog[r]) : ZERO_ENTRY;
     }
 };
 
@@ -1351,15 +1359,15 @@ template <int P, int T> struct LateReveal {
 template <int P, int T> struct RevealStage {
     using SM = Smem<P, T>;
     using G = Geo<T>;
-    static constexpr bool ALL = ProgTraits<P>::STORE == ST_RESTORE_ALL;
+    static constexpr int RULE = st_row_rule(ProgTraits<P>::STORE);
     Stager<T, (1 << T)> sr;
     uint32_t lost[((1 << T) + G::THREADS - 1) / G::THREADS];
     __device__ __forceinline__ void issue(const PassArgs& a, const Thr& c, const uint32_t* el) {
-        sr.issue(a.mul_tab, RevealEntry<T, ALL>{a, c, el});
+        sr.issue(a.mul_tab, RevealEntry<T, RULE>{a, c, el});
 #pragma unroll
         for (int i = 0; i < (int)(sizeof lost / sizeof lost[0]); i++) {
             const uint32_t k = threadIdx.x + i * G::THREADS;
-            lost[i] = k < (1u << T) && row_wanted<ALL>(a, row_rel<T>(c, a, k) + a.row_base_out);
+            lost[i] = k < (1u << T) && row_wanted<RULE>(a, row_rel<T>(c, a, k) + a.row_base_out);
         }
     }
     __device__ __forceinline__ void commit(uint8_t* smem) const {

@@ -65,6 +65,7 @@ PassKernel pass_kernels_dec(int prog, int T, int nv);  // rs16_pass_dec.hip: DEC
 PassFn pass_kernels_tower(int prog, int T, int nv);    // rs16_pass_tower.hip: the tower flavours (nullptr: none)
 PassFn pass_kernel_tower_wide3(int prog, int T);       // rs16_pass_tower.hip: PassKernel::wide3 (nullptr: none)
 PassKernel pass_kernels_repair(int prog, int T);       // rs16_pass_repair.hip: DEC_LAST_ALL, DEC_SINGLE_ALL (no narrow variants)
+PassKernel pass_kernels_select(int prog, int T);       // rs16_pass_select.hip: DEC_LAST_SEL, DEC_SINGLE_SEL (no narrow variants)
 
 #if defined(__HIPCC__) || defined(__HIP__)
 // ---------------------------------------------------------------------------
@@ -102,6 +103,7 @@ __device__ __forceinline__ void stripe_displace(PassArgs& a, uint32_t st) {
     a.seg_b += st * a.bs_seg_b;
     a.rest += st * a.bs_rest;
     a.rest_b += st * a.bs_rest_b;
+    if (a.wanted) a.wanted += st * a.bs_wanted;
     if (a.flags_a) a.flags_a += st * a.bs_fa;
     if (a.flags_b) a.flags_b += st * a.bs_fb;
     if (a.elog) a.elog += st * a.bs_elog;
@@ -149,10 +151,16 @@ __device__ __forceinline__ bool row_lost_original(const PassArgs& a, uint32_t r)
     const uint8_t* fl = a.rest_seg_b ? a.flags_b : a.flags_a;
     return r >= base && r - base < cnt && fl && !fl[r - base];
 }
-// A row the pass reveals and stores: a lost original, or (ALL, the repair's
-// programs) a row of either segment without a received flag.
-template <bool ALL> __device__ __forceinline__ bool row_wanted(const PassArgs& a, uint32_t r) {
-    if constexpr (!ALL) return row_lost_original(a, r);
+// A row the pass reveals and stores, by the program's rule: a lost original
+// (ROWS_LOST); a row of either segment without a received flag (ROWS_ALL, the
+// repair's programs); a lost original whose byte of the read set is nonzero
+// (ROWS_SEL, the selective decode's programs -- the byte is read only for a
+// lost original, so never outside the read set's [0, original count)).
+enum RowRule : int { ROWS_LOST = 0, ROWS_ALL, ROWS_SEL };
+template <int RULE> __device__ __forceinline__ bool row_wanted(const PassArgs& a, uint32_t r) {
+    if constexpr (RULE == ROWS_LOST) return row_lost_original(a, r);
+    if constexpr (RULE == ROWS_SEL)
+        return row_lost_original(a, r) && a.wanted[r - (a.rest_seg_b ? a.chunk : 0)] != 0;
     if (r < a.a_count) return a.flags_a && !a.flags_a[r];
     return r >= a.chunk && r - a.chunk < a.b_count && a.flags_b && !a.flags_b[r - a.chunk];
 }

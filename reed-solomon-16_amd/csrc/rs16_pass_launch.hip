@@ -1,6 +1,7 @@
 // rs16_pass_launch.hip -- launch_pass: which pass kernel a launch takes and
 // how it is launched.  The kernels themselves are instantiated in
-// rs16_pass_enc.hip, rs16_pass_dec.hip and rs16_pass_tower.hip (template:
+// rs16_pass_enc.hip, rs16_pass_dec.hip, rs16_pass_tower.hip, rs16_pass_repair.hip
+// and rs16_pass_select.hip (template:
 // rs16_pass.hpp); this unit sees them through the PassKernel lookups only.
 #include <algorithm>
 
@@ -35,10 +36,23 @@ struct RepairTable {
             for (int T = 0; T <= 8; T++) k[p][T] = pass_kernels_repair(DEC_LAST_ALL + p, T);
     }
 };
+// The selective decode's programs (rs16_pass_select.hip), likewise.
+struct SelectTable {
+    PassKernel k[2][9], none{};
+    SelectTable() {
+        static_assert(DEC_SINGLE_SEL == DEC_LAST_SEL + 1, "the table's rows");
+        for (int p = 0; p < 2; p++)
+            for (int T = 0; T <= 8; T++) k[p][T] = pass_kernels_select(DEC_LAST_SEL + p, T);
+    }
+};
 static const PassKernel& find_kernel(int prog, int T, int nv) {
     if (repair_prog(prog)) {
         static const RepairTable repair;
         return nv == 0 ? repair.k[prog - DEC_LAST_ALL][T] : repair.none;
+    }
+    if (select_prog(prog)) {
+        static const SelectTable select;
+        return nv == 0 ? select.k[prog - DEC_LAST_SEL][T] : select.none;
     }
     static const KernelTable table;
     return table.k[prog][T][nv];
@@ -142,8 +156,10 @@ ZForm z_form_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t
 }
 
 hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles, hipStream_t s) {
-    if (prog < 0 || (prog >= NUM_PROGS && !repair_prog(prog)) || T < 0 || T > 8) return hipErrorInvalidValue;
-    if (repair_prog(prog) && !find_kernel(prog, T, 0).fn) return hipErrorInvalidValue;  // (DEC_LAST_ALL: T >= 4, DEC_SINGLE_ALL: T >= 1)
+    const bool appended = repair_prog(prog) || select_prog(prog);  // (the programs behind the profiling ids)
+    if (prog < 0 || (prog >= NUM_PROGS && !appended) || T < 0 || T > 8) return hipErrorInvalidValue;
+    if (appended && !find_kernel(prog, T, 0).fn) return hipErrorInvalidValue;  // (DEC_LAST_*: T >= 4, DEC_SINGLE_*: T >= 1)
+    if (select_prog(prog) && !args.wanted) return hipErrorInvalidValue;  // (the read set is dereferenced)
     if (num_tiles == 0 || args.qrow == 0) return hipSuccess;
     PassArgs a = args;
     // Narrow twiddles: the launch's tiles are tile_base + [0, tiles of one

@@ -32,6 +32,7 @@ __all__ = [
     "DIAG_TILE_LAST", "DIAG_NO_TILE_LAST", "DIAG_FD_LDS", "DIAG_COL_RADIX4", "DIAG_NO_IDENTITY", "DIAG_NO_MID_DIRECT", "DIAG_WIDE_TWIDDLES", "DIAG_NO_LATE_ROWS", "DIAG_NO_PAIRED_ROWS", "DIAG_NO_TOWER_ROWS", "encode_host", "decode_host",
     "encode_host_batch", "decode_host_batch", "decode_prepare", "decode_device_prepared",
     "repair_device", "repair_device_batch", "repair_path",
+    "decode_device_select", "decode_device_select_batch", "select_path",
     "UpdatePlan", "update_recovery_device", "UPDATE_MAX_SHARDS",
     "encode_host_multi", "decode_host_multi", "Comm", "column_slice", "scatter_columns", "gather_columns",
 ]
@@ -737,6 +738,50 @@ def repair_path(original_count, recovery_count, original_received_count, recover
     p = lib().rs16_host_repair_path(original_count, recovery_count, original_received_count,
                                     recovery_received_count, C.byref(lo), C.byref(t0), C.byref(nt))
     return p, lo.value, t0.value, nt.value
+
+
+def decode_device_select(original_count, recovery_count, shard_bytes, d_original, d_original_received,
+                         d_original_wanted, d_recovery, d_recovery_received, original_received_count,
+                         recovery_received_count, wanted_count, stream=None, engine: Optional[Engine] = None,
+                         check: bool = False):
+    """rs16_decode_device_select: decode_device restoring only the lost originals
+    whose byte of d_original_wanted (original_count device bytes) is nonzero;
+    wanted_count of them.  Other lost slots keep their bytes.  check=True:
+    rs16_decode_check afterwards."""
+    eng = engine or default_engine()
+    err = RS16Error()
+    _check(lib().rs16_decode_device_select(eng.h, original_count, recovery_count, shard_bytes, Engine._ptr(d_original),
+                                           Engine._ptr(d_original_received), Engine._ptr(d_original_wanted),
+                                           Engine._ptr(d_recovery), Engine._ptr(d_recovery_received),
+                                           original_received_count, recovery_received_count, wanted_count, stream,
+                                           C.byref(err)), err)
+    if check:
+        _check(lib().rs16_decode_check(eng.h, stream, C.byref(err)), err)
+
+
+def decode_device_select_batch(original_count, recovery_count, shard_bytes, nstripes, d_original, original_stride,
+                               d_original_received, d_original_wanted, d_recovery, recovery_stride,
+                               d_recovery_received, original_received_count, recovery_received_count, wanted_count,
+                               stream=None, engine: Optional[Engine] = None, check: bool = False):
+    """rs16_decode_device_select_batch: nstripes stripes with one shared erasure
+    pattern and one shared read set.  check=True: rs16_decode_check afterwards."""
+    eng = engine or default_engine()
+    err = RS16Error()
+    _check(lib().rs16_decode_device_select_batch(eng.h, original_count, recovery_count, shard_bytes, nstripes,
+                                                 Engine._ptr(d_original), original_stride,
+                                                 Engine._ptr(d_original_received), Engine._ptr(d_original_wanted),
+                                                 Engine._ptr(d_recovery), recovery_stride,
+                                                 Engine._ptr(d_recovery_received), original_received_count,
+                                                 recovery_received_count, wanted_count, stream, C.byref(err)), err)
+    if check:
+        _check(lib().rs16_decode_check(eng.h, stream, C.byref(err)), err)
+
+
+def select_path(original_count, recovery_count, original_received_count, recovery_received_count, wanted_count):
+    """rs16_host_select_path: 0 nothing to do, 1 the plain decode, 2 the selective
+    decode, -1 the call fails; host arithmetic, no device."""
+    return lib().rs16_host_select_path(original_count, recovery_count, original_received_count,
+                                       recovery_received_count, wanted_count)
 
 
 def decode_prepare(original_count, recovery_count, shard_bytes, d_original_received, d_recovery_received,

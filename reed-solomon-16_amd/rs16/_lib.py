@@ -115,6 +115,10 @@ SIGNATURES = {
     "rs16_repair_device": (_i, [_p, _sz, _sz, _sz, _p, _p, _p, _p, _sz, _sz, _p, _e]),
     "rs16_repair_device_batch": (_i, [_p, _sz, _sz, _sz, _sz, _p, _sz, _p, _p, _sz, _p, _sz, _sz, _p, _e]),
     "rs16_host_repair_path": (_i, [_sz, _sz, _sz, _sz, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "rs16_decode_device_select": (_i, [_p, _sz, _sz, _sz, _p, _p, _p, _p, _p, _sz, _sz, _sz, _p, _e]),
+    "rs16_decode_device_select_batch": (_i, [_p, _sz, _sz, _sz, _sz, _p, _sz, _p, _p, _p, _sz, _p, _sz, _sz, _sz, _p,
+                                             _e]),
+    "rs16_host_select_path": (_i, [_sz, _sz, _sz, _sz, _sz]),
     "rs16_decode_check": (_i, [_p, _p, _e]),
     "rs16_device_alloc": (_p, [_p, _sz, _e]),
     "rs16_device_free": (None, [_p, _p]),
