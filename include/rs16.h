@@ -432,6 +432,96 @@ int rs16_decode_device_select_batch(rs16_engine* eng, size_t original_count, siz
                                     const uint8_t* d_recovery_received, size_t original_received_count,
                                     size_t recovery_received_count, size_t wanted_count, void* stream,
                                     rs16_error* err);
+/* Scrub: verify a stripe's stored recovery shards on the device.  Tells whether
+ * the recovery shards in d_recovery still equal the encode of the originals in
+ * d_original and, if not, which recovery shards and which byte columns differ.
+ * d_original holds all original_count shards, d_recovery recovery_count slots;
+ * both are READ ONLY and 64-byte aligned like every other device shard array.
+ * Rate selection is that of rs16_encode_device.
+ * The check set d_recovery_checked: NULL means every recovery shard is checked;
+ * otherwise recovery_count bytes, 0 = "do not compare this slot" (the shard may
+ * be missing: the slot's bytes are never read as data that matters), any nonzero
+ * byte = "compare".  It needs no alignment, and no byte outside [0,
+ * recovery_count) is read.
+ * Outputs: d_recovery_mismatch[j] is written for every j < recovery_count,
+ * whatever it held before: 1 when shard j is checked and differs in at least one
+ * byte from what rs16_encode_device would write there for these originals, else
+ * 0.  d_column_mismatch may be NULL; if given it is shard_bytes / 64 bytes, and
+ * byte c is 1 when some checked recovery shard differs within bytes [64 c, 64 c
+ * + 64), else 0.  Every 64-byte column block is an independent codeword, so the
+ * pair of arrays tells "one recovery shard rotted" (one row, few columns) from
+ * "an original rotted" (many rows at the same columns).  Neither output array
+ * needs alignment; no byte outside them is written.  There is no count and no
+ * "which original is bad": locating a corrupt original is syndrome decoding,
+ * which this library does not do.
+ * The call is asynchronous on `stream` and ordered on the engine's scratch like
+ * an encode.  Like rs16_encode_device it is not a decode: it neither discards a
+ * pending rs16_decode_prepare nor changes what rs16_decode_check reports.
+ * Column slices (rs16_engine_set_slices) do not apply.
+ * Errors, in this order: UnsupportedShardCount / InvalidShardSize as
+ * rs16_validate gives them; InvalidArgument for a NULL or misaligned shard
+ * array, a NULL d_recovery_mismatch and, in the batch form, a bad stride or
+ * nstripes > 2^20.  nstripes == 0: RS16_OK, nothing launched.
+ * Two paths (rs16_host_verify_path), both starting with a clear of the flag arrays
+ * on the stream; the kernels only ever store the byte 1:
+ *   1 = fused: the encode's own launches up to the last one, whose place a
+ *       comparing form of it takes (ENC_LAST_VFY / ENC_SINGLE_VFY): it loads the
+ *       stored row where the encode would store the computed one and writes
+ *       flag bytes where they differ.  No second recovery array, no store sweep,
+ *       no compare launch.  Exists where the engine's encode of the shape ends
+ *       in a pass-codec store pass: not for stripes the column codec encodes
+ *       (512 / 1024-row chunks up to 2 KiB of quad columns, the multi-chunk
+ *       column forms) nor for chunks below 16 rows in the multi-chunk rates or
+ *       one-row chunks.  Its three-pass sequence keeps the work rows in the
+ *       shards' form (as under RS16_DIAG_NO_PAIRED_ROWS).
+ *   0 = encode + compare: the engine's encode into a buffer of its own
+ *       (recovery_count x shard_bytes per stripe, reserved on first use), then
+ *       one compare kernel (VERIFY_CMP) over it and the stored shards.
+ * RS16_DIAG_NO_FUSED_VERIFY / RS16_DIAG_FORCE_FUSED_VERIFY force either path
+ * wherever it exists; the flags are identical under both.
+ * When to prefer it (measured on one MI355X per run at 1 KiB shards, clean and
+ * with one original corrupted, DESIGN.md 3.18, profiles/r18_verify.txt; the
+ * other candidate is an encode into a second array plus a compare kernel of the
+ * caller's own, which is what path 0 does inside the library): a scrub costs an
+ * encode plus 4-17 us, and never a second recovery array of the caller's.  Over
+ * rs16_encode_device alone, on the default path: +15.7 to +16.8 us at
+ * 32768:32768 (76 against 60 us), +6.5 to +7.2 at 8000:8000 (41 against 34),
+ * +8.1 to +8.3 at 60000:3000 (107 against 98), +10.0 to +11.6 at 5:3000 (18.7
+ * against 7.3), +7.5 to +8.1 at 1000:1000 (15.6 against 7.8), +3.8 to +7.4 for
+ * the batches below.  The default path is the fused one only where it was faster than
+ * encode + compare in every alternating pair of every run, clean and corrupted:
+ * batches of 4 or more one-chunk high-rate stripes of 1024-row chunks (513 ..
+ * 1024 recovery shards, at most as many originals), which are too wide for the
+ * column codec -- 4 / 8 / 32 x 1000:1000: 23.1 / 28.8 / 68.3 us against 25.5 /
+ * 30.0 / 75.8 (0.91 / 0.96 / 0.90 x).  Everywhere else the default is encode +
+ * compare and the fused kernels stay reachable through the force flag: at
+ * 32768:32768 the fused path is 0.4-1.3 us faster in the median (75.7 against
+ * 76.1 us) but lost 1 to 3 of 9 pairs per run -- its three passes keep the work
+ * rows in the shards' form (the middle pass 32.5 against 27.6 us in tower form)
+ * and its last pass takes 26.2 us against 19.4, which together give back most of
+ * the 14.2 us compare kernel; at 8000:8000 it is 0.2-0.8 us SLOWER (41.3 against
+ * 40.8) and at 60000:3000 1.2-1.6 us slower (107.9 against 106.7), losing every
+ * pair but two; one 1000:1000 stripe forced through the passes
+ * (RS16_DIAG_NO_COLUMN) is 1.4-1.7 us faster fused (20.3 against 22.0) but won
+ * only 7 of 9 pairs in one of three runs.  Stripes the column codec encodes and
+ * chunks below 16 rows in the multi-chunk rates have no fused kernel.  Sizes in
+ * between are not measured. */
+int rs16_verify_device(rs16_engine* eng, size_t original_count, size_t recovery_count, size_t shard_bytes,
+                       const void* d_original, const void* d_recovery, const uint8_t* d_recovery_checked,
+                       uint8_t* d_recovery_mismatch, uint8_t* d_column_mismatch, void* stream, rs16_error* err);
+/* rs16_verify_device for `nstripes` stripes: stripe i's shards at + i
+ * original_stride / recovery_stride (multiples of 64, at least the arrays'
+ * sizes), its flags at d_recovery_mismatch + i recovery_mismatch_stride and
+ * d_column_mismatch + i column_mismatch_stride (at least recovery_count and
+ * shard_bytes / 64; anything smaller is InvalidArgument).  Only each stripe's
+ * used range is written: bytes between the strides stay as they were.  The
+ * check set is shared by all stripes: a failed device holds the same index of
+ * every stripe.  Every stripe's flags equal rs16_verify_device on it alone. */
+int rs16_verify_device_batch(rs16_engine* eng, size_t original_count, size_t recovery_count, size_t shard_bytes,
+                             size_t nstripes, const void* d_original, size_t original_stride,
+                             const void* d_recovery, size_t recovery_stride, const uint8_t* d_recovery_checked,
+                             uint8_t* d_recovery_mismatch, size_t recovery_mismatch_stride,
+                             uint8_t* d_column_mismatch, size_t column_mismatch_stride, void* stream, rs16_error* err);
 /* Checked mode of the engine's last decode: waits for `stream` and compares
  * the received counts that decode was given with the rows the device flags
  * mark received (the eval_poly kernels count them per 64-row chunk as they
@@ -727,10 +817,14 @@ enum {
                                       decode of 2^14 / 2^15-row chunks, widths a multiple of 512 bytes,
                                       keep a quad's two dwords next to each other there and move a row
                                       with one 8-byte access per lane; rs16_host_paired_rows) */
-    RS16_DIAG_NO_TOWER_ROWS = 16384 /* paired rows of the work buffer stay in the shards' coordinates
+    RS16_DIAG_NO_TOWER_ROWS = 16384, /* paired rows of the work buffer stay in the shards' coordinates
                                       (default: they are kept as a + b beta over the GF(2^8) subfield, in
                                       which the middle pass multiplies by a subfield twiddle with 6
                                       lookups instead of 9; rs16_host_tower_rows) */
+    RS16_DIAG_NO_FUSED_VERIFY = 32768, /* rs16_verify_device always as encode + compare (path 0); wins
+                                      over RS16_DIAG_FORCE_FUSED_VERIFY when both are set */
+    RS16_DIAG_FORCE_FUSED_VERIFY = 65536 /* ... as the fused path wherever a comparing kernel exists for
+                                      the shape's last pass, whatever the default gate says */
 };
 int rs16_engine_set_diagnostics(rs16_engine* eng, int flags);
 /* Deprecated (the round-4 process-wide form, kept for existing callers):
@@ -874,6 +968,13 @@ int rs16_host_update_consts(uint32_t rows, uint64_t shard_bytes, uint32_t n, uin
  * the low rate; chunk = a_count rounded up to a power of two.) */
 int rs16_host_repair_path(size_t original_count, size_t recovery_count, size_t original_received_count,
                           size_t recovery_received_count, uint32_t* lo, uint32_t* first_tile, uint32_t* tiles);
+/* The path rs16_verify_device / rs16_verify_device_batch takes for a shape, as
+ * the entry points decide it (one host function) on an engine with the
+ * diagnostic switches `diag` (RS16_DIAG_*) and the default column-codec limits:
+ * 1 = fused, 0 = encode + compare, -1 = the counts or the shard size are not
+ * supported.  nstripes: the stripes of the batch form (1: the single call). */
+int rs16_host_verify_path(size_t original_count, size_t recovery_count, size_t shard_bytes, size_t nstripes,
+                          int diag);
 /* The path rs16_decode_device_select takes, as the entry points decide it (one
  * host function; no device needed): 0 nothing to do (every original received,
  * or wanted_count == 0), 1 = rs16_decode_device (the read set covers every lost

@@ -112,7 +112,8 @@ static int host_pass_consts(int prog, int T, uint32_t lo, size_t n, const uint64
                             const uint64_t* s_seg, const uint64_t* s_rest, const uint32_t* qrow, uint32_t chunk,
                             uint32_t row_base_in, uint32_t in_rows_mask, uint32_t a_count, int diag,
                             rs16_pass_consts* out) {
-    if (prog < 0 || prog >= NUM_PROGS || T < 0 || T > 8 || !out) return 0;
+    // (the scrub's programs lie behind the profiling ids, as the repair's and the select's)
+    if (prog < 0 || (prog >= NUM_PROGS && !verify_prog(prog)) || T < 0 || T > 8 || !out) return 0;
     const PassKernel& k = pass_kernel_of(prog, T);
     if (!k.fn) return 0;
     PassArgs a{};
@@ -296,7 +297,8 @@ extern "C" int rs16_decode_check(rs16_engine* e, void* stream, rs16_error* err) 
 static constexpr int DIAG_ALL = DIAG_FORCE_VOFF64 | DIAG_EVAL_TWO_KERNEL | DIAG_EVAL_FULL | DIAG_NO_COLUMN |
                                 DIAG_FORCE_COLUMN | DIAG_TILE_LAST | DIAG_NO_TILE_LAST | DIAG_FD_LDS |
                                 DIAG_COL_RADIX4 | DIAG_NO_IDENTITY | DIAG_NO_MID_DIRECT | DIAG_WIDE_TWIDDLES |
-                                DIAG_NO_LATE_ROWS | DIAG_NO_PAIRED_ROWS | DIAG_NO_TOWER_ROWS;
+                                DIAG_NO_LATE_ROWS | DIAG_NO_PAIRED_ROWS | DIAG_NO_TOWER_ROWS |
+                                DIAG_NO_FUSED_VERIFY | DIAG_FORCE_FUSED_VERIFY;
 extern "C" int rs16_engine_set_diagnostics(rs16_engine* e, int flags) {
     const int old = e->diag;
     e->diag = flags & DIAG_ALL;
@@ -314,6 +316,7 @@ extern "C" const char* rs16_prog_name(int prog) {
                                   "DEC_HALF_FIRST", "DEC_HALF_MID", "EVAL_POLY", "COL_ENC", "COL_DEC",
                                   "DEC_MID_DIRECT", "DEC_TILE_LAST",
                                   "DEC_LAST_SEL", "DEC_SINGLE_SEL", "DEC_TILE_LAST_SEL", "COL_DEC_SEL",
+                                  "ENC_LAST_VFY", "ENC_SINGLE_VFY", "VERIFY_CMP",
                                   "DEC_LAST_ALL", "DEC_SINGLE_ALL", "REPAIR_COPY"};
     static_assert(sizeof names / sizeof names[0] == NUM_PROF, "profiling names");
     return (prog >= 0 && prog < NUM_PROF) ? names[prog] : "?";

@@ -368,12 +368,49 @@ int rs16_engine::ifft(uint8_t* data, size_t S, size_t pos, size_t size, size_t s
     return RS16_OK;
 }
 
+// The last launch of an encode as the scrub's comparing program: nothing is
+// stored to a recovery array (out stays null), the stored rows are read at the
+// addresses the recovery stores would take.
+static void sink_args(PassArgs& a, const VerifySink& v) {
+    a.out = nullptr;
+    a.S_out = 0;
+    a.vfy_cmp = v.cmp;
+    a.vfy_S = v.S_cmp;
+    a.bs_vfy_cmp = v.bs_cmp;
+    a.vfy_rows = v.rows;
+    a.vfy_cols = v.cols;
+    a.vfy_checked = v.checked;
+    a.bs_vfy_rows = v.bs_rows;
+    a.bs_vfy_cols = v.bs_cols;
+    a.bs_vfy_checked = 0;  // (one check set for all stripes)
+}
+
+// Whether the engine's encode of the shape ends in a pass-codec store pass that
+// has a comparing form (ENC_SINGLE_VFY at T >= 1, ENC_LAST_VFY at T >= 4): the
+// branches of encode_high_fused, encode_high_multi and encode_low_multi, in
+// their order.  nst: the stripes of one batched launch (encode_high_fused).
+bool rs16_engine::verify_fusable(bool high, size_t k, size_t m, size_t S, size_t nst) const {
+    if (high && k <= next_pow2(m)) {
+        const int L = ilog2(next_pow2(m));
+        return L >= 1 && !col_ok(L, S, nst);  // (L <= 8: one pass; above: lo = L / 2 >= 4)
+    }
+    const size_t chunk = next_pow2(high ? m : k);
+    const uint32_t nch = (uint32_t)(((high ? k : m) + chunk - 1) / chunk);
+    const int L = ilog2(chunk), lo = L <= 8 ? L : L / 2;
+    if (lo < 4) return false;  // (fft_to_recovery's last pass at T = lo; L = 0: the copy branches)
+    if (L == (int)COLM_L && nch <= COLM_MAX_CHUNKS && (high || nch > 1) && col_ok(L, S, 1)) return false;
+    if (!high && nch == 1 && col_ok(L, S, 1)) return false;
+    if ((high || nch > 1) && col_chunks_ok(L, nch, S, high)) return false;
+    return true;
+}
+
 // HighRateEncoder::encode for original_count <= chunk (src/rate/rate_high.rs:44-83):
 //   recovery = FFT(IFFT(originals zero-padded to chunk, skew = chunk), skew = 0)[0..m)
 // as three passes over the 2-D row factorisation (contiguous low bits /
 // strided high bits); IFFT-high and FFT-high share the strided pass.
 int rs16_engine::encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec, uint8_t* Z,
-                                   hipStream_t s, rs16_error* err, size_t nst, size_t bs_orig, size_t bs_rec) {
+                                   hipStream_t s, rs16_error* err, size_t nst, size_t bs_orig, size_t bs_rec,
+                                   const VerifySink* vs) {
     const size_t chunk = next_pow2(m);
     const int L = ilog2(chunk);
     PassArgs a = base_args(this, S);
@@ -394,7 +431,9 @@ int rs16_engine::encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, 
         a.bs_seg = bs_seg;
         return tiles * ns;
     };
-    if (col_ok(L, S, nst)) {
+    // (a verify sink: the shapes of verify_fusable only, whose last launch compares)
+    if (vs && !verify_fusable(true, k, m, S, nst)) return set_error(err, RS16_INVALID_ARGUMENT);
+    if (!vs && col_ok(L, S, nst)) {
         // 512 / 1024-row chunks: the whole encode in one launch (rs16_col.hip)
         ColArgs c = col_args();
         c.in = d_orig;
@@ -413,13 +452,16 @@ int rs16_engine::encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, 
     if (L <= 8) {
         a.out = d_rec;
         a.S_out = S_user;
-        RS16_PASS(ENC_SINGLE, L, a, batch(1, 0, bs_rec, bs_orig), s);
+        if (vs) sink_args(a, *vs);
+        RS16_PASS(vs ? ENC_SINGLE_VFY : ENC_SINGLE, L, a, batch(1, 0, bs_rec, bs_orig), s);
         return RS16_OK;
     }
     const int lo = row_split(L).lo, hi = row_split(L).hi;
     const size_t zs = chunk * S;
     // the form of Z between the three passes, one decision for all of them
-    const ZForm zf = z_form_sequence((uint32_t)chunk, S, S_user, a.a_count, a.chunk, a.row_base_in, diag);
+    // (a verify sink: the work rows in the shards' own form -- the comparing
+    // last pass has the general kernel only)
+    const ZForm zf = vs ? Z_SHARD : z_form_sequence((uint32_t)chunk, S, S_user, a.a_count, a.chunk, a.row_base_in, diag);
     a.out = Z;
     a.lo = 0;
     z_form_args(a, zf);
@@ -432,7 +474,8 @@ int rs16_engine::encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, 
     a.S_out = S_user;
     a.lo = 0;
     const uint32_t tiles = (uint32_t)((m + ((size_t)1 << lo) - 1) >> lo);
-    RS16_PASS(ENC_LAST, lo, a, batch(tiles, zs, bs_rec, 0), s);
+    if (vs) sink_args(a, *vs);
+    RS16_PASS(vs ? ENC_LAST_VFY : ENC_LAST, lo, a, batch(tiles, zs, bs_rec, 0), s);
     return RS16_OK;
 }
 
@@ -908,7 +951,8 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
 // like the IFFTs below, skew_delta applied to absolute rows), recovery rows
 // [0, m) stored to d_rec.
 int rs16_engine::fft_to_recovery(size_t m, size_t S, size_t S_user, const uint8_t* src, uint8_t* Z, uint8_t* d_rec,
-                                 size_t chunk, uint32_t nch, uint32_t skew, hipStream_t s, rs16_error* err) {
+                                 size_t chunk, uint32_t nch, uint32_t skew, hipStream_t s, rs16_error* err,
+                                 const VerifySink* vs) {
     const int L = ilog2(chunk), lo = L <= 8 ? L : L / 2, hi = L - lo;
     PassArgs a = base_args(this, S);
     a.skew_fft = skew;
@@ -927,7 +971,8 @@ int rs16_engine::fft_to_recovery(size_t m, size_t S, size_t S_user, const uint8_
     a.S_out = S_user;
     a.lo = 0;
     a.out_rows = (uint32_t)m;
-    RS16_PASS(ENC_LAST, lo, a, (uint32_t)((m + ((size_t)1 << lo) - 1) >> lo), s);
+    if (vs) sink_args(a, *vs);
+    RS16_PASS(vs ? ENC_LAST_VFY : ENC_LAST, lo, a, (uint32_t)((m + ((size_t)1 << lo) - 1) >> lo), s);
     return RS16_OK;
 }
 
@@ -942,19 +987,21 @@ int rs16_engine::fft_to_recovery(size_t m, size_t S, size_t S_user, const uint8_
 // all chunks; the first pass gathers the originals, rows >= k read as zero),
 // then one XOR reduction, then the FFT.
 int rs16_engine::encode_high_multi(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec,
-                                   uint8_t* Z, hipStream_t s, rs16_error* err) {
+                                   uint8_t* Z, hipStream_t s, rs16_error* err, const VerifySink* vs) {
     const size_t chunk = next_pow2(m);
     const uint32_t nch = (uint32_t)((k + chunk - 1) / chunk);
     const int L = ilog2(chunk), lo = L <= 8 ? L : L / 2, hi = L - lo;
+    // (a verify sink: the shapes of verify_fusable only -- none of the branches before the passes)
+    if (vs && !verify_fusable(true, k, m, S, 1)) return set_error(err, RS16_INVALID_ARGUMENT);
     if (L == 0) {  // one-row chunks: the single recovery row is the XOR of the originals
         if (Z != d_orig) RS16_HIP(hipMemcpy2DAsync(Z, S, d_orig, S_user, S, k, hipMemcpyDeviceToDevice, s));
         RS16_HIP(launch_xor_chunks(Z, S, nch, s));
         if (d_rec != Z) RS16_HIP(hipMemcpyAsync(d_rec, Z, S, hipMemcpyDeviceToDevice, s));
         return RS16_OK;
     }
-    if (L == (int)COLM_L && nch <= COLM_MAX_CHUNKS && col_ok(L, S, 1))
+    if (!vs && L == (int)COLM_L && nch <= COLM_MAX_CHUNKS && col_ok(L, S, 1))
         return col_multi(k, m, S, S_user, d_orig, d_rec, nch, true, s, err);
-    if (col_chunks_ok(L, nch, S, true)) {
+    if (!vs && col_chunks_ok(L, nch, S, true)) {
         // 256 / 512 / 1024-row chunks: every chunk's IFFT into Z (one
         // workgroup per quad column and chunk), then the FFT of their XOR
         ColArgs c = col_args();
@@ -992,7 +1039,7 @@ int rs16_engine::encode_high_multi(size_t k, size_t m, size_t S, size_t S_user, 
         RS16_PASS(GEN_IFFT, hi, a, nch << lo, s);
     }
     RS16_HIP(launch_xor_chunks(Z, chunk * S, nch, s));
-    return fft_to_recovery(m, S, S_user, Z, Z, d_rec, chunk, 1, 0, s, err);
+    return fft_to_recovery(m, S, S_user, Z, Z, d_rec, chunk, 1, 0, s, err, vs);
 }
 
 // LowRateEncoder::encode (src/rate/rate_low.rs:44-83): IFFT of the
@@ -1002,10 +1049,12 @@ int rs16_engine::encode_high_multi(size_t k, size_t m, size_t S, size_t S_user, 
 // are not made: the transformed chunk goes to the scratch U and the FFT's
 // first pass reads it for every chunk (PassArgs::in_rows_mask).
 int rs16_engine::encode_low_multi(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec,
-                                  uint8_t* Z, uint8_t* U, hipStream_t s, rs16_error* err) {
+                                  uint8_t* Z, uint8_t* U, hipStream_t s, rs16_error* err, const VerifySink* vs) {
     const size_t chunk = next_pow2(k);
     const uint32_t nch = (uint32_t)((m + chunk - 1) / chunk);
     const int L = ilog2(chunk), lo = L <= 8 ? L : L / 2, hi = L - lo;
+    // (a verify sink: the shapes of verify_fusable only -- none of the branches before the passes)
+    if (vs && !verify_fusable(false, k, m, S, 1)) return set_error(err, RS16_INVALID_ARGUMENT);
     if (L == 0) {  // one original: every transform is the identity, every recovery row a copy
         if (Z != d_orig) RS16_HIP(hipMemcpyAsync(Z, d_orig, S, hipMemcpyDeviceToDevice, s));
         RS16_HIP(launch_copy_chunks(Z, S, nch, s));
@@ -1074,5 +1123,5 @@ int rs16_engine::encode_low_multi(size_t k, size_t m, size_t S, size_t S_user, c
         a.lo = lo;
         RS16_PASS(GEN_IFFT, hi, a, 1u << lo, s);
     }
-    return fft_to_recovery(m, S, S_user, U, Z, d_rec, chunk, nch, (uint32_t)chunk, s, err);
+    return fft_to_recovery(m, S, S_user, U, Z, d_rec, chunk, nch, (uint32_t)chunk, s, err, vs);
 }

@@ -95,6 +95,20 @@ struct RepairTiles {
 };
 RepairTiles repair_tiles(const DecodeGeom& g);
 
+// The scrub (rs16_verify_device, fused path): where the last launch of an
+// encode compares instead of storing -- the stored recovery shards (row stride
+// S_cmp), the row flags, the column flags (nullptr: none) and the check set
+// (nullptr: every row), with the byte strides from stripe to stripe of a
+// batched launch.  The check set is shared by the stripes.
+struct VerifySink {
+    const uint8_t* cmp;
+    size_t S_cmp, bs_cmp;
+    uint8_t* rows;
+    uint8_t* cols;
+    const uint8_t* checked;
+    size_t bs_rows, bs_cols;
+};
+
 }  // namespace rs16
 
 struct rs16_encoder;
@@ -265,7 +279,13 @@ struct rs16_engine {
     // S = row width worked on (a column slice of the caller's arrays when
     // S < S_user), S_user = row stride of d_orig / d_rec (Z: stride S).
     int encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec, uint8_t* Z,
-                          hipStream_t s, rs16_error* err, size_t nstripes = 1, size_t bs_orig = 0, size_t bs_rec = 0);
+                          hipStream_t s, rs16_error* err, size_t nstripes = 1, size_t bs_orig = 0, size_t bs_rec = 0,
+                          const rs16::VerifySink* vs = nullptr);
+    // vs (here and in the multi-chunk encoders): the last launch is the
+    // comparing program (ENC_SINGLE_VFY / ENC_LAST_VFY) on the sink, d_rec is
+    // not used, and the work rows keep the shards' form; only for the shapes
+    // of verify_fusable (others: RS16_INVALID_ARGUMENT, nothing launched).
+    bool verify_fusable(bool high, size_t k, size_t m, size_t S, size_t nstripes) const;
     // Fused decode (both rates): seg_a / seg_b gather sources with device
     // flags; lost originals written to rest; Z, U work (n rows each; Z may
     // alias the sources when they live at their work positions).
@@ -330,12 +350,13 @@ struct rs16_engine {
     // S_user, Z is the work space (work_count x S; may be d_orig), the
     // recovery rows [0, m) go to d_rec (pitch S_user; may be Z).
     int encode_high_multi(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec,
-                          uint8_t* Z, hipStream_t s, rs16_error* err);
+                          uint8_t* Z, hipStream_t s, rs16_error* err, const rs16::VerifySink* vs = nullptr);
     // U: chunk x S bytes for the transformed originals, owned by the call's
     // stream (the engine's ws_u on the engine-ordered paths, a slot's own
     // buffer on concurrent slots); required -- there is no fallback.
     int encode_low_multi(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec,
-                         uint8_t* Z, uint8_t* U, hipStream_t s, rs16_error* err);
+                         uint8_t* Z, uint8_t* U, hipStream_t s, rs16_error* err, const rs16::VerifySink* vs = nullptr);
     int fft_to_recovery(size_t m, size_t S, size_t S_user, const uint8_t* src, uint8_t* Z, uint8_t* d_rec,
-                        size_t chunk, uint32_t nch, uint32_t skew, hipStream_t s, rs16_error* err);
+                        size_t chunk, uint32_t nch, uint32_t skew, hipStream_t s, rs16_error* err,
+                        const rs16::VerifySink* vs = nullptr);
 };

@@ -158,6 +158,14 @@ enum ProfId : int {
     DEC_SINGLE_SEL,       // gather*e -> IFFT -> formal derivative -> FFT -> reveal the read set -> store
     PROF_DEC_TILE_LAST_SEL,  // DEC_LAST_SEL, one wave per quad column (tile_last_sel_kernel)
     PROF_COL_DEC_SEL,     // one-launch codec: the general decode restoring the read set only
+    // The scrub's programs (rs16_verify_device; rs16_pass_verify.hip), beside the
+    // select's: the encoder's last pass and its one-pass form comparing the
+    // rows they would store with the stored recovery shards (launch_pass takes
+    // them), and the compare kernel of the encode + compare path
+    // (rs16_verify_cmp.hip).
+    ENC_LAST_VFY,         // load -> FFT -> compare rows < out_rows with the stored ones, flag the differences
+    ENC_SINGLE_VFY,       // gather -> IFFT -> FFT -> compare rows < out_rows, flag the differences
+    PROF_VERIFY_CMP,      // rows of the re-encoded recovery against the caller's recovery array, flags only
     // The repair's programs (rs16_repair_device; rs16_pass_repair.hip), behind
     // every other id.  The first two are pass programs with kernels
     // (launch_pass takes them), the third is the copy kernel of the
@@ -169,6 +177,7 @@ enum ProfId : int {
 };
 constexpr bool repair_prog(int prog) { return prog == DEC_LAST_ALL || prog == DEC_SINGLE_ALL; }
 constexpr bool select_prog(int prog) { return prog == DEC_LAST_SEL || prog == DEC_SINGLE_SEL; }
+constexpr bool verify_prog(int prog) { return prog == ENC_LAST_VFY || prog == ENC_SINGLE_VFY; }
 
 struct PassArgs {
     uint8_t* out;              // plain store base (row 0 of the transform)
@@ -316,6 +325,22 @@ struct PassArgs {
     // points share one read set among the stripes: 0).  Read by no other program.
     const uint8_t* wanted;
     uint64_t bs_wanted;
+    // The scrub's programs (ENC_LAST_VFY / ENC_SINGLE_VFY) store no row: row r <
+    // out_rows, as computed, is compared with the stored row at vfy_cmp + r
+    // vfy_S (the address of the recovery store with vfy_cmp in place of out;
+    // stripe s at + s bs_vfy_cmp), and a lane whose quad differs stores the byte
+    // 1 to vfy_rows[r] and, when vfy_cols is given, to vfy_cols[b] of the quad's
+    // 64-byte block b (stripe s at + s bs_vfy_rows / bs_vfy_cols bytes; the
+    // caller clears both arrays first).  vfy_checked (nullptr: every row): one
+    // byte per row, 0 = the row is neither read nor compared (stripe s at + s
+    // bs_vfy_checked; the entry points share one set among the stripes: 0).
+    // Read by no other program.
+    const uint8_t* vfy_cmp;
+    uint64_t vfy_S, bs_vfy_cmp;
+    uint8_t* vfy_rows;
+    uint8_t* vfy_cols;
+    const uint8_t* vfy_checked;
+    uint64_t bs_vfy_rows, bs_vfy_cols, bs_vfy_checked;
 };
 
 // n / d for any 32-bit n without a division or a branch: the high 64 bits of
@@ -431,6 +456,8 @@ enum DiagFlags : int {
     DIAG_NO_LATE_ROWS = 4096,  // every wave-staged pass as pass_kernel (no pass_kernel_late; PassConsts::late_rows = 0)
     DIAG_NO_PAIRED_ROWS = 8192, // the work buffer's rows in the reference form in every sequence (z_form_sequence: Z_SHARD)
     DIAG_NO_TOWER_ROWS = 16384, // paired rows stay in Cantor coordinates (z_form_sequence: at most Z_PAIRED; the 9-lookup narrow multiply)
+    DIAG_NO_FUSED_VERIFY = 32768,    // rs16_verify_device: always the encode into the engine's buffer + the compare kernel
+    DIAG_FORCE_FUSED_VERIFY = 65536, // ... the comparing last pass wherever the encode ends in a pass with such a kernel
 };
 
 constexpr size_t RS16_ZERO_BYTES = 65536;
@@ -495,6 +522,16 @@ hipError_t launch_formal_derivative(uint8_t* out, const uint8_t* in, size_t shar
 // was received and is not written), for nstripes stripes sharing the flags.
 hipError_t launch_repair_copy(uint8_t* dst, const uint8_t* src, const uint8_t* flags, uint32_t rows, uint64_t S,
                               uint64_t bs_dst, uint64_t bs_src, uint32_t nstripes, hipStream_t s);
+// The scrub's encode + compare path (rs16_verify_cmp.hip): row r < rows of enc
+// (the engine's encode; stride S, stripe stride bs_enc) against row r of rec
+// (the stored shards; stride S, stripe stride bs_rec) for every r whose byte
+// checked[r] is nonzero (checked nullptr: every r), for nstripes stripes sharing
+// the check set.  A lane that finds a difference stores 1 to row_flags[r] and,
+// when col_flags is given, to col_flags[b] of each 64-byte block b it found one
+// in (stripe s at + s bs_rows / bs_cols bytes).  Nothing else is written.
+hipError_t launch_verify_cmp(const uint8_t* enc, const uint8_t* rec, const uint8_t* checked, uint8_t* row_flags,
+                             uint8_t* col_flags, uint32_t rows, uint64_t S, uint64_t bs_enc, uint64_t bs_rec,
+                             uint64_t bs_rows, uint64_t bs_cols, uint32_t nstripes, hipStream_t s);
 
 // Delta update of recovery shards (rs16_update.hip): rec[r] ^= sum over
 // e < n of delta[e] * (table of entry idx[(row0 + r) n + e]) for r < rows.

@@ -8,7 +8,8 @@
 // (rs16_pass_enc.hip, rs16_pass_dec.hip; rs16_pass_tower.hip for the tower
 // flavours pass_kernel_late_tower; rs16_pass_repair.hip for the repair's
 // programs, pass_kernel_repair; rs16_pass_select.hip for the selective
-// decode's, pass_kernel_select); launch_pass (rs16_pass_launch.hip)
+// decode's, pass_kernel_select; rs16_pass_verify.hip for the scrub's,
+// pass_kernel_verify); launch_pass (rs16_pass_launch.hip)
 // reaches the kernels through their PassKernel lookups.
 //
 // Structure of one pass
@@ -82,7 +83,10 @@ enum LoadMode { LD_PLAIN = 0, LD_GATHER_ENC, LD_GATHER_DEC, LD_DEC_LAST };
 // segments, each stored to its own segment's array (PassArgs::rest / rest_b).
 // ST_RESTORE_SEL (the selective decode's programs): ST_RESTORE for the lost
 // originals of the read set only (PassArgs::wanted); the addresses are ST_RESTORE's.
-enum StoreMode { ST_PLAIN = 0, ST_RECOVERY, ST_RESTORE, ST_RESTORE_ALL, ST_RESTORE_SEL };
+// ST_VERIFY (the scrub's programs): ST_RECOVERY's rows and addresses on the
+// stored recovery array (PassArgs::vfy_cmp), which is loaded and compared with
+// the computed row; only flag bytes are stored (verify_rows).
+enum StoreMode { ST_PLAIN = 0, ST_RECOVERY, ST_RESTORE, ST_RESTORE_ALL, ST_RESTORE_SEL, ST_VERIFY };
 constexpr bool st_restores(int st) { return st == ST_RESTORE || st == ST_RESTORE_ALL || st == ST_RESTORE_SEL; }
 // the row predicate of a restoring store mode (row_wanted)
 constexpr int st_row_rule(int st) { return st == ST_RESTORE_ALL ? ROWS_ALL : (st == ST_RESTORE_SEL ? ROWS_SEL : ROWS_LOST); }
@@ -116,6 +120,8 @@ RS16_PROG(DEC_LAST_ALL, LD_DEC_LAST, false, false, true, ST_RESTORE_ALL)
 RS16_PROG(DEC_SINGLE_ALL, LD_GATHER_DEC, true, true, true, ST_RESTORE_ALL)
 RS16_PROG(DEC_LAST_SEL, LD_DEC_LAST, false, false, true, ST_RESTORE_SEL)
 RS16_PROG(DEC_SINGLE_SEL, LD_GATHER_DEC, true, true, true, ST_RESTORE_SEL)
+RS16_PROG(ENC_LAST_VFY, LD_PLAIN, false, false, true, ST_VERIFY)
+RS16_PROG(ENC_SINGLE_VFY, LD_GATHER_ENC, true, false, true, ST_VERIFY)
 #undef RS16_PROG
 
 // Row bits in registers: 4 (16 rows per thread) from T = 6 on; 3 at T = 5
@@ -1595,6 +1601,40 @@ __device__ __forceinline__ gbyte* restore_all_ptr(const PassArgs& a, const Thr& 
                         cs.offL);
     }
 }
+// ST_VERIFY (the scrub's programs): row registers m0 .. m0 + N - 1 of an item
+// against the stored recovery rows.  A row is compared when the lane holds a
+// quad, the row lies below out_rows and its byte of the check set (if any) is
+// nonzero -- the byte is read for rows below out_rows only, and the stored array
+// for compared rows only: every other lane reads the zero page in its place
+// (ld_sel: the array has out_rows rows and a slab may be wider than the shard),
+// so the N requests go out together, ahead of the first compare.  A lane whose
+// quad differs stores 1 to its row's flag and to the flag of the quad's 64-byte
+// block (offL = (Qg >> 3) * 64 + (Qg & 7) * 4 of quad Qg: block Qg >> 3 = offL
+// >> 6).  Several lanes and workgroups may store the same byte, all the value 1.
+template <int P, int T, bool V32, int N>
+__device__ __forceinline__ void verify_rows(const PassArgs& a, const Thr& cs, const uint32_t (&L)[Geo<T>::NR],
+                                            const uint32_t (&H)[Geo<T>::NR], int m0) {
+    static_assert(ProgTraits<P>::STORE == ST_VERIFY && ProgTraits<P>::FFT, "the scrub's programs end in layout A");
+    const uint32_t lr = lane_rows<T, false>(cs, a);
+    const WaveRows<T, false> wr(cs, a);
+    const LaneOff<V32> lo(lr, a.vfy_S, cs.offL);
+    bool ok[N];
+    uint32_t sl[N], sh[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        const uint32_t ur = wr(m0 + i);
+        ok[i] = cs.active & row_below(ur, lr, a.out_rows);
+        if (a.vfy_checked) ok[i] = ok[i] && a.vfy_checked[ur + lr] != 0;
+        ld_sel(a, lo.at(sgpr_ptr(a.vfy_cmp + (uint64_t)ur * a.vfy_S)), ok[i], cs.offL, sl[i], sh[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        if (ok[i] & (((sl[i] ^ L[m0 + i]) | (sh[i] ^ H[m0 + i])) != 0)) {
+            a.vfy_rows[wr(m0 + i) + lr] = 1;
+            if (a.vfy_cols) a.vfy_cols[cs.offL >> 6] = 1;
+        }
+    }
+}
 // The store of row register m of an item (the counterpart of load_rows): recovery / work rows as they are, lost originals revealed
 // (x (65535 - e), rate_high.rs:236-242) into the caller's original array.
 template <int P, int T, bool V32>
@@ -1615,6 +1655,7 @@ __device__ __forceinline__ void store_row(const PassArgs& a, const Thr& cs, uint
         const LaneOff<V32> lo(lr, a.S_out, cs.offL);
         st_ptr<NT>(lo.at(sgpr_ptr(a.out + (uint64_t)ur * a.S_out)), cs.active & row_below(ur, lr, a.out_rows), L, H);
     } else {
+        static_assert(st_restores(PT::STORE), "ST_VERIFY stores no row: verify_rows");
         // lost original row r -> restored-originals row r + row_base_out - (segment start)
         const LaneOff<V32> lo(lr, a.S_rest, cs.offL);
         const int64_t shift = (int64_t)a.row_base_out - (a.rest_seg_b ? (int64_t)a.chunk : 0);
@@ -1638,8 +1679,12 @@ __device__ __forceinline__ void store_row(const PassArgs& a, const Thr& cs, uint
 template <int P, int T, bool V32>
 __device__ __forceinline__ void store_rows(const PassArgs& a, const Thr& cs, const uint32_t (&L)[Geo<T>::NR],
                                            const uint32_t (&H)[Geo<T>::NR], const uint4* rvt, const uint32_t* lostf) {
+    if constexpr (ProgTraits<P>::STORE == ST_VERIFY) {
+        verify_rows<P, T, V32, Geo<T>::NR>(a, cs, L, H, 0);
+    } else {
 #pragma unroll
-    for (int m = 0; m < Geo<T>::NR; m++) store_row<P, T, V32>(a, cs, L[m], H[m], m, rvt, lostf);
+        for (int m = 0; m < Geo<T>::NR; m++) store_row<P, T, V32>(a, cs, L[m], H[m], m, rvt, lostf);
+    }
 }
 // Early stores: the last FFT block in layout A runs depth-first (LayerSeq),
 // so rows m, m + 1 are final as soon as their layer-0 group is done; this
@@ -1653,7 +1698,11 @@ template <int P, int T, bool PAIR = false> struct EarlyStore {
     const FastStore<P, T, PAIR> fs;
     __device__ __forceinline__ void operator()(const uint32_t (&L)[Geo<T>::NR], const uint32_t (&H)[Geo<T>::NR],
                                                int m) const {
-        if (PAIR || fs.on) {
+        if constexpr (ProgTraits<P>::STORE == ST_VERIFY) {
+            // (the stored quads of both rows requested, then compared)
+            if (a.voff32) verify_rows<P, T, true, 2>(a, cs, L, H, m);
+            else verify_rows<P, T, false, 2>(a, cs, L, H, m);
+        } else if (PAIR || fs.on) {
             fs.row(m, L[m], H[m]);
             fs.row(m + 1, L[m + 1], H[m + 1]);
         } else if (a.voff32) {
@@ -2060,6 +2109,16 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
 // RS16_PASS_HEAD (`a`, `G` in scope; leaves c, tile, slab, rcn): the item of
 // this workgroup (launch_pass: one per workgroup), its thread coordinates,
 // with batched stripes the stripe's arrays and the tile within the stripe.
+// (The scrub's arrays are displaced here, for its programs alone: stripe_displace,
+// which the small kernels call too, stays as it is.)
+template <int P> __device__ __forceinline__ void verify_displace(PassArgs& a, uint32_t st) {
+    if constexpr (ProgTraits<P>::STORE == ST_VERIFY) {
+        a.vfy_cmp += st * a.bs_vfy_cmp;
+        a.vfy_rows += st * a.bs_vfy_rows;
+        if (a.vfy_cols) a.vfy_cols += st * a.bs_vfy_cols;
+        if (a.vfy_checked) a.vfy_checked += st * a.bs_vfy_checked;
+    }
+}
 #define RS16_PASS_HEAD(P, T) \
     const uint32_t item = blockIdx.x; \
     Thr c; \
@@ -2077,6 +2136,7 @@ __device__ __forceinline__ void process_item(const PassArgs& a, const Thr& c, ui
         first_stripe = st == 0; \
         tile -= st * a.stripe_tiles; \
         stripe_displace(a, st); \
+        verify_displace<P>(a, st); \
     } \
     tile += a.tile_base; \
     c.b_low = tile & ((1u << a.lo) - 1); \

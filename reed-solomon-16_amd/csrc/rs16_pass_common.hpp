@@ -66,6 +66,7 @@ PassFn pass_kernels_tower(int prog, int T, int nv);    // rs16_pass_tower.hip: t
 PassFn pass_kernel_tower_wide3(int prog, int T);       // rs16_pass_tower.hip: PassKernel::wide3 (nullptr: none)
 PassKernel pass_kernels_repair(int prog, int T);       // rs16_pass_repair.hip: DEC_LAST_ALL, DEC_SINGLE_ALL (no narrow variants)
 PassKernel pass_kernels_select(int prog, int T);       // rs16_pass_select.hip: DEC_LAST_SEL, DEC_SINGLE_SEL (no narrow variants)
+PassKernel pass_kernels_verify(int prog, int T);       // rs16_pass_verify.hip: ENC_LAST_VFY, ENC_SINGLE_VFY (no narrow variants)
 
 #if defined(__HIPCC__) || defined(__HIP__)
 // ---------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // rs16_pass_launch.hip -- launch_pass: which pass kernel a launch takes and
 // how it is launched.  The kernels themselves are instantiated in
-// rs16_pass_enc.hip, rs16_pass_dec.hip, rs16_pass_tower.hip, rs16_pass_repair.hip
-// and rs16_pass_select.hip (template:
+// rs16_pass_enc.hip, rs16_pass_dec.hip, rs16_pass_tower.hip, rs16_pass_repair.hip,
+// rs16_pass_select.hip and rs16_pass_verify.hip (template:
 // rs16_pass.hpp); this unit sees them through the PassKernel lookups only.
 #include <algorithm>
 
@@ -45,6 +45,15 @@ struct SelectTable {
             for (int T = 0; T <= 8; T++) k[p][T] = pass_kernels_select(DEC_LAST_SEL + p, T);
     }
 };
+// The scrub's programs (rs16_pass_verify.hip), likewise.
+struct VerifyTable {
+    PassKernel k[2][9], none{};
+    VerifyTable() {
+        static_assert(ENC_SINGLE_VFY == ENC_LAST_VFY + 1, "the table's rows");
+        for (int p = 0; p < 2; p++)
+            for (int T = 0; T <= 8; T++) k[p][T] = pass_kernels_verify(ENC_LAST_VFY + p, T);
+    }
+};
 static const PassKernel& find_kernel(int prog, int T, int nv) {
     if (repair_prog(prog)) {
         static const RepairTable repair;
@@ -53,6 +62,10 @@ static const PassKernel& find_kernel(int prog, int T, int nv) {
     if (select_prog(prog)) {
         static const SelectTable select;
         return nv == 0 ? select.k[prog - DEC_LAST_SEL][T] : select.none;
+    }
+    if (verify_prog(prog)) {
+        static const VerifyTable verify;
+        return nv == 0 ? verify.k[prog - ENC_LAST_VFY][T] : verify.none;
     }
     static const KernelTable table;
     return table.k[prog][T][nv];
@@ -77,7 +90,8 @@ PassConsts pass_launch_consts(const PassKernel& k, int T, const PassArgs& a) {
     c.nslab = (a.qrow + k.quads - 1) / k.quads;
     {
         const uint64_t hws = k.quads >= 64 ? 1 : 64 / k.quads;
-        const uint64_t smax = std::max(std::max(a.S_in, a.S_out), std::max(a.S_seg, a.S_rest));
+        // (vfy_S: the stored rows the scrub's programs compare with, 0 in every other launch)
+        const uint64_t smax = std::max(std::max(std::max(a.S_in, a.S_out), std::max(a.S_seg, a.S_rest)), a.vfy_S);
         const uint64_t span = (uint64_t)1 << (T + a.lo);  // rows of one tile's aligned block
         // A lane's byte offset below its wave's row base is lane_rows x S +
         // offL (rs16_pass.hpp LaneOff): lane_rows, the rows from the wave's
@@ -156,10 +170,12 @@ ZForm z_form_sequence(uint32_t chunk_rows, uint64_t S, uint64_t S_user, uint32_t
 }
 
 hipError_t launch_pass(int prog, int T, const PassArgs& args, uint32_t num_tiles, hipStream_t s) {
-    const bool appended = repair_prog(prog) || select_prog(prog);  // (the programs behind the profiling ids)
+    const bool appended = repair_prog(prog) || select_prog(prog) || verify_prog(prog);  // (the programs behind the profiling ids)
     if (prog < 0 || (prog >= NUM_PROGS && !appended) || T < 0 || T > 8) return hipErrorInvalidValue;
-    if (appended && !find_kernel(prog, T, 0).fn) return hipErrorInvalidValue;  // (DEC_LAST_*: T >= 4, DEC_SINGLE_*: T >= 1)
+    if (appended && !find_kernel(prog, T, 0).fn) return hipErrorInvalidValue;  // (*_LAST_*: T >= 4, *_SINGLE_*: T >= 1)
     if (select_prog(prog) && !args.wanted) return hipErrorInvalidValue;  // (the read set is dereferenced)
+    // (the stored rows and the row flags are dereferenced)
+    if (verify_prog(prog) && (!args.vfy_cmp || !args.vfy_rows)) return hipErrorInvalidValue;
     if (num_tiles == 0 || args.qrow == 0) return hipSuccess;
     PassArgs a = args;
     // Narrow twiddles: the launch's tiles are tile_base + [0, tiles of one

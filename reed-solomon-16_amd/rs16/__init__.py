@@ -30,9 +30,11 @@ __all__ = [
     "RATE_DEFAULT", "RATE_HIGH", "RATE_LOW", "GF_ORDER", "GF_MODULUS", "set_diagnostics",
     "DIAG_FORCE_VOFF64", "DIAG_EVAL_TWO_KERNEL", "DIAG_EVAL_FULL", "DIAG_NO_COLUMN", "DIAG_FORCE_COLUMN",
     "DIAG_TILE_LAST", "DIAG_NO_TILE_LAST", "DIAG_FD_LDS", "DIAG_COL_RADIX4", "DIAG_NO_IDENTITY", "DIAG_NO_MID_DIRECT", "DIAG_WIDE_TWIDDLES", "DIAG_NO_LATE_ROWS", "DIAG_NO_PAIRED_ROWS", "DIAG_NO_TOWER_ROWS", "encode_host", "decode_host",
+    "DIAG_NO_FUSED_VERIFY", "DIAG_FORCE_FUSED_VERIFY",
     "encode_host_batch", "decode_host_batch", "decode_prepare", "decode_device_prepared",
     "repair_device", "repair_device_batch", "repair_path",
     "decode_device_select", "decode_device_select_batch", "select_path",
+    "verify_device", "verify_device_batch", "verify", "verify_path",
     "UpdatePlan", "update_recovery_device", "UPDATE_MAX_SHARDS",
     "encode_host_multi", "decode_host_multi", "Comm", "column_slice", "scatter_columns", "gather_columns",
 ]
@@ -47,6 +49,8 @@ DIAG_WIDE_TWIDDLES = 2048
 DIAG_NO_LATE_ROWS = 4096
 DIAG_NO_PAIRED_ROWS = 8192
 DIAG_NO_TOWER_ROWS = 16384
+DIAG_NO_FUSED_VERIFY = 32768
+DIAG_FORCE_FUSED_VERIFY = 65536
 # Test convenience only: the flags set_diagnostics() without an engine gave
 # every live engine, and that engines created later in this Python process
 # start with.  The library itself keeps the switches per engine.
@@ -782,6 +786,83 @@ def select_path(original_count, recovery_count, original_received_count, recover
     decode, -1 the call fails; host arithmetic, no device."""
     return lib().rs16_host_select_path(original_count, recovery_count, original_received_count,
                                        recovery_received_count, wanted_count)
+
+
+def _dev_ptr(x):
+    """A device address from None, an int, a DeviceArray or anything with data_ptr()."""
+    if x is None:
+        return None
+    return x.ptr if hasattr(x, "ptr") else Engine._ptr(x)
+
+
+def verify_device(original_count, recovery_count, shard_bytes, d_original, d_recovery, d_recovery_mismatch,
+                  d_column_mismatch=None, d_recovery_checked=None, stream=None, engine: Optional[Engine] = None):
+    """rs16_verify_device: the scrub of one stripe.  d_recovery_mismatch
+    (recovery_count device bytes) gets 1 for every checked recovery shard that
+    differs from the encode of d_original, d_column_mismatch (shard_bytes / 64
+    bytes, or None) 1 for every 64-byte column block with a difference;
+    d_recovery_checked (recovery_count bytes, 0 = skip the slot; None: all).
+    Pointers or DeviceArrays; both shard arrays are read only."""
+    eng = engine or default_engine()
+    err = RS16Error()
+    _check(lib().rs16_verify_device(eng.h, original_count, recovery_count, shard_bytes, _dev_ptr(d_original),
+                                    _dev_ptr(d_recovery), _dev_ptr(d_recovery_checked),
+                                    _dev_ptr(d_recovery_mismatch), _dev_ptr(d_column_mismatch), stream,
+                                    C.byref(err)), err)
+
+
+def verify_device_batch(original_count, recovery_count, shard_bytes, nstripes, d_original, original_stride,
+                        d_recovery, recovery_stride, d_recovery_mismatch, recovery_mismatch_stride,
+                        d_column_mismatch=None, column_mismatch_stride=0, d_recovery_checked=None, stream=None,
+                        engine: Optional[Engine] = None):
+    """rs16_verify_device_batch: nstripes stripes with one shared check set;
+    stripe i's flags at + i * recovery_mismatch_stride / column_mismatch_stride."""
+    eng = engine or default_engine()
+    err = RS16Error()
+    _check(lib().rs16_verify_device_batch(eng.h, original_count, recovery_count, shard_bytes, nstripes,
+                                          _dev_ptr(d_original), original_stride, _dev_ptr(d_recovery),
+                                          recovery_stride, _dev_ptr(d_recovery_checked),
+                                          _dev_ptr(d_recovery_mismatch), recovery_mismatch_stride,
+                                          _dev_ptr(d_column_mismatch), column_mismatch_stride, stream,
+                                          C.byref(err)), err)
+
+
+def verify_path(original_count, recovery_count, shard_bytes, nstripes=1, diag=0):
+    """rs16_host_verify_path: 0 encode + compare, 1 the fused path, -1 the shape
+    is not supported, on an engine with the diagnostic switches `diag`; host
+    arithmetic, no device."""
+    return lib().rs16_host_verify_path(original_count, recovery_count, shard_bytes, nstripes, diag)
+
+
+def verify(original_count: int, recovery_count: int, original, recovery, checked=None,
+           engine: Optional[Engine] = None):
+    """Scrub one stripe held on the host: `original` and `recovery` are sequences
+    of equal-length shards (bytes or uint8 arrays), `checked` an optional
+    sequence of recovery_count flags (0 = do not compare that slot).  Uploads,
+    runs rs16_verify_device and returns (indices of the mismatching recovery
+    shards, indices of the mismatching 64-byte column blocks) as sorted numpy
+    arrays -- both empty when the stripe is consistent."""
+    from .device import DeviceArray
+
+    eng = engine or default_engine()
+    o = np.ascontiguousarray([np.frombuffer(bytes(x), np.uint8) for x in original])
+    r = np.ascontiguousarray([np.frombuffer(bytes(x), np.uint8) for x in recovery])
+    if o.ndim != 2 or r.ndim != 2 or o.shape[0] != original_count or r.shape[0] != recovery_count or \
+            o.shape[1] != r.shape[1]:
+        raise Error("InvalidArgument")
+    shard_bytes = o.shape[1]
+    d_o, d_r = DeviceArray.from_numpy(eng, o), DeviceArray.from_numpy(eng, r)
+    d_rows, d_cols = DeviceArray(eng, recovery_count), DeviceArray(eng, max(shard_bytes // 64, 1))
+    d_chk = None
+    if checked is not None:
+        chk = np.asarray(checked)
+        if chk.shape != (recovery_count,):
+            raise Error("InvalidArgument")
+        d_chk = DeviceArray.from_numpy(eng, (chk != 0).astype(np.uint8))
+    verify_device(original_count, recovery_count, shard_bytes, d_o, d_r, d_rows, d_cols, d_chk, engine=eng)
+    rows = d_rows.download()[:recovery_count]
+    cols = d_cols.download()[:shard_bytes // 64]
+    return np.flatnonzero(rows), np.flatnonzero(cols)
 
 
 def decode_prepare(original_count, recovery_count, shard_bytes, d_original_received, d_recovery_received,

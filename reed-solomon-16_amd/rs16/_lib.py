@@ -119,6 +119,9 @@ SIGNATURES = {
     "rs16_decode_device_select_batch": (_i, [_p, _sz, _sz, _sz, _sz, _p, _sz, _p, _p, _p, _sz, _p, _sz, _sz, _sz, _p,
                                              _e]),
     "rs16_host_select_path": (_i, [_sz, _sz, _sz, _sz, _sz]),
+    "rs16_verify_device": (_i, [_p, _sz, _sz, _sz, _p, _p, _p, _p, _p, _p, _e]),
+    "rs16_verify_device_batch": (_i, [_p, _sz, _sz, _sz, _sz, _p, _sz, _p, _sz, _p, _p, _sz, _p, _sz, _p, _e]),
+    "rs16_host_verify_path": (_i, [_sz, _sz, _sz, _sz, _i]),
     "rs16_decode_check": (_i, [_p, _p, _e]),
     "rs16_device_alloc": (_p, [_p, _sz, _e]),
     "rs16_device_free": (None, [_p, _p]),
