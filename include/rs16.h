@@ -452,8 +452,8 @@ int rs16_decode_device_select_batch(rs16_engine* eng, size_t original_count, siz
  * pair of arrays tells "one recovery shard rotted" (one row, few columns) from
  * "an original rotted" (many rows at the same columns).  Neither output array
  * needs alignment; no byte outside them is written.  There is no count and no
- * "which original is bad": locating a corrupt original is syndrome decoding,
- * which this library does not do.
+ * "which original is bad" here: rs16_locate_device below names the one corrupt
+ * shard of each column block.
  * The call is asynchronous on `stream` and ordered on the engine's scratch like
  * an encode.  Like rs16_encode_device it is not a decode: it neither discards a
  * pending rs16_decode_prepare nor changes what rs16_decode_check reports.
@@ -522,6 +522,115 @@ int rs16_verify_device_batch(rs16_engine* eng, size_t original_count, size_t rec
                              const void* d_recovery, size_t recovery_stride, const uint8_t* d_recovery_checked,
                              uint8_t* d_recovery_mismatch, size_t recovery_mismatch_stride,
                              uint8_t* d_column_mismatch, size_t column_mismatch_stride, void* stream, rs16_error* err);
+/* Locate: which ONE shard of each 64-byte column block is corrupt.  The scrub
+ * above says that a stripe is inconsistent; this call says which shard to
+ * distrust, per column block, and by what to XOR it to make the block
+ * consistent again -- what a caller needs to fix a silently rotted shard in
+ * place, or to set the received flags of rs16_repair_device.  The case is one
+ * device rotting silently: one corrupt shard per codeword.  No reference
+ * counterpart (the reference has erasure decoding only).
+ * The encode is GF(2^16)-linear per element position, recovery_j = sum_i
+ * M[j][i] original_i, and the code is MDS.  With syndrome_j = encode(stored
+ * originals)_j ^ stored recovery_j: one corrupt recovery shard j makes exactly
+ * syndrome_j nonzero; one corrupt original i with error e makes every syndrome
+ * nonzero, syndrome_j = M[j][i] e, and syndrome_0 / syndrome_1 = M[0][i] /
+ * M[1][i] names i, because every 2 x 2 minor of M is nonzero.
+ *
+ * A plan is per (rate, original_count, recovery_count) and holds rows 0 and 1
+ * of M on the device as logs, a table ratio -> i and the field's log / exp
+ * tables.  `rate` means what it means for rs16_update_plan_new: the rate the
+ * stripe was encoded with, RS16_RATE_DEFAULT = the choice of rs16_encode_device.
+ * rs16_locate_plan_new is synchronous: the two rows come from the engine's own
+ * encode of unit vectors (exact on every rate path) -- original i carries the
+ * element 1 at element position i of a stripe of 64 ceil(original_count / 32)
+ * bytes per shard, taken in column chunks of 1 KiB shards (512 originals each,
+ * 64 encodes at 32768:32768), of which only recovery rows 0 and 1 are copied
+ * back.  Errors, in this order: UnsupportedShardCount as rs16_validate gives it
+ * for `rate`; recovery_count < 2: InvalidArgument (distance 2 detects an error
+ * and cannot locate it).  Like an update plan, a locate plan is attached to its
+ * engine and detached by rs16_engine_free: later calls on it fail with
+ * RS16_INVALID_ARGUMENT and rs16_locate_plan_free then frees only host memory.
+ * Calls enqueued on a caller's stream must have finished before the plan or its
+ * engine is freed (the kernels read the plan's tables).
+ *
+ * rs16_locate_device fills one entry per 64-byte column block c < B =
+ * shard_bytes / 64; every entry is written, whatever it held before:
+ *   RS16_LOCATE_CLEAN        every recovery shard equals the encode in this
+ *                            block.  d_block_shard[c] = 0xFFFFFFFF, fix = 0.
+ *   RS16_LOCATE_RECOVERY     d_block_shard[c] = j: every inconsistent element
+ *                            of the block has exactly one nonzero syndrome, in
+ *                            the same row j.  The fix is row j's syndrome bytes
+ *                            of this block.
+ *   RS16_LOCATE_ORIGINAL     d_block_shard[c] = i: every inconsistent element
+ *                            of the block is explained by an error in original i
+ *                            alone -- verified against all recovery_count
+ *                            recovery shards, not only rows 0 and 1.  The fix is
+ *                            the error in the shard layout, 32 low bytes then 32
+ *                            high bytes.
+ *   RS16_LOCATE_UNLOCATABLE  anything else: 2 .. recovery_count - 1 nonzero
+ *                            syndromes at an element, a ratio no original has, a
+ *                            candidate that fails the check against all rows,
+ *                            elements of one block that name different shards.
+ *                            d_block_shard[c] = 0xFFFFFFFF, fix = 0.
+ * d_block_fix may be NULL; if given it is B x 64 bytes: XOR block c of it into
+ * bytes [64 c, 64 c + 64) of the named shard and the block is consistent.
+ * Guarantee: a block in which at most recovery_count - 1 shards are corrupt at
+ * any one element position is never attributed to a wrong shard -- it is
+ * located when that number is 1 and (elements that disagree aside) reported
+ * UNLOCATABLE otherwise.  This follows from the code's minimum distance
+ * recovery_count + 1: two error patterns with the same syndromes differ by a
+ * codeword, which has at least recovery_count + 1 nonzero shards.  At
+ * recovery_count = 2 it covers exactly one corrupt shard: two corrupt shards at
+ * one element position can look like a third, and the call then names it.
+ * Both shard arrays are READ ONLY and 64-byte aligned like every other device
+ * shard array.  d_block_status, d_block_shard and d_block_fix need only their
+ * natural alignment; no byte outside them is written.
+ * The call is asynchronous on `stream` and ordered on the engine's scratch like
+ * rs16_verify_device: it is not a decode, it neither discards a pending
+ * rs16_decode_prepare nor changes what rs16_decode_check reports.  Column
+ * slices (rs16_engine_set_slices) do not apply.
+ * Errors, in this order: a NULL or detached plan: InvalidArgument;
+ * InvalidShardSize as rs16_validate gives it; a NULL or misaligned shard array,
+ * a NULL d_block_status or d_block_shard: InvalidArgument.
+ * The sequence on the device: the engine's encode of d_original into a buffer of
+ * its own (as the scrub's path 0); a scan of all recovery_count rows that
+ * counts, per element position, the rows with a nonzero syndrome element and
+ * keeps the smallest such row; a decide kernel that classifies each block and
+ * scatters each ORIGINAL candidate's error e = syndrome_0 / M[0][i] into a
+ * zeroed original_count x shard_bytes error array E of the engine; the engine's
+ * encode of E; and a confirm kernel that downgrades an ORIGINAL block to
+ * UNLOCATABLE unless encode(E) equals the syndrome in all recovery_count rows of
+ * the block.  The engine keeps E, both encodes and the counts: (original_count +
+ * 2 recovery_count) x shard_bytes beside the encode's work space.
+ * Not provided: a batch form, host-memory forms, more than one corrupt shard
+ * per codeword, and skipping the second encode when no block names an original
+ * (the host would have to wait for the device to know).
+ * When to prefer it (measured on one MI355X at 1 KiB shards, clean and with
+ * one original corrupted, bursts alternating with rs16_verify_device of the same
+ * stripe on the same build; DESIGN.md 3.19, profiles/r19_locate.txt): a locate
+ * costs about two encodes plus three sweeps, 1.6-2.0 x a scrub, so scrub with
+ * rs16_verify_device and call this for the stripes it flags.  At 32768:32768:
+ * 134.4 us clean and 148.4 with one original corrupted, against the scrub's 73.6
+ * and 75.0 (1.83 x / 1.98 x; 2.3 / 2.5 x an encode); of that the two encodes are
+ * about 118 us (58.9 each alone), the scan 13.9-14.6 (the scrub's compare kernel: 13.5-14.9), the
+ * decide kernel 8 and the confirm kernel 6 clean, 15.8 with a block to check
+ * (per-kernel figures under profiling, which lengthens short launches).  At
+ * 1000:1000: 24.1 us clean and 27.1 corrupted against 15.4 and 15.6 (1.56 x /
+ * 1.73 x), the three kernels at the 6-7.5 us floor of a profiled launch.
+ * rs16_locate_plan_new costs 6.0 ms of host time at 32768:32768 (64 encodes) and
+ * 0.12 ms at 1000:1000: keep the plan of a geometry that is scrubbed.  Sizes in
+ * between are not measured. */
+typedef struct rs16_locate_plan rs16_locate_plan;
+rs16_locate_plan* rs16_locate_plan_new(rs16_engine* eng, int rate, size_t original_count, size_t recovery_count,
+                                       rs16_error* err);
+void rs16_locate_plan_free(rs16_locate_plan* plan);
+/* Diagnostics / tests: out[i] = M[0][i], out[original_count + i] = M[1][i] as
+ * field elements (2 x original_count values). */
+int rs16_locate_plan_rows(rs16_locate_plan* plan, uint16_t* out, rs16_error* err);
+enum { RS16_LOCATE_CLEAN = 0, RS16_LOCATE_ORIGINAL = 1, RS16_LOCATE_RECOVERY = 2, RS16_LOCATE_UNLOCATABLE = 3 };
+int rs16_locate_device(rs16_locate_plan* plan, size_t shard_bytes, const void* d_original, const void* d_recovery,
+                       uint8_t* d_block_status, uint32_t* d_block_shard, void* d_block_fix, void* stream,
+                       rs16_error* err);
 /* Checked mode of the engine's last decode: waits for `stream` and compares
  * the received counts that decode was given with the rows the device flags
  * mark received (the eval_poly kernels count them per 64-row chunk as they

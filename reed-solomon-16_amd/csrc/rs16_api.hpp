@@ -31,11 +31,12 @@ inline int begin_ordered(rs16_engine* e, void* stream, hipStream_t* s, rs16_erro
 }
 
 // Objects created on an engine (rs16_engine::encoders / decoders /
-// update_plans): detach releases the object's device memory and clears its
+// update_plans / locate_plans): detach releases the object's device memory and clears its
 // engine; the object's free() forgets it in its engine's list.
 void detach(rs16_encoder* enc);
 void detach(rs16_decoder* dec);
 void detach(rs16_update_plan* plan);
+void detach(rs16_locate_plan* plan);
 template <class V, class T> void forget(V& v, T* x) { v.erase(std::remove(v.begin(), v.end(), x), v.end()); }
 template <class T> void free_attached(T* x, std::vector<T*> rs16_engine::*list) {
     if (!x) return;

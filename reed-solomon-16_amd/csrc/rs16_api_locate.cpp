@@ -1,0 +1,200 @@
+// rs16_api_locate.cpp -- C ABI (include/rs16.h): locating the one corrupt shard
+// of each 64-byte column block of a stripe (rs16_locate_plan,
+// rs16_locate_device).
+#include "rs16_api.hpp"
+
+using namespace rs16;
+
+// ---------------------------------------------------------------------------
+// The encode is GF(2^16)-linear per element position, recovery_j = sum_i
+// M[j][i] original_i, and the code is MDS.  With syndrome_j = encode(stored
+// originals)_j ^ stored recovery_j, one corrupt recovery shard j leaves exactly
+// syndrome_j nonzero, and one corrupt original i with error e makes every
+// syndrome nonzero, syndrome_j = M[j][i] e; then syndrome_0 / syndrome_1 =
+// M[0][i] / M[1][i] names i (every 2 x 2 minor of M is nonzero, so the k ratios
+// differ) and e = syndrome_0 / M[0][i].  A plan holds rows 0 and 1 of M as logs.
+// ---------------------------------------------------------------------------
+struct rs16_locate_plan {
+    rs16_engine* eng;  // nullptr once the engine was freed (detached)
+    bool high = false;
+    size_t k = 0, m = 0;
+    std::vector<uint16_t> rows;  // 2 k field elements: M[0][i], then M[1][i]
+    // u16 tables on the device: log (GF_ORDER), exp (GF_ORDER), ratio -> i
+    // (GF_ORDER, the last entry unused), log M[0][i] (k)
+    DevBuf tab;
+};
+
+void rs16::detach(rs16_locate_plan* p) {
+    p->tab.release();
+    p->eng = nullptr;
+}
+
+// Rows 0 and 1 of M from the engine's own encode of unit vectors, so they are
+// exact on every rate path: original i carries the element 1 at element
+// position i, i.e. in block i / 32 of a stripe of 64 ceil(k / 32)-byte shards,
+// and recovery row j returns M[j][i] there.  Taken in column chunks of at most
+// UNIT_BYTES per shard (512 originals each), so the work space stays small: the
+// unit array is cleared once, and each chunk sets its ones, encodes, copies
+// rows 0 and 1 back and clears its ones again.
+static constexpr size_t UNIT_BYTES = 1024;
+static int locate_rows(rs16_engine* e, bool high, size_t k, size_t m, std::vector<uint16_t>& rows, rs16_error* err) {
+    const size_t per = UNIT_BYTES / 2;
+    const size_t Smax = std::min(UNIT_BYTES, 64 * ((k + 31) / 32));
+    std::vector<uint8_t> rec(2 * Smax);
+    rows.assign(2 * k, 0);
+    DevBuf d_unit, d_rec;
+    auto run = [&]() -> int {
+        RS16_HIP(d_unit.reserve(k * Smax));
+        RS16_HIP(d_rec.reserve(m * Smax));
+        hipStream_t s = e->stream;
+        if (int rc = e->order(s, err)) return rc;
+        // (on the stream the ones are set on: a non-blocking stream does not wait for the null stream)
+        RS16_HIP(hipMemsetAsync(d_unit.p, 0, k * Smax, s));
+        RS16_HIP(e->ws_z.reserve(rs16_encoder_work_count(high, k, m) * Smax));
+        uint8_t* U;
+        if (int rc = engine_u(e, high, k, Smax, &U, err)) return rc;
+        for (size_t i0 = 0; i0 < k; i0 += per) {
+            const size_t n = std::min(per, k - i0), S = 64 * ((n + 31) / 32);
+            RS16_HIP(launch_locate_unit((uint8_t*)d_unit.p, S, (uint32_t)i0, (uint32_t)n, 1, s));
+            if (int rc = encode_dev(e, high, k, m, S, (const uint8_t*)d_unit.p, (uint8_t*)d_rec.p, (uint8_t*)e->ws_z.p,
+                                    U, s, err))
+                return rc;
+            RS16_HIP(launch_locate_unit((uint8_t*)d_unit.p, S, (uint32_t)i0, (uint32_t)n, 0, s));
+            RS16_HIP(hipMemcpyAsync(rec.data(), d_rec.p, 2 * S, hipMemcpyDeviceToHost, s));
+            RS16_HIP(hipStreamSynchronize(s));
+            for (size_t j = 0; j < 2; j++)
+                for (size_t q = 0; q < n; q++) {
+                    const size_t at = j * S + 64 * (q / 32) + q % 32;
+                    rows[j * k + i0 + q] = (uint16_t)(rec[at] | (uint16_t)rec[at + 32] << 8);
+                }
+        }
+        return e->scratch_done(s, err);
+    };
+    const int rc = run();
+    d_unit.release();
+    d_rec.release();
+    return rc;
+}
+
+extern "C" rs16_locate_plan* rs16_locate_plan_new(rs16_engine* eng, int rate, size_t k, size_t m, rs16_error* err) {
+    if (!eng) return set_error(err, RS16_INVALID_ARGUMENT), nullptr;
+    bool high;
+    if (resolve_rate(rate, k, m, 64, &high, err)) return nullptr;
+    // distance 2 detects an error and cannot locate it
+    if (m < 2) return set_error(err, RS16_INVALID_ARGUMENT), nullptr;
+    if (eng->activate(err)) return nullptr;
+    rs16_locate_plan* p = new (std::nothrow) rs16_locate_plan();
+    if (!p) return set_error(err, RS16_INVALID_ARGUMENT), nullptr;
+    p->eng = eng;
+    p->high = high, p->k = k, p->m = m;
+    eng->locate_plans.push_back(p);
+    auto build = [&]() -> int {
+        if (int rc = locate_rows(eng, high, k, m, p->rows, err)) return rc;
+        const HostTables& t = host_tables();
+        std::vector<uint16_t> tab(3 * (size_t)GF_ORDER + k);
+        std::copy(t.log.begin(), t.log.end(), tab.begin());
+        std::copy(t.exp.begin(), t.exp.end(), tab.begin() + GF_ORDER);
+        uint16_t* ratio = tab.data() + 2 * (size_t)GF_ORDER;
+        uint16_t* log_m0 = ratio + GF_ORDER;
+        std::fill(ratio, ratio + GF_ORDER, (uint16_t)0xFFFF);
+        for (size_t i = 0; i < k; i++) {
+            const uint16_t a = p->rows[i], b = p->rows[k + i];
+            // what the method rests on (MDS: no zero entry, no singular 2 x 2 minor)
+            if (a == 0 || b == 0) return set_error(err, RS16_INVALID_ARGUMENT);
+            const uint32_t la = t.log[a], lb = t.log[b];
+            const uint32_t d = la >= lb ? la - lb : la + GF_MODULUS - lb;
+            if (ratio[d] != 0xFFFF) return set_error(err, RS16_INVALID_ARGUMENT);
+            ratio[d] = (uint16_t)i;
+            log_m0[i] = (uint16_t)la;
+        }
+        RS16_HIP(p->tab.reserve(tab.size() * 2));
+        RS16_HIP(hipMemcpy(p->tab.p, tab.data(), tab.size() * 2, hipMemcpyHostToDevice));
+        return RS16_OK;
+    };
+    if (build()) {
+        rs16_locate_plan_free(p);
+        return nullptr;
+    }
+    set_error(err, RS16_OK);
+    return p;
+}
+
+extern "C" void rs16_locate_plan_free(rs16_locate_plan* p) { free_attached(p, &rs16_engine::locate_plans); }
+
+extern "C" int rs16_locate_plan_rows(rs16_locate_plan* p, uint16_t* out, rs16_error* err) {
+    if (!p || !p->eng || !out) return set_error(err, RS16_INVALID_ARGUMENT);
+    memcpy(out, p->rows.data(), p->rows.size() * sizeof(uint16_t));
+    return set_error(err, RS16_OK);
+}
+
+// A work buffer of the locate that must keep its contents between calls: grown
+// if needed, *regrown set when that lost them.
+static hipError_t keep(DevBuf& b, size_t bytes, bool* regrown) {
+    if (bytes > b.cap) *regrown = true;
+    return b.reserve(bytes);
+}
+
+// One launch under profiling id `id` (rs16_engine_set_profiling).
+template <class F> static int timed(rs16_engine* e, int id, hipStream_t s, rs16_error* err, F launch) {
+    hipEvent_t pev;
+    if (int rc = e->prof_begin(s, &pev, err)) return rc;
+    RS16_HIP(launch());
+    return e->prof_end(id, s, pev, err);
+}
+
+extern "C" int rs16_locate_device(rs16_locate_plan* p, size_t S, const void* d_original, const void* d_recovery,
+                                  uint8_t* d_block_status, uint32_t* d_block_shard, void* d_block_fix, void* stream,
+                                  rs16_error* err) {
+    if (!p || !p->eng) return set_error(err, RS16_INVALID_ARGUMENT);
+    const size_t k = p->k, m = p->m;
+    const bool high = p->high;
+    if (int rc = rs16_validate(high ? RS16_RATE_HIGH : RS16_RATE_LOW, k, m, S, err)) return rc;
+    if (!d_original || !d_recovery || !d_block_status || !d_block_shard || !shard_aligned(d_original) ||
+        !shard_aligned(d_recovery))
+        return set_error(err, RS16_INVALID_ARGUMENT);
+    rs16_engine* e = p->eng;
+    hipStream_t s;
+    if (int rc = begin_ordered(e, stream, &s, err)) return rc;
+    RS16_HIP(e->ws_z.reserve(rs16_encoder_work_count(high, k, m) * S));
+    uint8_t* Z = (uint8_t*)e->ws_z.p;
+    uint8_t* U;
+    if (int rc = engine_u(e, high, k, S, &U, err)) return rc;
+    RS16_HIP(e->ws_rep.reserve(m * S));
+    RS16_HIP(e->ws_loc_rep.reserve(m * S));
+    RS16_HIP(e->ws_loc_cand.reserve(S / 64 * 4));
+    bool regrown = false;
+    RS16_HIP(keep(e->ws_loc_e, k * S, &regrown));
+    // copies of the scan's pairs, which its row walkers spread over: shards up
+    // to 64 KiB have few lanes per row and many walkers per column
+    const uint32_t nslots = S <= 65536 ? LOCATE_MAX_SLOTS : 1;
+    RS16_HIP(keep(e->ws_loc_acc, nslots * (S / 2) * 8, &regrown));
+    if (regrown || !e->loc_clean) {
+        e->loc_clean = false;
+        RS16_HIP(hipMemsetAsync(e->ws_loc_e.p, 0, e->ws_loc_e.cap, s));
+        RS16_HIP(hipMemsetAsync(e->ws_loc_acc.p, 0, e->ws_loc_acc.cap, s));
+    }
+    e->loc_clean = false;  // until the confirm kernel, which puts the last of it back, is enqueued
+    const uint16_t* tab = (const uint16_t*)p->tab.p;
+    LocateArgs a{};
+    a.enc = (const uint8_t*)e->ws_rep.p;
+    a.rec = (const uint8_t*)d_recovery;
+    a.enc2 = (const uint8_t*)e->ws_loc_rep.p;
+    a.E = (uint8_t*)e->ws_loc_e.p;
+    a.acc = (unsigned long long*)e->ws_loc_acc.p;
+    a.nslots = nslots;
+    a.cand = (uint32_t*)e->ws_loc_cand.p;
+    a.log = tab, a.exp = tab + GF_ORDER, a.ratio = tab + 2 * (size_t)GF_ORDER, a.log_m0 = tab + 3 * (size_t)GF_ORDER;
+    a.status = d_block_status, a.shard = d_block_shard, a.fix = (uint8_t*)d_block_fix;
+    a.S = S, a.k = (uint32_t)k, a.m = (uint32_t)m, a.blocks = (uint32_t)(S / 64);
+    // the syndromes' first half, then what they say ...
+    if (int rc = encode_dev(e, high, k, m, S, (const uint8_t*)d_original, (uint8_t*)e->ws_rep.p, Z, U, s, err)) return rc;
+    if (int rc = timed(e, PROF_LOCATE_SCAN, s, err, [&] { return launch_locate_scan(a, s); })) return rc;
+    if (int rc = timed(e, PROF_LOCATE_DECIDE, s, err, [&] { return launch_locate_decide(a, s); })) return rc;
+    // ... and the check of every ORIGINAL candidate against all m rows.  Always
+    // run: whether any block names an original is known on the device only.
+    if (int rc = encode_dev(e, high, k, m, S, a.E, (uint8_t*)e->ws_loc_rep.p, Z, U, s, err)) return rc;
+    if (int rc = timed(e, PROF_LOCATE_CONFIRM, s, err, [&] { return launch_locate_confirm(a, s); })) return rc;
+    e->loc_clean = true;
+    if (int rc = e->scratch_done(s, err)) return rc;
+    return set_error(err, RS16_OK);
+}

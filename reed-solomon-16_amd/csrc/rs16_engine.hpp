@@ -114,6 +114,7 @@ struct VerifySink {
 struct rs16_encoder;
 struct rs16_decoder;
 struct rs16_update_plan;
+struct rs16_locate_plan;
 
 struct rs16_engine {
     int device = 0;
@@ -133,6 +134,13 @@ struct rs16_engine {
     // the repair's recovery-only path: the re-encoded recovery shards of the
     // call's stripes (recovery_count x shard_bytes each), reserved on first use
     rs16::DevBuf ws_rep;
+    // rs16_locate_device: the candidate errors of the originals (k x S), their
+    // encode (m x S), the per-element (count, row sum) pairs of the scan and
+    // the per-block candidates.  ws_loc_e and the pairs are all zero between
+    // calls (loc_clean): the kernels put back what they wrote, and a call that
+    // finds the buffers regrown or a previous call cut short clears them whole.
+    rs16::DevBuf ws_loc_e, ws_loc_rep, ws_loc_acc, ws_loc_cand;
+    bool loc_clean = false;
     // the general decode's middle pass as v_perm tables of its matrix, per
     // transform size L (mid_tables; built on first use)
     rs16::DevBuf mid_tab[17];
@@ -239,6 +247,7 @@ struct rs16_engine {
     std::vector<rs16_encoder*> encoders;
     std::vector<rs16_decoder*> decoders;
     std::vector<rs16_update_plan*> update_plans;  // detached the same way (rs16_update_plan_free)
+    std::vector<rs16_locate_plan*> locate_plans;  // ... (rs16_locate_plan_free)
 
     // Pass launch (with optional hipEvent timing on the launch stream under
     // profiling id `prof` (rs16::ProfId; -1 = the program's own id).

@@ -166,6 +166,11 @@ enum ProfId : int {
     ENC_LAST_VFY,         // load -> FFT -> compare rows < out_rows with the stored ones, flag the differences
     ENC_SINGLE_VFY,       // gather -> IFFT -> FFT -> compare rows < out_rows, flag the differences
     PROF_VERIFY_CMP,      // rows of the re-encoded recovery against the caller's recovery array, flags only
+    // The locate's kernels (rs16_locate_device; rs16_locate.hip), beside the
+    // scrub's; none is a pass program.
+    PROF_LOCATE_SCAN,     // per element position: rows with a nonzero syndrome element, the sum of those rows
+    PROF_LOCATE_DECIDE,   // per block: status, shard, fix; an ORIGINAL candidate's error into the error array
+    PROF_LOCATE_CONFIRM,  // encode(error array) against the syndrome in every row of the ORIGINAL blocks
     // The repair's programs (rs16_repair_device; rs16_pass_repair.hip), behind
     // every other id.  The first two are pass programs with kernels
     // (launch_pass takes them), the third is the copy kernel of the
@@ -532,6 +537,49 @@ hipError_t launch_repair_copy(uint8_t* dst, const uint8_t* src, const uint8_t* f
 hipError_t launch_verify_cmp(const uint8_t* enc, const uint8_t* rec, const uint8_t* checked, uint8_t* row_flags,
                              uint8_t* col_flags, uint32_t rows, uint64_t S, uint64_t bs_enc, uint64_t bs_rec,
                              uint64_t bs_rows, uint64_t bs_cols, uint32_t nstripes, hipStream_t s);
+
+// Locating the one corrupt shard of each 64-byte column block
+// (rs16_locate_device; rs16_locate.hip).  The syndrome of row j is enc[j] ^
+// rec[j], never stored.  Element p of a row (p < S / 2) is element p & 31 of
+// block p >> 5: low byte at 64 (p >> 5) + (p & 31), high byte 32 further.
+constexpr uint32_t LOCATE_MAX_SLOTS = 16;  // copies of the scan's pairs (LocateArgs::nslots)
+struct LocateArgs {
+    const uint8_t* enc;     // the engine's encode of the stored originals (m x S)
+    const uint8_t* rec;     // the stored recovery shards (m x S)
+    const uint8_t* enc2;    // the engine's encode of E (m x S): the confirm kernel only
+    uint8_t* E;             // k x S, zero between calls: the candidate errors of the originals
+    // per element p: the number of rows with a nonzero syndrome element there
+    // (low 32 bits) and the sum of those rows (high 32 bits; the row itself
+    // when there is one), in nslots copies of S / 2 pairs each (a power of two:
+    // the scan's threads spread over them, the decide kernel adds them up);
+    // zero between calls -- the scan adds, the decide kernel reads and clears
+    unsigned long long* acc;
+    uint32_t nslots;
+    uint32_t* cand;         // per block: the candidate original of the decide kernel, ~0u: none
+    const uint16_t* log;    // GF_ORDER logs (HostTables::log)
+    const uint16_t* exp;    // GF_ORDER field elements by log
+    const uint16_t* log_m0; // k: log M[0][i]
+    const uint16_t* ratio;  // GF_MODULUS: (log M[0][i] - log M[1][i]) mod 65535 -> i, 0xFFFF: no original
+    uint8_t* status;        // per block (RS16_LOCATE_*)
+    uint32_t* shard;        // per block
+    uint8_t* fix;           // blocks x 64 bytes, nullptr: none
+    uint64_t S;
+    uint32_t k, m, blocks;
+};
+// The shape of the scan launch: cw column lanes (a lane = one low dword and the
+// matching high dword, 4 elements; S / 8 per row) by rsub rows per workgroup
+// pass, gx workgroups over the columns, gy over the rows, rows_per_wg rows each.
+// Host arithmetic only.
+struct LocateScanShape {
+    uint32_t cw, rsub, gx, gy, rows_per_wg;
+};
+LocateScanShape locate_scan_shape(uint64_t S, uint32_t m);
+hipError_t launch_locate_scan(const LocateArgs& a, hipStream_t s);
+hipError_t launch_locate_decide(const LocateArgs& a, hipStream_t s);
+hipError_t launch_locate_confirm(const LocateArgs& a, hipStream_t s);
+// The plan's unit stripe: byte `value` at element position q of row i0 + q for
+// q < n -- byte 64 (q >> 5) + (q & 31) of a row of Sc bytes.
+hipError_t launch_locate_unit(uint8_t* buf, uint64_t Sc, uint32_t i0, uint32_t n, uint32_t value, hipStream_t s);
 
 // Delta update of recovery shards (rs16_update.hip): rec[r] ^= sum over
 // e < n of delta[e] * (table of entry idx[(row0 + r) n + e]) for r < rows.

@@ -35,6 +35,8 @@ __all__ = [
     "repair_device", "repair_device_batch", "repair_path",
     "decode_device_select", "decode_device_select_batch", "select_path",
     "verify_device", "verify_device_batch", "verify", "verify_path",
+    "LocatePlan", "locate_device", "locate", "LOCATE_CLEAN", "LOCATE_ORIGINAL", "LOCATE_RECOVERY",
+    "LOCATE_UNLOCATABLE", "LOCATE_NO_SHARD",
     "UpdatePlan", "update_recovery_device", "UPDATE_MAX_SHARDS",
     "encode_host_multi", "decode_host_multi", "Comm", "column_slice", "scatter_columns", "gather_columns",
 ]
@@ -863,6 +865,96 @@ def verify(original_count: int, recovery_count: int, original, recovery, checked
     rows = d_rows.download()[:recovery_count]
     cols = d_cols.download()[:shard_bytes // 64]
     return np.flatnonzero(rows), np.flatnonzero(cols)
+
+
+LOCATE_CLEAN, LOCATE_ORIGINAL, LOCATE_RECOVERY, LOCATE_UNLOCATABLE = 0, 1, 2, 3  # RS16_LOCATE_*
+LOCATE_NO_SHARD = 0xFFFFFFFF
+
+
+class LocatePlan:
+    """rs16_locate_plan: rows 0 and 1 of the encode matrix of an original_count :
+    recovery_count stripe encoded at `rate` ("default" = the rate encode_device
+    picks), with which locate() names the one corrupt shard of each 64-byte
+    column block (include/rs16.h "Locate").  recovery_count >= 2."""
+
+    def __init__(self, original_count, recovery_count, rate="default", engine: Optional[Engine] = None):
+        self.engine = engine or default_engine()
+        self._err = RS16Error()
+        self.h = lib().rs16_locate_plan_new(self.engine.h, _RATES[rate], original_count, recovery_count,
+                                            C.byref(self._err))
+        if not self.h:
+            raise Error._from_c(self._err)
+        self.original_count, self.recovery_count = original_count, recovery_count
+
+    def rows(self) -> np.ndarray:
+        """(2, original_count) uint16: [j, i] = M[j][i] as a field element, j = 0, 1."""
+        out = np.empty((2, self.original_count), np.uint16)
+        _check(lib().rs16_locate_plan_rows(self.h, out.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(self._err)),
+               self._err)
+        return out
+
+    def locate(self, shard_bytes, d_original, d_recovery, d_block_status, d_block_shard, d_block_fix=None,
+               stream=None):
+        """rs16_locate_device: per 64-byte column block, d_block_status (uint8:
+        LOCATE_*), d_block_shard (uint32: the shard, LOCATE_NO_SHARD when none)
+        and, if given, d_block_fix (64 bytes: XOR into the named shard's block).
+        Pointers or DeviceArrays; both shard arrays are read only.
+        Asynchronous on `stream`."""
+        _check(lib().rs16_locate_device(self.h, shard_bytes, _dev_ptr(d_original), _dev_ptr(d_recovery),
+                                        _dev_ptr(d_block_status), _dev_ptr(d_block_shard), _dev_ptr(d_block_fix),
+                                        stream, C.byref(self._err)), self._err)
+
+    def close(self):
+        # Safe after the engine is gone: rs16_engine_free detaches its plans,
+        # and freeing a detached one only frees host memory.
+        if getattr(self, "h", None):
+            lib().rs16_locate_plan_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def locate_device(original_count, recovery_count, shard_bytes, d_original, d_recovery, d_block_status,
+                  d_block_shard, d_block_fix=None, rate="default", stream=None, engine: Optional[Engine] = None):
+    """One rs16_locate_device call through a plan built for it (and waited for:
+    the plan's tables must outlive the launches).  Callers that scrub many
+    stripes of one geometry keep a LocatePlan."""
+    plan = LocatePlan(original_count, recovery_count, rate, engine)
+    try:
+        plan.locate(shard_bytes, d_original, d_recovery, d_block_status, d_block_shard, d_block_fix, stream)
+        plan.engine.synchronize(stream)
+    finally:
+        plan.close()
+
+
+def locate(original_count: int, recovery_count: int, original, recovery, rate="default",
+           engine: Optional[Engine] = None):
+    """Locate the corrupt shard of each 64-byte column block of one stripe held on
+    the host: `original` and `recovery` are sequences of equal-length shards
+    (bytes or uint8 arrays).  Uploads, runs rs16_locate_device and returns
+    (status, shard, fix) as numpy arrays of one entry per column block: uint8
+    LOCATE_* values, uint32 shard indices (LOCATE_NO_SHARD when none) and a
+    (blocks, 64) uint8 array to XOR into the named shard's block."""
+    from .device import DeviceArray
+
+    eng = engine or default_engine()
+    o = np.ascontiguousarray([np.frombuffer(bytes(x), np.uint8) for x in original])
+    r = np.ascontiguousarray([np.frombuffer(bytes(x), np.uint8) for x in recovery])
+    if o.ndim != 2 or r.ndim != 2 or o.shape[0] != original_count or r.shape[0] != recovery_count or \
+            o.shape[1] != r.shape[1]:
+        raise Error("InvalidArgument")
+    shard_bytes = o.shape[1]
+    blocks = shard_bytes // 64
+    d_o, d_r = DeviceArray.from_numpy(eng, o), DeviceArray.from_numpy(eng, r)
+    d_status, d_shard, d_fix = DeviceArray(eng, blocks), DeviceArray(eng, blocks * 4), DeviceArray(eng, blocks * 64)
+    locate_device(original_count, recovery_count, shard_bytes, d_o, d_r, d_status, d_shard, d_fix, rate,
+                  engine=eng)
+    return (d_status.download()[:blocks], d_shard.download(np.uint32)[:blocks],
+            d_fix.download()[:blocks * 64].reshape(blocks, 64))
 
 
 def decode_prepare(original_count, recovery_count, shard_bytes, d_original_received, d_recovery_received,

@@ -122,6 +122,10 @@ SIGNATURES = {
     "rs16_verify_device": (_i, [_p, _sz, _sz, _sz, _p, _p, _p, _p, _p, _p, _e]),
     "rs16_verify_device_batch": (_i, [_p, _sz, _sz, _sz, _sz, _p, _sz, _p, _sz, _p, _p, _sz, _p, _sz, _p, _e]),
     "rs16_host_verify_path": (_i, [_sz, _sz, _sz, _sz, _i]),
+    "rs16_locate_plan_new": (_p, [_p, _i, _sz, _sz, _e]),
+    "rs16_locate_plan_free": (None, [_p]),
+    "rs16_locate_plan_rows": (_i, [_p, C.POINTER(C.c_uint16), _e]),
+    "rs16_locate_device": (_i, [_p, _sz, _p, _p, _p, _p, _p, _p, _e]),
     "rs16_decode_check": (_i, [_p, _p, _e]),
     "rs16_device_alloc": (_p, [_p, _sz, _e]),
     "rs16_device_free": (None, [_p, _p]),
