@@ -59,14 +59,36 @@ int encode_dev(rs16_engine* e, bool high, size_t k, size_t m, size_t S, const ui
                uint8_t* Z, uint8_t* U, hipStream_t s, rs16_error* err);
 // The engine's own low-rate scratch for an engine-ordered call (*U = nullptr for the high rate: none needed).
 int engine_u(rs16_engine* e, bool high, size_t k, size_t S, uint8_t** U, rs16_error* err);
+// Device encode of nstripes stripes on the engine's scratch, on the
+// engine-ordered stream s: stripe i's originals at d_orig + i bs_orig, its
+// recovery to d_rec + i bs_rec.  Which launches encode them and how much
+// scratch they take is decided here alone: the one-chunk high rate runs
+// batched -- each pass launch covers all stripes, a chunk of work rows per
+// stripe -- other shapes stripe by stripe in one stripe's work space.
+// vs: the scrub's fused path -- every stripe's last launch compares on the sink
+// (its cmp / rows / cols moved on by their stripe strides) and d_rec is not
+// used; only for the shapes of rs16_engine::verify_fusable.
+int encode_stripes(rs16_engine* e, bool high, size_t k, size_t m, size_t S, size_t nstripes, const uint8_t* d_orig,
+                   size_t bs_orig, uint8_t* d_rec, size_t bs_rec, hipStream_t s, rs16_error* err,
+                   const VerifySink* vs = nullptr);
+
+// What the layout of a batch of one geometry must satisfy: every stripe's
+// shards fit inside its stride, the strides are whole 64-byte blocks, as shard
+// sizes (every row stays aligned), and the stripes are few enough -- one
+// launch holds < 2^32 tiles; stay far below.
+constexpr size_t MAX_BATCH_STRIPES = (size_t)1 << 20;
+inline bool batch_layout_ok(size_t k, size_t m, size_t S, size_t nstripes, size_t o_stride, size_t r_stride) {
+    return o_stride >= k * S && r_stride >= m * S && o_stride % 64 == 0 && r_stride % 64 == 0 &&
+           nstripes <= MAX_BATCH_STRIPES;
+}
 
 // The decode's two sides.  The kernels know segments: A = work rows [0,
 // a_count), B = rows [chunk, chunk + b_count).  The callers know originals
 // and recovery.  The high rate uses recovery as A and originals as B, the low
 // rate the other way round -- decided here and nowhere else: every decode
 // entry point hands over its originals-side and recovery-side values once and
-// passes the members on.
-struct DecodeSides {
+// passes the members on (the kernels' view, DecodeSegs, is the base).
+struct DecodeSides : DecodeSegs {
     // One side as the caller has it: the shard array, its received flags, the
     // received count, and for batches the byte strides from stripe to stripe.
     struct Side {
@@ -81,10 +103,8 @@ struct DecodeSides {
     }
 
     DecodeGeom g;  // a_recv / b_recv set
-    const uint8_t *seg_a, *seg_b, *fl_a, *fl_b;
-    size_t bs_a, bs_b, fs_a, fs_b;
-    uint8_t* rest;  // where the restored originals go: the originals' array, stripe stride bs_rest
-    size_t bs_rest;
+    size_t fs_a, fs_b;
+    // (rest / bs_rest: the originals' array and its stripe stride)
     size_t orig_recv, rec_recv;
     size_t orig_base, rec_base;  // first work row of the originals / the recovery (rate_{high,low}.rs:279-299)
 
@@ -107,8 +127,21 @@ struct DecodeSides {
     }
     int passes(rs16_engine* e, size_t S, size_t S_user, size_t off, void* Z, void* U, void* rcount, hipStream_t s,
                rs16_error* err, size_t nstripes = 1) const {
-        return e->decode_passes(g, S, S_user, seg_a + off, fl_a, seg_b + off, fl_b, rest + off, (uint8_t*)Z,
-                                (uint8_t*)U, (uint32_t*)rcount, s, err, nstripes, bs_a, bs_b, bs_rest);
+        DecodeSegs v = *this;
+        v.S_user = S_user;
+        // (the repair restores the lost rows of both segments, each in its own array)
+        if (g.repair) v.rest = (uint8_t*)seg_a, v.bs_rest = bs_a, v.rest_b = (uint8_t*)seg_b, v.bs_rest_b = bs_b;
+        v.seg_a += off, v.seg_b += off, v.rest += off;
+        return e->decode_passes(g, S, v, (uint8_t*)Z, (uint8_t*)U, (uint32_t*)rcount, nstripes, s, err);
+    }
+    // A batched decode on the engine's scratch, on the engine-ordered stream s:
+    // n work rows of Z and of U per stripe, the eval kernels, then the passes
+    // (vary: eval's -- stripes with losses of their own).
+    int decode_batch(rs16_engine* e, size_t S, size_t nstripes, uint32_t vary, hipStream_t s, rs16_error* err) const {
+        RS16_HIP(e->ws_z.reserve(nstripes * g.n * S));
+        RS16_HIP(e->ws_u.reserve(nstripes * g.n * S));
+        if (int rc = eval(e, s, err, S, nstripes, vary)) return rc;
+        return passes(e, S, S, 0, e->ws_z.p, e->ws_u.p, e->evset->rcount.p, s, err, nstripes);
     }
 };
 

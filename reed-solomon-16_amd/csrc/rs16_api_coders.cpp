@@ -414,9 +414,12 @@ extern "C" int rs16_decoder_decode(rs16_decoder* d, rs16_error* err) {
     RS16_HIP(hipMemcpyAsync(fl + GF_ORDER, hf + GF_ORDER, g.b_count, hipMemcpyHostToDevice, e->stream));
     RS16_HIP(d->in_done.record(e->stream));
     uint8_t* w = (uint8_t*)d->work.p;
-    if (int rc = e->decode_fused(g, d->S, d->S, w, fl, w + (size_t)g.chunk * d->S, fl + GF_ORDER, w + d->orig_base * d->S,
-                                 w, (uint8_t*)d->ubuf.p, e->stream, err))
-        return rc;
+    DecodeSegs v;
+    v.seg_a = w, v.fl_a = fl;
+    v.seg_b = w + (size_t)g.chunk * d->S, v.fl_b = fl + GF_ORDER;
+    v.rest = w + d->orig_base * d->S;
+    v.S_user = d->S;
+    if (int rc = e->decode_fused(g, d->S, v, w, (uint8_t*)d->ubuf.p, e->stream, err)) return rc;
     e->forget_decode();
     if (int rc = e->scratch_done(e->stream, err)) return rc;
     if (d->host_round)

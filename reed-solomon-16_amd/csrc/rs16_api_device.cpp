@@ -21,6 +21,33 @@ int rs16::engine_u(rs16_engine* e, bool high, size_t k, size_t S, uint8_t** U, r
     *U = (uint8_t*)e->ws_u.p;
     return RS16_OK;
 }
+int rs16::encode_stripes(rs16_engine* e, bool high, size_t k, size_t m, size_t S, size_t nstripes,
+                         const uint8_t* d_orig, size_t bs_orig, uint8_t* d_rec, size_t bs_rec, hipStream_t s,
+                         rs16_error* err, const VerifySink* vs) {
+    const size_t chunk = next_pow2(m);
+    if (high && k <= chunk) {
+        RS16_HIP(e->ws_z.reserve(nstripes * chunk * S));
+        return e->encode_high_fused(k, m, S, S, d_orig, d_rec, (uint8_t*)e->ws_z.p, s, err, nstripes, bs_orig, bs_rec, vs);
+    }
+    RS16_HIP(e->ws_z.reserve(rs16_encoder_work_count(high, k, m) * S));
+    uint8_t *Z = (uint8_t*)e->ws_z.p, *U;
+    if (int rc = engine_u(e, high, k, S, &U, err)) return rc;
+    for (size_t i = 0; i < nstripes; i++) {
+        const uint8_t* oi = d_orig + i * bs_orig;
+        if (!vs) {
+            if (int rc = encode_dev(e, high, k, m, S, oi, d_rec + i * bs_rec, Z, U, s, err)) return rc;
+            continue;
+        }
+        VerifySink v = *vs;
+        v.cmp += i * v.bs_cmp;
+        v.rows += i * v.bs_rows;
+        if (v.cols) v.cols += i * v.bs_cols;
+        if (int rc = high ? e->encode_high_multi(k, m, S, S, oi, nullptr, Z, s, err, &v)
+                          : e->encode_low_multi(k, m, S, S, oi, nullptr, Z, U, s, err, &v))
+            return rc;
+    }
+    return RS16_OK;
+}
 
 extern "C" int rs16_encode_device(rs16_engine* e, size_t k, size_t m, size_t S, const void* d_original,
                                   void* d_recovery, void* stream, rs16_error* err) {
@@ -61,32 +88,14 @@ extern "C" int rs16_encode_device_batch(rs16_engine* e, size_t k, size_t m, size
     bool high;
     if (int rc = resolve_rate(RS16_RATE_DEFAULT, k, m, S, &high, err)) return rc;
     if (nstripes == 0) return set_error(err, RS16_OK);
-    // (strides in whole 64-byte blocks, as shard sizes: every row stays aligned)
-    if (!d_original || !d_recovery || original_stride < k * S || recovery_stride < m * S || original_stride % 64 ||
-        recovery_stride % 64 || !shard_aligned(d_original) || !shard_aligned(d_recovery))
+    if (!d_original || !d_recovery || !shard_aligned(d_original) || !shard_aligned(d_recovery) ||
+        !batch_layout_ok(k, m, S, nstripes, original_stride, recovery_stride))
         return set_error(err, RS16_INVALID_ARGUMENT);
-    const size_t chunk = next_pow2(m);
-    // one launch holds < 2^32 tiles; stay far below
-    if (nstripes > ((size_t)1 << 20)) return set_error(err, RS16_INVALID_ARGUMENT);
     hipStream_t s;
     if (int rc = begin_ordered(e, stream, &s, err)) return rc;
-    const size_t wc = rs16_encoder_work_count(high, k, m);
-    const uint8_t* o = (const uint8_t*)d_original;
-    uint8_t* r = (uint8_t*)d_recovery;
-    if (high && k <= chunk) {
-        RS16_HIP(e->ws_z.reserve(nstripes * chunk * S));
-        if (int rc = e->encode_high_fused(k, m, S, S, o, r, (uint8_t*)e->ws_z.p, s, err, nstripes, original_stride,
-                                          recovery_stride))
-            return rc;
-    } else {
-        RS16_HIP(e->ws_z.reserve(wc * S));
-        uint8_t* U;
-        if (int rc = engine_u(e, high, k, S, &U, err)) return rc;
-        for (size_t i = 0; i < nstripes; i++)
-            if (int rc = encode_dev(e, high, k, m, S, o + i * original_stride, r + i * recovery_stride,
-                                    (uint8_t*)e->ws_z.p, U, s, err))
-                return rc;
-    }
+    if (int rc = encode_stripes(e, high, k, m, S, nstripes, (const uint8_t*)d_original, original_stride,
+                                (uint8_t*)d_recovery, recovery_stride, s, err))
+        return rc;
     if (int rc = e->scratch_done(s, err)) return rc;
     return set_error(err, RS16_OK);
 }
@@ -240,15 +249,11 @@ extern "C" int rs16_decode_device_batch(rs16_engine* e, size_t k, size_t m, size
     const DecodeSides ds(high, k, m, {d_original, d_original_received, orig_recv, original_stride},
                          {d_recovery, d_recovery_received, rec_recv, recovery_stride});
     if (orig_recv == k) return note_flags_only(e, ds, stream, err);
-    if (!d_original || !d_recovery || original_stride < k * S || recovery_stride < m * S || original_stride % 64 ||
-        recovery_stride % 64 || nstripes > ((size_t)1 << 20))
+    if (!d_original || !d_recovery || !batch_layout_ok(k, m, S, nstripes, original_stride, recovery_stride))
         return set_error(err, RS16_INVALID_ARGUMENT);
     hipStream_t s;
     if (int rc = begin_ordered(e, stream, &s, err)) return rc;
-    RS16_HIP(e->ws_z.reserve(nstripes * ds.g.n * S));
-    RS16_HIP(e->ws_u.reserve(nstripes * ds.g.n * S));
-    if (int rc = ds.eval(e, s, err, S, nstripes)) return rc;
-    if (int rc = ds.passes(e, S, S, 0, e->ws_z.p, e->ws_u.p, e->evset->rcount.p, s, err, nstripes)) return rc;
+    if (int rc = ds.decode_batch(e, S, nstripes, 0, s, err)) return rc;
     if (int rc = e->scratch_done(s, err)) return rc;
     return set_error(err, RS16_OK);
 }
@@ -277,9 +282,9 @@ extern "C" int rs16_decode_device_batch_varied(rs16_engine* e, size_t k, size_t 
     e->forget_decode();
     if (nstripes == 0) return set_error(err, RS16_OK);
     if (!d_original || !d_recovery || !d_original_received || !d_recovery_received || !original_received_counts ||
-        !recovery_received_counts || original_stride < k * S || recovery_stride < m * S || original_stride % 64 ||
-        recovery_stride % 64 || !shard_aligned(d_original) || !shard_aligned(d_recovery) ||
-        original_received_stride < k || recovery_received_stride < m || nstripes > ((size_t)1 << 16))
+        !recovery_received_counts || !batch_layout_ok(k, m, S, nstripes, original_stride, recovery_stride) ||
+        !shard_aligned(d_original) || !shard_aligned(d_recovery) || original_received_stride < k ||
+        recovery_received_stride < m || nstripes > ((size_t)1 << 16))
         return set_error(err, RS16_INVALID_ARGUMENT);
     for (size_t i = 0; i < nstripes; i++) {
         const size_t o = original_received_counts[i], r = recovery_received_counts[i];
@@ -310,11 +315,7 @@ extern "C" int rs16_decode_device_batch_varied(rs16_engine* e, size_t k, size_t 
                              {(const uint8_t*)d_recovery + g0 * recovery_stride,
                               d_recovery_received + g0 * recovery_received_stride, max_r, recovery_stride,
                               recovery_received_stride});
-        RS16_HIP(e->ws_z.reserve(ns * ds.g.n * S));
-        RS16_HIP(e->ws_u.reserve(ns * ds.g.n * S));
-        const uint32_t vary = ns > 1 ? (uint32_t)ns : 0;
-        if (int rc = ds.eval(e, s, err, S, ns, vary)) return rc;
-        if (int rc = ds.passes(e, S, S, 0, e->ws_z.p, e->ws_u.p, e->evset->rcount.p, s, err, ns)) return rc;
+        if (int rc = ds.decode_batch(e, S, ns, ns > 1 ? (uint32_t)ns : 0, s, err)) return rc;
     }
     e->forget_decode();
     if (int rc = e->scratch_done(s, err)) return rc;

@@ -50,14 +50,11 @@ static int locate_rows(rs16_engine* e, bool high, size_t k, size_t m, std::vecto
         if (int rc = e->order(s, err)) return rc;
         // (on the stream the ones are set on: a non-blocking stream does not wait for the null stream)
         RS16_HIP(hipMemsetAsync(d_unit.p, 0, k * Smax, s));
-        RS16_HIP(e->ws_z.reserve(rs16_encoder_work_count(high, k, m) * Smax));
-        uint8_t* U;
-        if (int rc = engine_u(e, high, k, Smax, &U, err)) return rc;
+        // (the first chunk is the widest: the engine's scratch grows there or not at all)
         for (size_t i0 = 0; i0 < k; i0 += per) {
             const size_t n = std::min(per, k - i0), S = 64 * ((n + 31) / 32);
             RS16_HIP(launch_locate_unit((uint8_t*)d_unit.p, S, (uint32_t)i0, (uint32_t)n, 1, s));
-            if (int rc = encode_dev(e, high, k, m, S, (const uint8_t*)d_unit.p, (uint8_t*)d_rec.p, (uint8_t*)e->ws_z.p,
-                                    U, s, err))
+            if (int rc = encode_stripes(e, high, k, m, S, 1, (const uint8_t*)d_unit.p, 0, (uint8_t*)d_rec.p, 0, s, err))
                 return rc;
             RS16_HIP(launch_locate_unit((uint8_t*)d_unit.p, S, (uint32_t)i0, (uint32_t)n, 0, s));
             RS16_HIP(hipMemcpyAsync(rec.data(), d_rec.p, 2 * S, hipMemcpyDeviceToHost, s));
@@ -134,14 +131,6 @@ static hipError_t keep(DevBuf& b, size_t bytes, bool* regrown) {
     return b.reserve(bytes);
 }
 
-// One launch under profiling id `id` (rs16_engine_set_profiling).
-template <class F> static int timed(rs16_engine* e, int id, hipStream_t s, rs16_error* err, F launch) {
-    hipEvent_t pev;
-    if (int rc = e->prof_begin(s, &pev, err)) return rc;
-    RS16_HIP(launch());
-    return e->prof_end(id, s, pev, err);
-}
-
 extern "C" int rs16_locate_device(rs16_locate_plan* p, size_t S, const void* d_original, const void* d_recovery,
                                   uint8_t* d_block_status, uint32_t* d_block_shard, void* d_block_fix, void* stream,
                                   rs16_error* err) {
@@ -155,10 +144,6 @@ extern "C" int rs16_locate_device(rs16_locate_plan* p, size_t S, const void* d_o
     rs16_engine* e = p->eng;
     hipStream_t s;
     if (int rc = begin_ordered(e, stream, &s, err)) return rc;
-    RS16_HIP(e->ws_z.reserve(rs16_encoder_work_count(high, k, m) * S));
-    uint8_t* Z = (uint8_t*)e->ws_z.p;
-    uint8_t* U;
-    if (int rc = engine_u(e, high, k, S, &U, err)) return rc;
     RS16_HIP(e->ws_rep.reserve(m * S));
     RS16_HIP(e->ws_loc_rep.reserve(m * S));
     RS16_HIP(e->ws_loc_cand.reserve(S / 64 * 4));
@@ -187,13 +172,16 @@ extern "C" int rs16_locate_device(rs16_locate_plan* p, size_t S, const void* d_o
     a.status = d_block_status, a.shard = d_block_shard, a.fix = (uint8_t*)d_block_fix;
     a.S = S, a.k = (uint32_t)k, a.m = (uint32_t)m, a.blocks = (uint32_t)(S / 64);
     // the syndromes' first half, then what they say ...
-    if (int rc = encode_dev(e, high, k, m, S, (const uint8_t*)d_original, (uint8_t*)e->ws_rep.p, Z, U, s, err)) return rc;
-    if (int rc = timed(e, PROF_LOCATE_SCAN, s, err, [&] { return launch_locate_scan(a, s); })) return rc;
-    if (int rc = timed(e, PROF_LOCATE_DECIDE, s, err, [&] { return launch_locate_decide(a, s); })) return rc;
+    if (int rc = encode_stripes(e, high, k, m, S, 1, (const uint8_t*)d_original, 0, (uint8_t*)e->ws_rep.p, 0, s, err))
+        return rc;
+    if (int rc = e->profiled(PROF_LOCATE_SCAN, s, err, [&](uint64_t*) { return launch_locate_scan(a, s); })) return rc;
+    if (int rc = e->profiled(PROF_LOCATE_DECIDE, s, err, [&](uint64_t*) { return launch_locate_decide(a, s); }))
+        return rc;
     // ... and the check of every ORIGINAL candidate against all m rows.  Always
     // run: whether any block names an original is known on the device only.
-    if (int rc = encode_dev(e, high, k, m, S, a.E, (uint8_t*)e->ws_loc_rep.p, Z, U, s, err)) return rc;
-    if (int rc = timed(e, PROF_LOCATE_CONFIRM, s, err, [&] { return launch_locate_confirm(a, s); })) return rc;
+    if (int rc = encode_stripes(e, high, k, m, S, 1, a.E, 0, (uint8_t*)e->ws_loc_rep.p, 0, s, err)) return rc;
+    if (int rc = e->profiled(PROF_LOCATE_CONFIRM, s, err, [&](uint64_t*) { return launch_locate_confirm(a, s); }))
+        return rc;
     e->loc_clean = true;
     if (int rc = e->scratch_done(s, err)) return rc;
     return set_error(err, RS16_OK);

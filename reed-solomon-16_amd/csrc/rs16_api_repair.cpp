@@ -36,9 +36,7 @@ static int repair(rs16_engine* e, size_t k, size_t m, size_t S, bool batched, si
     e->forget_decode();  // (whatever happens below, the previous decode is not checked again)
     if (!d_original || !d_recovery || !fl_o || !fl_r || !shard_aligned(d_original) || !shard_aligned(d_recovery))
         return set_error(err, RS16_INVALID_ARGUMENT);
-    if (batched && (o_stride < k * S || r_stride < m * S || o_stride % 64 || r_stride % 64 ||
-                    nstripes > ((size_t)1 << 20)))
-        return set_error(err, RS16_INVALID_ARGUMENT);
+    if (batched && !batch_layout_ok(k, m, S, nstripes, o_stride, r_stride)) return set_error(err, RS16_INVALID_ARGUMENT);
     if (orig_recv > k || rec_recv > m) return set_error(err, RS16_INVALID_ARGUMENT);
     if (int rc = check_received(k, orig_recv, rec_recv, err)) return rc;
     if (nstripes == 0) return set_error(err, RS16_OK);
@@ -62,24 +60,13 @@ static int repair(rs16_engine* e, size_t k, size_t m, size_t S, bool batched, si
         const size_t rs = m * S;
         RS16_HIP(e->ws_rep.reserve(nstripes * rs));
         uint8_t* rep = (uint8_t*)e->ws_rep.p;
-        const uint8_t* o = (const uint8_t*)d_original;
-        const size_t wc = rs16_encoder_work_count(high, k, m);
-        if (high && k <= next_pow2(m)) {
-            RS16_HIP(e->ws_z.reserve(nstripes * next_pow2(m) * S));
-            if (int rc = e->encode_high_fused(k, m, S, S, o, rep, (uint8_t*)e->ws_z.p, s, err, nstripes, o_stride, rs))
-                return rc;
-        } else {
-            RS16_HIP(e->ws_z.reserve(wc * S));
-            uint8_t* U;
-            if (int rc = engine_u(e, high, k, S, &U, err)) return rc;
-            for (size_t i = 0; i < nstripes; i++)
-                if (int rc = encode_dev(e, high, k, m, S, o + i * o_stride, rep + i * rs, (uint8_t*)e->ws_z.p, U, s, err))
-                    return rc;
-        }
-        hipEvent_t pev;
-        if (int rc = e->prof_begin(s, &pev, err)) return rc;
-        RS16_HIP(launch_repair_copy((uint8_t*)d_recovery, rep, fl_r, (uint32_t)m, S, r_stride, rs, (uint32_t)nstripes, s));
-        if (int rc = e->prof_end(PROF_REPAIR_COPY, s, pev, err)) return rc;
+        if (int rc = encode_stripes(e, high, k, m, S, nstripes, (const uint8_t*)d_original, o_stride, rep, rs, s, err))
+            return rc;
+        if (int rc = e->profiled(PROF_REPAIR_COPY, s, err, [&](uint64_t*) {
+                return launch_repair_copy((uint8_t*)d_recovery, rep, fl_r, (uint32_t)m, S, r_stride, rs,
+                                          (uint32_t)nstripes, s);
+            }))
+            return rc;
         if (int rc = e->scratch_done(s, err)) return rc;
         return set_error(err, RS16_OK);
     }
@@ -87,13 +74,7 @@ static int repair(rs16_engine* e, size_t k, size_t m, size_t S, bool batched, si
     // stores of its last pass extended to both segments (DecodeGeom::repair).
     DecodeSides ds(high, k, m, {d_original, fl_o, orig_recv, o_stride}, {d_recovery, fl_r, rec_recv, r_stride});
     ds.g.repair = true;
-    RS16_HIP(e->ws_z.reserve(nstripes * ds.g.n * S));
-    RS16_HIP(e->ws_u.reserve(nstripes * ds.g.n * S));
-    if (int rc = ds.eval(e, s, err, S, nstripes)) return rc;
-    if (int rc = e->decode_passes(ds.g, S, S, ds.seg_a, ds.fl_a, ds.seg_b, ds.fl_b, (uint8_t*)ds.seg_a,
-                                  (uint8_t*)e->ws_z.p, (uint8_t*)e->ws_u.p, (uint32_t*)e->evset->rcount.p, s, err,
-                                  nstripes, ds.bs_a, ds.bs_b, ds.bs_a, (uint8_t*)ds.seg_b, ds.bs_b))
-        return rc;
+    if (int rc = ds.decode_batch(e, S, nstripes, 0, s, err)) return rc;
     if (int rc = e->scratch_done(s, err)) return rc;
     return set_error(err, RS16_OK);
 }

@@ -28,9 +28,7 @@ static int decode_select(rs16_engine* e, size_t k, size_t m, size_t S, bool batc
     if (!d_original || !d_recovery || !fl_o || !fl_r || !wanted || !shard_aligned(d_original) ||
         !shard_aligned(d_recovery))
         return set_error(err, RS16_INVALID_ARGUMENT);
-    if (batched && (o_stride < k * S || r_stride < m * S || o_stride % 64 || r_stride % 64 ||
-                    nstripes > ((size_t)1 << 20)))
-        return set_error(err, RS16_INVALID_ARGUMENT);
+    if (batched && !batch_layout_ok(k, m, S, nstripes, o_stride, r_stride)) return set_error(err, RS16_INVALID_ARGUMENT);
     if (orig_recv > k || rec_recv > m || wanted_count > k - orig_recv) return set_error(err, RS16_INVALID_ARGUMENT);
     if (int rc = check_received(k, orig_recv, rec_recv, err)) return rc;
     if (nstripes == 0) return set_error(err, RS16_OK);
@@ -52,10 +50,7 @@ static int decode_select(rs16_engine* e, size_t k, size_t m, size_t S, bool batc
     ds.g.select = true;
     ds.g.wanted = wanted;
     ds.g.wanted_count = wanted_count;
-    RS16_HIP(e->ws_z.reserve(nstripes * ds.g.n * S));
-    RS16_HIP(e->ws_u.reserve(nstripes * ds.g.n * S));
-    if (int rc = ds.eval(e, s, err, S, nstripes)) return rc;
-    if (int rc = ds.passes(e, S, S, 0, e->ws_z.p, e->ws_u.p, e->evset->rcount.p, s, err, nstripes)) return rc;
+    if (int rc = ds.decode_batch(e, S, nstripes, 0, s, err)) return rc;
     if (int rc = e->scratch_done(s, err)) return rc;
     return set_error(err, RS16_OK);
 }

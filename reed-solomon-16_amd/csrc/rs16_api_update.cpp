@@ -39,11 +39,7 @@ static int update_coefficients(rs16_engine* e, bool high, size_t k, size_t m, co
         RS16_HIP(hipMemcpy(d_unit.p, unit.data(), k * S, hipMemcpyHostToDevice));
         hipStream_t s = e->stream;
         if (int rc = e->order(s, err)) return rc;
-        RS16_HIP(e->ws_z.reserve(rs16_encoder_work_count(high, k, m) * S));
-        uint8_t* U;
-        if (int rc = engine_u(e, high, k, S, &U, err)) return rc;
-        if (int rc = encode_dev(e, high, k, m, S, (const uint8_t*)d_unit.p, (uint8_t*)d_rec.p, (uint8_t*)e->ws_z.p, U,
-                                s, err))
+        if (int rc = encode_stripes(e, high, k, m, S, 1, (const uint8_t*)d_unit.p, 0, (uint8_t*)d_rec.p, 0, s, err))
             return rc;
         if (int rc = e->scratch_done(s, err)) return rc;
         RS16_HIP(hipStreamSynchronize(s));

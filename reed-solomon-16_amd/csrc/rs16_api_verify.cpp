@@ -47,8 +47,8 @@ static int verify(rs16_engine* e, size_t k, size_t m, size_t S, bool batched, si
     if (!d_original || !d_recovery || !row_flags || !shard_aligned(d_original) || !shard_aligned(d_recovery))
         return set_error(err, RS16_INVALID_ARGUMENT);
     const size_t blocks = S / 64;
-    if (batched && (o_stride < k * S || r_stride < m * S || o_stride % 64 || r_stride % 64 || rf_stride < m ||
-                    (col_flags && cf_stride < blocks) || nstripes > ((size_t)1 << 20)))
+    if (batched && (!batch_layout_ok(k, m, S, nstripes, o_stride, r_stride) || rf_stride < m ||
+                    (col_flags && cf_stride < blocks)))
         return set_error(err, RS16_INVALID_ARGUMENT);
     if (nstripes == 0) return set_error(err, RS16_OK);
     hipStream_t s;
@@ -64,49 +64,24 @@ static int verify(rs16_engine* e, size_t k, size_t m, size_t S, bool batched, si
     }
     const uint8_t* o = (const uint8_t*)d_original;
     const uint8_t* r = (const uint8_t*)d_recovery;
-    const size_t chunk = next_pow2(m), wc = rs16_encoder_work_count(high, k, m);
-    const bool one_chunk = high && k <= chunk;
-    const bool fused = verify_path(e, high, k, m, S, nstripes) == 1;
     // (the encode's work space: the engine's buffers, never the caller's shards)
-    RS16_HIP(e->ws_z.reserve(one_chunk ? nstripes * chunk * S : wc * S));
-    uint8_t* Z = (uint8_t*)e->ws_z.p;
-    uint8_t* U = nullptr;
-    if (!one_chunk)
-        if (int rc = engine_u(e, high, k, S, &U, err)) return rc;
-    if (fused) {
+    if (verify_path(e, high, k, m, S, nstripes) == 1) {
         // The encode's sequence up to its last launch, which compares with the
         // stored rows instead of storing: no second recovery array.
-        VerifySink vs{r, S, r_stride, row_flags, col_flags, checked, rf_stride, cf_stride};
-        if (one_chunk) {
-            if (int rc = e->encode_high_fused(k, m, S, S, o, nullptr, Z, s, err, nstripes, o_stride, 0, &vs)) return rc;
-        } else {
-            for (size_t i = 0; i < nstripes; i++) {
-                vs.cmp = r + i * r_stride;
-                vs.rows = row_flags + i * rf_stride;
-                vs.cols = col_flags ? col_flags + i * cf_stride : nullptr;
-                const uint8_t* oi = o + i * o_stride;
-                if (int rc = high ? e->encode_high_multi(k, m, S, S, oi, nullptr, Z, s, err, &vs)
-                                  : e->encode_low_multi(k, m, S, S, oi, nullptr, Z, U, s, err, &vs))
-                    return rc;
-            }
-        }
+        const VerifySink vs{r, S, r_stride, row_flags, col_flags, checked, rf_stride, cf_stride};
+        if (int rc = encode_stripes(e, high, k, m, S, nstripes, o, o_stride, nullptr, 0, s, err, &vs)) return rc;
     } else {
         // The engine's encode of the stripe(s) into a buffer of its own, then
         // one compare kernel over it and the stored shards.
         const size_t rs = m * S;
         RS16_HIP(e->ws_rep.reserve(nstripes * rs));
         uint8_t* rep = (uint8_t*)e->ws_rep.p;
-        if (one_chunk) {
-            if (int rc = e->encode_high_fused(k, m, S, S, o, rep, Z, s, err, nstripes, o_stride, rs)) return rc;
-        } else {
-            for (size_t i = 0; i < nstripes; i++)
-                if (int rc = encode_dev(e, high, k, m, S, o + i * o_stride, rep + i * rs, Z, U, s, err)) return rc;
-        }
-        hipEvent_t pev;
-        if (int rc = e->prof_begin(s, &pev, err)) return rc;
-        RS16_HIP(launch_verify_cmp(rep, r, checked, row_flags, col_flags, (uint32_t)m, S, rs, r_stride, rf_stride,
-                                   cf_stride, (uint32_t)nstripes, s));
-        if (int rc = e->prof_end(PROF_VERIFY_CMP, s, pev, err)) return rc;
+        if (int rc = encode_stripes(e, high, k, m, S, nstripes, o, o_stride, rep, rs, s, err)) return rc;
+        if (int rc = e->profiled(PROF_VERIFY_CMP, s, err, [&](uint64_t*) {
+                return launch_verify_cmp(rep, r, checked, row_flags, col_flags, (uint32_t)m, S, rs, r_stride,
+                                         rf_stride, cf_stride, (uint32_t)nstripes, s);
+            }))
+            return rc;
     }
     if (int rc = e->scratch_done(s, err)) return rc;
     return set_error(err, RS16_OK);

@@ -214,13 +214,6 @@ int rs16_engine::prof_collect(rs16_error* err) {
     return RS16_OK;
 }
 
-template <class F> int rs16_engine::profiled(int prof, hipStream_t s, rs16_error* err, F launch) {
-    hipEvent_t ev;
-    if (int rc = prof_begin(s, &ev, err)) return rc;
-    RS16_HIP(launch(stamp_buf && prof == stamp_prof ? (uint64_t*)stamp_buf : nullptr));
-    return prof_end(prof, s, ev, err);
-}
-
 int rs16_engine::pass(int prog, int T, const PassArgs& a, uint32_t tiles, hipStream_t s, rs16_error* err, int prof) {
     return profiled(prof < 0 ? prog : prof, s, err, [&](uint64_t* stamps) {
         if (!stamps) return launch_pass(prog, T, a, tiles, s);
@@ -488,11 +481,10 @@ int rs16_engine::encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, 
 // where the formal derivative FD = I + L + H is split into its low-bit part L
 // and high-bit part H (L commutes with the high-bit layers and
 // FFT_high o IFFT_high = I), so no separate derivative pass is needed.
-int rs16_engine::decode_fused(const DecodeGeom& g, size_t S, size_t S_user, const uint8_t* seg_a, const uint8_t* flags_a,
-                              const uint8_t* seg_b, const uint8_t* flags_b, uint8_t* rest, uint8_t* Z, uint8_t* U,
+int rs16_engine::decode_fused(const DecodeGeom& g, size_t S, const DecodeSegs& v, uint8_t* Z, uint8_t* U,
                               hipStream_t s, rs16_error* err) {
-    if (int rc = decode_eval(g, flags_a, flags_b, s, err, S)) return rc;
-    return decode_passes(g, S, S_user, seg_a, flags_a, seg_b, flags_b, rest, Z, U, (uint32_t*)evset->rcount.p, s, err);
+    if (int rc = decode_eval(g, v.fl_a, v.fl_b, s, err, S)) return rc;
+    return decode_passes(g, S, v, Z, U, (uint32_t*)evset->rcount.p, 1, s, err);
 }
 
 int rs16_engine::guard_eval(hipStream_t s, bool consume, rs16_error* err) {
@@ -578,9 +570,6 @@ int rs16_engine::decode_eval(const DecodeGeom& g, const uint8_t* flags_a, const 
     eval_in_col = S && !g.repair && (half_decode(g) ? g.high && col_ok(ilog2(g.n) - 1, S, nstripes)
                                                     : col_ok(ilog2(g.n), S, nstripes, true));
     if (eval_in_col) return RS16_OK;
-    es.stamps = stamp_prof == PROF_EVAL_POLY ? (uint64_t*)stamp_buf : nullptr;
-    hipEvent_t pev;
-    if (int rc = prof_begin(s, &pev, err)) return rc;
     // The decode passes that read erasure logs finish eval_poly's last
     // 256-point FWHT themselves, for the 256-row block of their tile's rows
     // (one kernel less) -- except the one-pass half-transform decode, whose
@@ -588,15 +577,13 @@ int rs16_engine::decode_eval(const DecodeGeom& g, const uint8_t* flags_a, const 
     const bool small = g.high && g.n <= 2048 && !(diag & DIAG_EVAL_FULL);
     // (the column codec's half decodes of 2^9 / 2^10 rows finish it too)
     elog_fused = !(half_decode(g) && ilog2(g.n) - 1 <= 8);
-    if (small) {
+    uint32_t *work = (uint32_t*)evset->work32.p, *elog = (uint32_t*)evset->elog.p;
+    return profiled(PROF_EVAL_POLY, s, err, [&](uint64_t* stamps) {
+        es.stamps = stamps;
         // erasures are zero from row n on: only n/256 live blocks (rs16_misc.hip)
-        RS16_HIP(launch_eval_poly_small(es, (uint32_t)g.n, (uint32_t*)evset->work32.p, (uint32_t*)evset->elog.p, d_log_walsh,
-                                        s, !elog_fused));
-    } else {
-        RS16_HIP(launch_eval_poly_from_flags(es, (uint32_t*)evset->work32.p, (uint32_t*)evset->elog.p, d_log_walsh, s,
-                                             !elog_fused));
-    }
-    return prof_end(PROF_EVAL_POLY, s, pev, err);
+        if (small) return launch_eval_poly_small(es, (uint32_t)g.n, work, elog, d_log_walsh, s, !elog_fused);
+        return launch_eval_poly_from_flags(es, work, elog, d_log_walsh, s, !elog_fused);
+    });
 }
 
 // Half-transform decode.  When every original is lost and the originals'
@@ -658,22 +645,20 @@ int rs16_engine::mid_tables(int L, const uint32_t** out, rs16_error* err) {
 
 // The pass sequence of a decode, given what decode_eval left in evset->elog /
 // evset->work32 (erasure logs), evset->rbits (received rows) and evset->zflag (zero tiles).
-int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, const uint8_t* seg_a, const uint8_t* flags_a,
-                               const uint8_t* seg_b, const uint8_t* flags_b, uint8_t* rest, uint8_t* Z, uint8_t* U,
-                               uint32_t* rcount, hipStream_t s, rs16_error* err, size_t nst, size_t bs_a, size_t bs_b,
-                               size_t bs_rest, uint8_t* rest_b, size_t bs_rest_b) {
+int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, const DecodeSegs& v, uint8_t* Z, uint8_t* U,
+                               uint32_t* rcount, size_t nst, hipStream_t s, rs16_error* err) {
     PassArgs a = base_args(this, S);
-    a.S_seg = a.S_rest = S_user;
-    a.seg_a = seg_a;
-    a.seg_b = seg_b;
-    a.flags_a = flags_a;
-    a.flags_b = flags_b;
+    a.S_seg = a.S_rest = v.S_user;
+    a.seg_a = v.seg_a;
+    a.seg_b = v.seg_b;
+    a.flags_a = v.fl_a;
+    a.flags_b = v.fl_b;
     a.a_count = g.a_count;
     a.chunk = g.chunk;
     a.b_count = g.b_count;
     a.elog = (const uint32_t*)evset->elog.p;
     a.ework = elog_fused ? (const uint32_t*)evset->work32.p : nullptr;
-    a.rest = rest;
+    a.rest = v.rest;
     a.rest_seg_b = g.high ? 1 : 0;
     a.rbits = (const uint32_t*)evset->rbits.p;
     a.skew_ifft = a.skew_fft = 0;
@@ -692,11 +677,11 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
     // rows at Z / U + i n S
     const uint32_t ns = (uint32_t)nst;
     const size_t zs = (size_t)g.n * S;
-    a.bs_seg = bs_a;
-    a.bs_seg_b = bs_b;
-    a.bs_rest = bs_rest;
-    a.rest_b = rest_b;
-    a.bs_rest_b = bs_rest_b;
+    a.bs_seg = v.bs_a;
+    a.bs_seg_b = v.bs_b;
+    a.bs_rest = v.bs_rest;
+    a.rest_b = v.rest_b;
+    a.bs_rest_b = v.bs_rest_b;
     auto batch = [&](uint32_t tiles, size_t bs_in, size_t bs_in2, size_t bs_out) {
         a.stripe_tiles = ns > 1 ? tiles : 0;
         a.bs_in = bs_in;
@@ -717,15 +702,15 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
             // i.e. the encoder's three passes with the half's twiddles; the
             // first and last count the received flags for rs16_decode_check
             const int lo = row_split(Lh).lo, hi = row_split(Lh).hi;
-            a.seg_a = g.high ? seg_a : seg_b;
-            a.bs_seg = g.high ? bs_a : bs_b;
+            a.seg_a = g.high ? v.seg_a : v.seg_b;
+            a.bs_seg = g.high ? v.bs_a : v.bs_b;
             a.a_count = half;
             a.rcount = rcount;
-            a.cnt_flags = g.high ? flags_a : flags_b;
+            a.cnt_flags = g.high ? v.fl_a : v.fl_b;
             a.cnt_base = src;
             a.cnt_seg = g.high ? 0 : 1;
             // (the form of Z between these three passes, as in the encode)
-            const ZForm zf = z_form_sequence(half, S, S_user, a.a_count, a.chunk, a.row_base_in, diag);
+            const ZForm zf = z_form_sequence(half, S, v.S_user, a.a_count, a.chunk, a.row_base_in, diag);
             a.lo = 0;
             a.out = Z;
             z_form_args(a, zf);
@@ -735,14 +720,14 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
             a.in = Z;
             RS16_PASS_AS(PROF_DEC_HALF_MID, ENC_MID, hi, a, batch(1u << lo, zs, 0, zs), s);
             a.lo = 0;
-            a.out = rest;
-            a.S_out = S_user;
+            a.out = v.rest;
+            a.S_out = v.S_user;
             a.out_rows = orig;
             a.rcount = rcount;
-            a.cnt_flags = g.high ? flags_b : flags_a;
+            a.cnt_flags = g.high ? v.fl_b : v.fl_a;
             a.cnt_base = dst;
             a.cnt_seg = g.high ? 1 : 0;
-            RS16_PASS_AS(DEC_HALF_LAST, ENC_LAST, lo, a, batch((orig + (1u << lo) - 1) >> lo, zs, 0, bs_rest), s);
+            RS16_PASS_AS(DEC_HALF_LAST, ENC_LAST, lo, a, batch((orig + (1u << lo) - 1) >> lo, zs, 0, v.bs_rest), s);
             return RS16_OK;
         }
         // 2^6 .. 2^10-row halves: the whole decode in one launch (rs16_col.hip)
@@ -756,15 +741,15 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
         }
         if (col_eval || col_ok(Lh, S, ns)) {
             ColArgs c = col_args();
-            c.in = g.high ? seg_a : seg_b;
-            c.flags = g.high ? flags_a : flags_b;
+            c.in = g.high ? v.seg_a : v.seg_b;
+            c.flags = g.high ? v.fl_a : v.fl_b;
             c.in_rows = g.high ? g.a_count : g.b_count;
-            c.out = rest;
-            c.S_in = c.S_out = S_user;
+            c.out = v.rest;
+            c.S_in = c.S_out = v.S_user;
             c.qrow = (uint32_t)(S / 8);
             c.nstripes = ns;
-            c.bs_in = g.high ? bs_a : bs_b;
-            c.bs_out = bs_rest;
+            c.bs_in = g.high ? v.bs_a : v.bs_b;
+            c.bs_out = v.bs_rest;
             c.out_rows = orig;
             c.base_in = c.skew_ifft = src;
             c.base_out = c.skew_fft = dst;
@@ -775,7 +760,7 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
             c.bs_elog = var_ns ? VARY_WORK : 0;
             if (col_eval) {
                 // eval_poly in the kernel (decode_eval launched nothing)
-                c.flags_o = flags_b;
+                c.flags_o = v.fl_b;
                 c.o_rows = g.b_count;
                 c.vtab = nullptr;  // (col(): d_col_v + col_v_offset(2^(L+1)))
                 c.rcount = rcount;
@@ -803,24 +788,24 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, size_t S_user, con
         // segment A / B = recovery / originals (high rate) or originals /
         // recovery (low rate, rate_low.rs:168-247)
         ColArgs c = col_args();
-        c.in = seg_a;
-        c.flags = flags_a;
+        c.in = v.seg_a;
+        c.flags = v.fl_a;
         c.in_rows = g.a_count;
-        c.in_b = seg_b;
-        c.bs_in_b = bs_b;
-        c.flags_o = flags_b;
+        c.in_b = v.seg_b;
+        c.bs_in_b = v.bs_b;
+        c.flags_o = v.fl_b;
         c.o_rows = g.b_count;
         c.chunk = g.chunk;
         c.rev_a = g.high ? 0 : 1;
         c.e_pad = g.high ? 1 : 0;
         c.e_tail = g.high ? 0 : 1;
         c.e_k = g.high ? 0 : host_tables().col_k[L];
-        c.out = rest;
-        c.S_in = c.S_out = S_user;
+        c.out = v.rest;
+        c.S_in = c.S_out = v.S_user;
         c.qrow = (uint32_t)(S / 8);
         c.nstripes = ns;
-        c.bs_in = bs_a;
-        c.bs_out = bs_rest;
+        c.bs_in = v.bs_a;
+        c.bs_out = v.bs_rest;
         c.out_rows = g.high ? g.b_count : g.a_count;
         c.rcount = rcount;
         c.bs_flags = var_bs_fa;

@@ -109,6 +109,22 @@ struct VerifySink {
     size_t bs_rows, bs_cols;
 };
 
+// The decode's view of its two segments (decode_passes, decode_fused): the
+// gather sources with their device flags and where the lost rows go.
+// S_user: the row stride of seg_a / seg_b / rest / rest_b; bs_*: the byte
+// strides from stripe to stripe of a batched launch.
+struct DecodeSegs {
+    const uint8_t *seg_a = nullptr, *seg_b = nullptr, *fl_a = nullptr, *fl_b = nullptr;
+    size_t bs_a = 0, bs_b = 0;
+    uint8_t* rest = nullptr;  // where the restored originals go, stripe stride bs_rest
+    size_t bs_rest = 0;
+    // g.repair: rest / bs_rest are segment A's array and stripe stride, rest_b
+    // / bs_rest_b segment B's; the lost rows of both are restored
+    uint8_t* rest_b = nullptr;
+    size_t bs_rest_b = 0;
+    size_t S_user = 0;
+};
+
 }  // namespace rs16
 
 struct rs16_encoder;
@@ -257,8 +273,13 @@ struct rs16_engine {
     int prof_end(int id, hipStream_t s, hipEvent_t ev, rs16_error* err);
     // One kernel launch under profiling id `prof`: launch(stamps) returns the
     // launch's hipError_t; stamps = stamp_buf when `prof` is the stamped id,
-    // else nullptr (rs16_engine.cpp).
-    template <class F> int profiled(int prof, hipStream_t s, rs16_error* err, F launch);
+    // else nullptr.  The only caller of prof_begin / prof_end.
+    template <class F> int profiled(int prof, hipStream_t s, rs16_error* err, F launch) {
+        hipEvent_t ev;
+        if (int rc = prof_begin(s, &ev, err)) return rc;
+        const hipError_t he = launch(stamp_buf && prof == stamp_prof ? (uint64_t*)stamp_buf : nullptr);
+        return he == hipSuccess ? prof_end(prof, s, ev, err) : rs16::hip_fail(err, he);
+    }
     bool profiling = false;
     // diagnostic timelines (rs16_engine_set_stamps): passes under profiling
     // id stamp_prof get stamp_buf (RS16_STAMPS builds record into it)
@@ -295,12 +316,11 @@ struct rs16_engine {
     // not used, and the work rows keep the shards' form; only for the shapes
     // of verify_fusable (others: RS16_INVALID_ARGUMENT, nothing launched).
     bool verify_fusable(bool high, size_t k, size_t m, size_t S, size_t nstripes) const;
-    // Fused decode (both rates): seg_a / seg_b gather sources with device
-    // flags; lost originals written to rest; Z, U work (n rows each; Z may
-    // alias the sources when they live at their work positions).
-    // S = row width, S_user = row stride of seg_a / seg_b / rest (Z, U: stride S)
-    int decode_fused(const rs16::DecodeGeom& g, size_t S, size_t S_user, const uint8_t* seg_a, const uint8_t* flags_a,
-                     const uint8_t* seg_b, const uint8_t* flags_b, uint8_t* rest, uint8_t* Z, uint8_t* U,
+    // Fused decode (both rates) of one stripe: v's seg_a / seg_b gather
+    // sources with device flags; lost originals written to v.rest; Z, U work
+    // (n rows each; Z may alias the sources when they live at their work
+    // positions).  S = row width (Z, U: stride S)
+    int decode_fused(const rs16::DecodeGeom& g, size_t S, const rs16::DecodeSegs& v, uint8_t* Z, uint8_t* U,
                      hipStream_t s, rs16_error* err);
     // decode_fused = decode_eval (erasure logs into ws_elog) + decode_passes.
     // S / nstripes: the width of the decode_passes launches that follow (0:
@@ -327,12 +347,8 @@ struct rs16_engine {
     // rcount: where a column decode that evaluates the polynomial itself
     // writes the received counts (ErasureSpec::rcount layout): ws_rcount on
     // the call's own stream, a buffer of their own for concurrent slots.
-    int decode_passes(const rs16::DecodeGeom& g, size_t S, size_t S_user, const uint8_t* seg_a, const uint8_t* flags_a,
-                      const uint8_t* seg_b, const uint8_t* flags_b, uint8_t* rest, uint8_t* Z, uint8_t* U,
-                      uint32_t* rcount, hipStream_t s, rs16_error* err, size_t nstripes = 1, size_t bs_a = 0,
-                      size_t bs_b = 0, size_t bs_rest = 0, uint8_t* rest_b = nullptr, size_t bs_rest_b = 0);
-    // (g.repair: rest / bs_rest are segment A's array and stripe stride, rest_b
-    // / bs_rest_b segment B's; the lost rows of both are restored)
+    int decode_passes(const rs16::DecodeGeom& g, size_t S, const rs16::DecodeSegs& v, uint8_t* Z, uint8_t* U,
+                      uint32_t* rcount, size_t nstripes, hipStream_t s, rs16_error* err);
     // The half-transform decode applies (every original lost, originals
     // segment = one half of the work rows).
     static bool half_decode(const rs16::DecodeGeom& g);

@@ -836,6 +836,20 @@ def verify_path(original_count, recovery_count, shard_bytes, nstripes=1, diag=0)
     return lib().rs16_host_verify_path(original_count, recovery_count, shard_bytes, nstripes, diag)
 
 
+def _upload_stripe(eng, original_count, recovery_count, original, recovery):
+    """The host shard sequences of verify() / locate() as two uploaded
+    DeviceArrays, their counts and equal lengths checked: (shard_bytes, d_original,
+    d_recovery)."""
+    from .device import DeviceArray
+
+    o = np.ascontiguousarray([np.frombuffer(bytes(x), np.uint8) for x in original])
+    r = np.ascontiguousarray([np.frombuffer(bytes(x), np.uint8) for x in recovery])
+    if o.ndim != 2 or r.ndim != 2 or o.shape[0] != original_count or r.shape[0] != recovery_count or \
+            o.shape[1] != r.shape[1]:
+        raise Error("InvalidArgument")
+    return o.shape[1], DeviceArray.from_numpy(eng, o), DeviceArray.from_numpy(eng, r)
+
+
 def verify(original_count: int, recovery_count: int, original, recovery, checked=None,
            engine: Optional[Engine] = None):
     """Scrub one stripe held on the host: `original` and `recovery` are sequences
@@ -847,13 +861,7 @@ def verify(original_count: int, recovery_count: int, original, recovery, checked
     from .device import DeviceArray
 
     eng = engine or default_engine()
-    o = np.ascontiguousarray([np.frombuffer(bytes(x), np.uint8) for x in original])
-    r = np.ascontiguousarray([np.frombuffer(bytes(x), np.uint8) for x in recovery])
-    if o.ndim != 2 or r.ndim != 2 or o.shape[0] != original_count or r.shape[0] != recovery_count or \
-            o.shape[1] != r.shape[1]:
-        raise Error("InvalidArgument")
-    shard_bytes = o.shape[1]
-    d_o, d_r = DeviceArray.from_numpy(eng, o), DeviceArray.from_numpy(eng, r)
+    shard_bytes, d_o, d_r = _upload_stripe(eng, original_count, recovery_count, original, recovery)
     d_rows, d_cols = DeviceArray(eng, recovery_count), DeviceArray(eng, max(shard_bytes // 64, 1))
     d_chk = None
     if checked is not None:
@@ -942,14 +950,8 @@ def locate(original_count: int, recovery_count: int, original, recovery, rate="d
     from .device import DeviceArray
 
     eng = engine or default_engine()
-    o = np.ascontiguousarray([np.frombuffer(bytes(x), np.uint8) for x in original])
-    r = np.ascontiguousarray([np.frombuffer(bytes(x), np.uint8) for x in recovery])
-    if o.ndim != 2 or r.ndim != 2 or o.shape[0] != original_count or r.shape[0] != recovery_count or \
-            o.shape[1] != r.shape[1]:
-        raise Error("InvalidArgument")
-    shard_bytes = o.shape[1]
+    shard_bytes, d_o, d_r = _upload_stripe(eng, original_count, recovery_count, original, recovery)
     blocks = shard_bytes // 64
-    d_o, d_r = DeviceArray.from_numpy(eng, o), DeviceArray.from_numpy(eng, r)
     d_status, d_shard, d_fix = DeviceArray(eng, blocks), DeviceArray(eng, blocks * 4), DeviceArray(eng, blocks * 64)
     locate_device(original_count, recovery_count, shard_bytes, d_o, d_r, d_status, d_shard, d_fix, rate,
                   engine=eng)

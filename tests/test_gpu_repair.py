@@ -171,7 +171,7 @@ def test_flag_bytes(eng, k, m, name):
 
 @pytest.mark.parametrize("k,m,recv,nstripes", [(200, 200, (1, 1), 1), (200, 200, (0x80, 0xFF), 1),
                                                (1000, 100, (2, 0x40), 1), (5, 3000, (0xFF, 0x80), 1),
-                                               (200, 200, (0x80, 0xFF), 3)])
+                                               (200, 200, (0x80, 0xFF), 3), (5, 3000, (0xFF, 0x80), 2)])
 def test_recovery_only_writes_no_received_slot(eng, k, m, recv, nstripes):
     """Path 2 reads no recovery shard, so the received recovery slots can hold
     anything: here junk that the encode would not produce.  A copy that ignored

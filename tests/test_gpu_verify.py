@@ -271,7 +271,8 @@ def test_large_shapes(eng, k, m, sb, fused_prog):
                     assert expect_program(k, m, sb, diag) == fused_prog
 
 
-@pytest.mark.parametrize("k,m,sb,ns,extra", [(100, 100, 192, 5, NOCOL), (600, 300, 64, 3, NOCOL)])
+@pytest.mark.parametrize("k,m,sb,ns,extra", [(100, 100, 192, 5, NOCOL), (600, 300, 64, 3, NOCOL),
+                                             (40, 200, 64, 2, NOCOL)])  # (the low rate, stripe by stripe)
 def test_batch(eng, k, m, sb, ns, extra):
     names = ["rec_first", "none", "both", "rec_halves", "orig_last_block"][:ns]
     blocks = sb // 64
