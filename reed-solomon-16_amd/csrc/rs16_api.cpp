@@ -537,8 +537,8 @@ extern "C" int rs16_engine_fwht(rs16_engine* e, uint16_t* d, size_t trunc, void*
     if (int rc = e->activate(err)) return rc;
     if (int rc = e->order(e->pick(stream), err)) return rc;
     if (int rc = e->guard_eval(e->pick(stream), false, err)) return rc;
-    RS16_HIP(e->evset->work32.reserve(GF_ORDER * 4));
-    RS16_HIP(launch_fwht_u16(d, (uint32_t*)e->evset->work32.p, e->pick(stream)));
+    RS16_HIP(e->ev_main.work32.reserve(GF_ORDER * 4));
+    RS16_HIP(launch_fwht_u16(d, (uint32_t*)e->ev_main.work32.p, e->pick(stream)));
     if (int rc = e->scratch_done(e->pick(stream), err)) return rc;
     return set_error(err, RS16_OK);
 }
@@ -547,8 +547,8 @@ extern "C" int rs16_engine_eval_poly(rs16_engine* e, uint16_t* d, size_t trunc, 
     if (int rc = e->activate(err)) return rc;
     if (int rc = e->order(e->pick(stream), err)) return rc;
     if (int rc = e->guard_eval(e->pick(stream), false, err)) return rc;
-    RS16_HIP(e->evset->work32.reserve(GF_ORDER * 4));
-    RS16_HIP(launch_eval_poly_u16(d, (uint32_t*)e->evset->work32.p, e->d_log_walsh, e->pick(stream)));
+    RS16_HIP(e->ev_main.work32.reserve(GF_ORDER * 4));
+    RS16_HIP(launch_eval_poly_u16(d, (uint32_t*)e->ev_main.work32.p, e->d_log_walsh, e->pick(stream)));
     if (int rc = e->scratch_done(e->pick(stream), err)) return rc;
     return set_error(err, RS16_OK);
 }

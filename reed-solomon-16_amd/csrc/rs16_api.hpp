@@ -55,19 +55,21 @@ template <class T> void free_attached(T* x, std::vector<T*> rs16_engine::*list) 
 // originals) -- both owned by stream s for the call: the engine's ws_z /
 // ws_u on the engine-ordered paths (order() / scratch_done()), a slot's own
 // buffers on concurrent slots.
+// Which encoder runs is the engine's one decision (rs16_engine::encode_form).
+// vs: the scrub's fused path (rs16_engine::encode_high_fused).
 int encode_dev(rs16_engine* e, bool high, size_t k, size_t m, size_t S, const uint8_t* d_orig, uint8_t* d_rec,
-               uint8_t* Z, uint8_t* U, hipStream_t s, rs16_error* err);
+               uint8_t* Z, uint8_t* U, hipStream_t s, rs16_error* err, const VerifySink* vs = nullptr);
 // The engine's own low-rate scratch for an engine-ordered call (*U = nullptr for the high rate: none needed).
 int engine_u(rs16_engine* e, bool high, size_t k, size_t S, uint8_t** U, rs16_error* err);
 // Device encode of nstripes stripes on the engine's scratch, on the
 // engine-ordered stream s: stripe i's originals at d_orig + i bs_orig, its
 // recovery to d_rec + i bs_rec.  Which launches encode them and how much
-// scratch they take is decided here alone: the one-chunk high rate runs
+// scratch they take follows the encode form: the one-chunk high rate runs
 // batched -- each pass launch covers all stripes, a chunk of work rows per
 // stripe -- other shapes stripe by stripe in one stripe's work space.
 // vs: the scrub's fused path -- every stripe's last launch compares on the sink
 // (its cmp / rows / cols moved on by their stripe strides) and d_rec is not
-// used; only for the shapes of rs16_engine::verify_fusable.
+// used; only for the forms of EncodeForm::verify_fusable.
 int encode_stripes(rs16_engine* e, bool high, size_t k, size_t m, size_t S, size_t nstripes, const uint8_t* d_orig,
                    size_t bs_orig, uint8_t* d_rec, size_t bs_rec, hipStream_t s, rs16_error* err,
                    const VerifySink* vs = nullptr);
@@ -119,20 +121,23 @@ struct DecodeSides : DecodeSegs {
         orig_recv = orig.recv, rec_recv = rec.recv;
         std::tie(orig_base, rec_base) = by_segment<size_t>(high, 0, g.chunk);
     }
-    // rs16_engine::decode_eval / decode_passes with the members in their places.
+    // rs16_engine::decode_eval / decode_passes with the members in their places:
+    // eval writes to ev and fills *plan, which the passes of that evaluation get.
     // off: the byte column the shard arrays are entered at (a column slice).
-    int eval(rs16_engine* e, hipStream_t s, rs16_error* err, size_t S = 0, size_t nstripes = 1,
-             uint32_t vary = 0) const {
-        return e->decode_eval(g, fl_a, fl_b, s, err, S, nstripes, vary, fs_a, fs_b);
+    using EvalBufs = rs16_engine::EvalBufs;
+    using DecodePlan = rs16_engine::DecodePlan;
+    int eval(rs16_engine* e, EvalBufs& ev, DecodePlan* plan, hipStream_t s, rs16_error* err, size_t S = 0,
+             size_t nstripes = 1, uint32_t vary = 0, bool prepare = false) const {
+        return e->decode_eval(g, fl_a, fl_b, ev, plan, s, err, S, nstripes, vary, fs_a, fs_b, prepare);
     }
-    int passes(rs16_engine* e, size_t S, size_t S_user, size_t off, void* Z, void* U, void* rcount, hipStream_t s,
-               rs16_error* err, size_t nstripes = 1) const {
+    int passes(rs16_engine* e, const DecodePlan& plan, size_t S, size_t S_user, size_t off, void* Z, void* U,
+               void* rcount, hipStream_t s, rs16_error* err, size_t nstripes = 1) const {
         DecodeSegs v = *this;
         v.S_user = S_user;
         // (the repair restores the lost rows of both segments, each in its own array)
         if (g.repair) v.rest = (uint8_t*)seg_a, v.bs_rest = bs_a, v.rest_b = (uint8_t*)seg_b, v.bs_rest_b = bs_b;
         v.seg_a += off, v.seg_b += off, v.rest += off;
-        return e->decode_passes(g, S, v, (uint8_t*)Z, (uint8_t*)U, (uint32_t*)rcount, nstripes, s, err);
+        return e->decode_passes(g, S, v, (uint8_t*)Z, (uint8_t*)U, plan, (uint32_t*)rcount, nstripes, s, err);
     }
     // A batched decode on the engine's scratch, on the engine-ordered stream s:
     // n work rows of Z and of U per stripe, the eval kernels, then the passes
@@ -140,8 +145,9 @@ struct DecodeSides : DecodeSegs {
     int decode_batch(rs16_engine* e, size_t S, size_t nstripes, uint32_t vary, hipStream_t s, rs16_error* err) const {
         RS16_HIP(e->ws_z.reserve(nstripes * g.n * S));
         RS16_HIP(e->ws_u.reserve(nstripes * g.n * S));
-        if (int rc = eval(e, s, err, S, nstripes, vary)) return rc;
-        return passes(e, S, S, 0, e->ws_z.p, e->ws_u.p, e->evset->rcount.p, s, err, nstripes);
+        DecodePlan plan;
+        if (int rc = eval(e, e->ev_main, &plan, s, err, S, nstripes, vary)) return rc;
+        return passes(e, plan, S, S, 0, e->ws_z.p, e->ws_u.p, e->ev_main.rcount.p, s, err, nstripes);
     }
 };
 

@@ -9,10 +9,11 @@ using namespace rs16;
 // Device-resident one-shot codec.
 // ---------------------------------------------------------------------------
 int rs16::encode_dev(rs16_engine* e, bool high, size_t k, size_t m, size_t S, const uint8_t* d_orig, uint8_t* d_rec,
-                     uint8_t* Z, uint8_t* U, hipStream_t s, rs16_error* err) {
-    if (high && k <= next_pow2(m)) return e->encode_high_fused(k, m, S, S, d_orig, d_rec, Z, s, err);
-    return high ? e->encode_high_multi(k, m, S, S, d_orig, d_rec, Z, s, err)
-                : e->encode_low_multi(k, m, S, S, d_orig, d_rec, Z, U, s, err);
+                     uint8_t* Z, uint8_t* U, hipStream_t s, rs16_error* err, const VerifySink* vs) {
+    const EncodeForm f = e->encode_form(high, k, m, S, 1);
+    if (f.one_chunk) return e->encode_high_fused(f, k, m, S, S, d_orig, d_rec, Z, s, err, 1, 0, 0, vs);
+    return high ? e->encode_high_multi(f, k, m, S, S, d_orig, d_rec, Z, s, err, vs)
+                : e->encode_low_multi(f, k, m, S, S, d_orig, d_rec, Z, U, s, err, vs);
 }
 int rs16::engine_u(rs16_engine* e, bool high, size_t k, size_t S, uint8_t** U, rs16_error* err) {
     *U = nullptr;
@@ -24,10 +25,11 @@ int rs16::engine_u(rs16_engine* e, bool high, size_t k, size_t S, uint8_t** U, r
 int rs16::encode_stripes(rs16_engine* e, bool high, size_t k, size_t m, size_t S, size_t nstripes,
                          const uint8_t* d_orig, size_t bs_orig, uint8_t* d_rec, size_t bs_rec, hipStream_t s,
                          rs16_error* err, const VerifySink* vs) {
-    const size_t chunk = next_pow2(m);
-    if (high && k <= chunk) {
-        RS16_HIP(e->ws_z.reserve(nstripes * chunk * S));
-        return e->encode_high_fused(k, m, S, S, d_orig, d_rec, (uint8_t*)e->ws_z.p, s, err, nstripes, bs_orig, bs_rec, vs);
+    const EncodeForm f = e->encode_form(high, k, m, S, nstripes);
+    if (f.one_chunk) {
+        RS16_HIP(e->ws_z.reserve(nstripes * f.chunk * S));
+        return e->encode_high_fused(f, k, m, S, S, d_orig, d_rec, (uint8_t*)e->ws_z.p, s, err, nstripes, bs_orig,
+                                    bs_rec, vs);
     }
     RS16_HIP(e->ws_z.reserve(rs16_encoder_work_count(high, k, m) * S));
     uint8_t *Z = (uint8_t*)e->ws_z.p, *U;
@@ -42,9 +44,7 @@ int rs16::encode_stripes(rs16_engine* e, bool high, size_t k, size_t m, size_t S
         v.cmp += i * v.bs_cmp;
         v.rows += i * v.bs_rows;
         if (v.cols) v.cols += i * v.bs_cols;
-        if (int rc = high ? e->encode_high_multi(k, m, S, S, oi, nullptr, Z, s, err, &v)
-                          : e->encode_low_multi(k, m, S, S, oi, nullptr, Z, U, s, err, &v))
-            return rc;
+        if (int rc = encode_dev(e, high, k, m, S, oi, nullptr, Z, U, s, err, &v)) return rc;
     }
     return RS16_OK;
 }
@@ -58,7 +58,7 @@ extern "C" int rs16_encode_device(rs16_engine* e, size_t k, size_t m, size_t S, 
     if (int rc = begin_ordered(e, stream, &s, err)) return rc;
     const size_t wc = rs16_encoder_work_count(high, k, m);
     RS16_HIP(e->ws_z.reserve(wc * S));
-    const int n = (high && k <= next_pow2(m)) ? e->slice_count(S) : 1;
+    const int n = e->encode_form(high, k, m, S, 1).one_chunk ? e->slice_count(S) : 1;
     if (n == 1) {
         uint8_t* U;
         if (int rc = engine_u(e, high, k, S, &U, err)) return rc;
@@ -67,7 +67,8 @@ extern "C" int rs16_encode_device(rs16_engine* e, size_t k, size_t m, size_t S, 
             return rc;
     } else if (int rc = for_column_slices(e, S, n, s, err, [&](int j, size_t off, size_t w) {
                    // on the engine's slice streams (work space: wc x width each)
-                   return e->encode_high_fused(k, m, w, S, (const uint8_t*)d_original + off,
+                   return e->encode_high_fused(e->encode_form(high, k, m, w, 1), k, m, w, S,
+                                               (const uint8_t*)d_original + off,
                                                (uint8_t*)d_recovery + off, (uint8_t*)e->ws_z.p + wc * off,
                                                e->sl_stream[j], err);
                })) {
@@ -123,22 +124,23 @@ static int note_flags_only(rs16_engine* e, const DecodeSides& ds, void* stream, 
 }
 
 // The passes of a device decode whose eval_poly is in ev_main (decode_eval
-// on stream s or a preparation ordered before s), per column slice.
-static int decode_device_passes(rs16_engine* e, const DecodeSides& ds, size_t S, int n, hipStream_t s,
-                                rs16_error* err) {
+// on stream s or a preparation ordered before s, either one's plan), per
+// column slice.
+static int decode_device_passes(rs16_engine* e, const DecodeSides& ds, const rs16_engine::DecodePlan& plan, size_t S,
+                                int n, hipStream_t s, rs16_error* err) {
     const size_t rows = ds.g.n;
     RS16_HIP(e->ws_z.reserve(rows * S));
     RS16_HIP(e->ws_u.reserve(rows * S));
     uint8_t* Z = (uint8_t*)e->ws_z.p;
     uint8_t* U = (uint8_t*)e->ws_u.p;
     if (n == 1) {
-        if (int rc = ds.passes(e, S, S, 0, Z, U, e->ev_main.rcount.p, s, err)) return rc;
+        if (int rc = ds.passes(e, plan, S, S, 0, Z, U, e->ev_main.rcount.p, s, err)) return rc;
     } else if (int rc = for_column_slices(e, S, n, s, err, [&](int j, size_t off, size_t w) {
                    // (decode_eval was told the slices are narrower than S: no column
                    // decode evaluates the polynomial itself; with identity multipliers
                    // the first slice's passes count the received rows)
-                   void* rc_j = j == 0 && e->e_ident ? e->ev_main.rcount.p : nullptr;
-                   return ds.passes(e, w, S, off, Z + rows * off, U + rows * off, rc_j, e->sl_stream[j], err);
+                   void* rc_j = j == 0 && plan.ident ? e->ev_main.rcount.p : nullptr;
+                   return ds.passes(e, plan, w, S, off, Z + rows * off, U + rows * off, rc_j, e->sl_stream[j], err);
                })) {
         return rc;
     }
@@ -164,8 +166,9 @@ extern "C" int rs16_decode_device(rs16_engine* e, size_t k, size_t m, size_t S, 
     // erasure logs once, then the passes per column slice on the slice streams
     // (one slice: the column codec may compute them itself, decode_eval)
     const int n = e->slice_count(S);
-    if (int rc = ds.eval(e, s, err, n == 1 ? S : 0)) return rc;
-    return decode_device_passes(e, ds, S, n, s, err);
+    rs16_engine::DecodePlan plan;
+    if (int rc = ds.eval(e, e->ev_main, &plan, s, err, n == 1 ? S : 0)) return rc;
+    return decode_device_passes(e, ds, plan, S, n, s, err);
 }
 
 // Split decode (include/rs16.h): the flag-dependent half of
@@ -198,10 +201,7 @@ extern "C" int rs16_decode_prepare(rs16_engine* e, size_t k, size_t m, size_t S,
         hipStream_t s;
         if (int rc = begin_ordered(e, stream, &s, err)) return rc;
         if (int rc = e->guard_eval(s, false, err)) return rc;  // (an earlier, unconsumed preparation)
-        e->preparing = true;
-        const int rc = ds.eval(e, s, err, p.nslices == 1 ? S : 0);
-        e->preparing = false;
-        if (rc) return rc;
+        if (int rc = ds.eval(e, e->ev_main, &p.plan, s, err, p.nslices == 1 ? S : 0, 1, 0, true)) return rc;
         if (!e->prep_ev) RS16_HIP(hipEventCreateWithFlags(&e->prep_ev, hipEventDisableTiming));
         RS16_HIP(hipEventRecord(e->prep_ev, s));
         e->prep_pending = true;
@@ -226,7 +226,7 @@ extern "C" int rs16_decode_device_prepared(rs16_engine* e, size_t k, size_t m, s
     hipStream_t s;
     if (int rc = begin_ordered(e, stream, &s, err)) return rc;
     if (int rc = e->guard_eval(s, true, err)) return rc;  // after the preparation's eval_poly
-    return decode_device_passes(e, ds, S, p.nslices, s, err);
+    return decode_device_passes(e, ds, p.plan, S, p.nslices, s, err);
 }
 
 // rs16_decode_device for nstripes independent stripes that lost the same

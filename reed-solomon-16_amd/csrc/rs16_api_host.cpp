@@ -62,15 +62,15 @@ static int encode_host_slice(rs16_engine* e, HostSlot& sl, hipStream_t s, bool h
     RS16_HIP(hipMemcpy2DAsync((uint8_t*)h_recovery + off, S, sl.rec.p, w, w, m, hipMemcpyDeviceToHost, s));
     return RS16_OK;
 }
-// ds: the decode with sl's rows as its shard arrays (host_decode_sides).
-static int decode_host_slice(rs16_engine* e, HostSlot& sl, hipStream_t s, const DecodeSides& ds, size_t k, size_t m,
-                             size_t S, size_t off, size_t w, void* h_original, const void* h_recovery,
-                             rs16_error* err) {
+// ds: the decode with sl's rows as its shard arrays (host_decode_sides); plan: its evaluation's.
+static int decode_host_slice(rs16_engine* e, HostSlot& sl, hipStream_t s, const DecodeSides& ds,
+                             const rs16_engine::DecodePlan& plan, size_t k, size_t m, size_t S, size_t off, size_t w,
+                             void* h_original, const void* h_recovery, rs16_error* err) {
     if (ds.rec_recv)
         RS16_HIP(hipMemcpy2DAsync(sl.rec.p, w, (const uint8_t*)h_recovery + off, S, w, m, hipMemcpyHostToDevice, s));
     if (ds.orig_recv)
         RS16_HIP(hipMemcpy2DAsync(sl.orig.p, w, (const uint8_t*)h_original + off, S, w, k, hipMemcpyHostToDevice, s));
-    if (int rc = ds.passes(e, w, w, 0, sl.z.p, sl.u.p, sl.rcount.p, s, err)) return rc;
+    if (int rc = ds.passes(e, plan, w, w, 0, sl.z.p, sl.u.p, sl.rcount.p, s, err)) return rc;
     // restored originals land in place; received rows come back unchanged
     RS16_HIP(hipMemcpy2DAsync((uint8_t*)h_original + off, S, sl.orig.p, w, w, k, hipMemcpyDeviceToHost, s));
     return RS16_OK;
@@ -137,11 +137,12 @@ extern "C" int rs16_decode_host(rs16_engine* e, size_t k, size_t m, size_t S, vo
     const uint8_t* d_flags = (const uint8_t*)e->hflags.p;
     const DecodeSides ds[2] = {host_decode_sides(high, k, m, e->hslot[0], d_flags, orig_recv, rec_recv),
                                host_decode_sides(high, k, m, e->hslot[1], d_flags, orig_recv, rec_recv)};
-    if (int rc = ds[0].eval(e, e->stream, err, W)) return rc;
+    rs16_engine::DecodePlan plan;
+    if (int rc = ds[0].eval(e, e->ev_main, &plan, e->stream, err, W)) return rc;
     if (int rc = e->host_slots(err)) return rc;
     for (size_t off = 0, j = 0; off < S; off += W, j++) {
         auto& sl = e->hslot[j & 1];
-        if (int rc = decode_host_slice(e, sl, sl.s, ds[j & 1], k, m, S, off, std::min(W, S - off), h_original,
+        if (int rc = decode_host_slice(e, sl, sl.s, ds[j & 1], plan, k, m, S, off, std::min(W, S - off), h_original,
                                        h_recovery, err))
             return rc;
     }
@@ -190,12 +191,6 @@ int copy_runs(const uint8_t* flags, size_t n, bool want, size_t max_runs, F copy
     return RS16_OK;
 }
 constexpr size_t HP_MAX_RUNS = 64;
-// the engine's decode scratch set, restored on every exit path
-struct EvalSet {
-    rs16_engine* e;
-    explicit EvalSet(rs16_engine* eng, int lane) : e(eng) { e->evset = &e->ev_lane[lane]; }
-    ~EvalSet() { e->evset = &e->ev_main; }
-};
 }  // namespace
 
 int rs16_engine::host_pipe_events(rs16_error* err) {
@@ -302,12 +297,10 @@ extern "C" int rs16_decode_host_batch(rs16_engine* e, size_t k, size_t m, size_t
             first_lane = b;
         }
         // ---- codec, with the lane's own eval_poly outputs
-        {
-            EvalSet lane(e, b);
-            const DecodeSides ds = host_decode_sides(high, k, m, sl, d_of, ocnt[i], rcnt[i]);
-            if (int rc = ds.eval(e, sl.s, err, S)) return rc;
-            if (int rc = ds.passes(e, S, S, 0, sl.z.p, sl.u.p, sl.rcount.p, sl.s, err)) return rc;
-        }
+        const DecodeSides ds = host_decode_sides(high, k, m, sl, d_of, ocnt[i], rcnt[i]);
+        rs16_engine::DecodePlan plan;
+        if (int rc = ds.eval(e, e->ev_lane[b], &plan, sl.s, err, S)) return rc;
+        if (int rc = ds.passes(e, plan, S, S, 0, sl.z.p, sl.u.p, sl.rcount.p, sl.s, err)) return rc;
         // ---- out: the restored originals (in place in the lane's rows)
         if (int rc = copy_runs(fo, k, false, HP_MAX_RUNS, rows(ho, d_o, hipMemcpyDeviceToHost))) return rc;
     }
@@ -384,8 +377,10 @@ extern "C" int rs16_decode_host_multi(rs16_engine* const* engines, int n, size_t
         // (every engine its own flags and erasure logs, on its own stream, ahead of its slice)
         if (int rc = upload_host_flags(e, k, m, original_received, recovery_received, err)) return rc;
         const DecodeSides ds = host_decode_sides(high, k, m, sl, (const uint8_t*)e->hflags.p, orig_recv, rec_recv);
-        if (int rc = ds.eval(e, e->stream, err, w)) return rc;
-        if (int rc = decode_host_slice(e, sl, e->stream, ds, k, m, S, off, w, h_original, h_recovery, err)) return rc;
+        rs16_engine::DecodePlan plan;
+        if (int rc = ds.eval(e, e->ev_main, &plan, e->stream, err, w)) return rc;
+        if (int rc = decode_host_slice(e, sl, e->stream, ds, plan, k, m, S, off, w, h_original, h_recovery, err))
+            return rc;
     }
     if (int rc = multi_sync(engines, n, err)) return rc;
     for (int j = 0; j < n; j++) engines[j]->forget_decode();  // (host flags: nothing to check)

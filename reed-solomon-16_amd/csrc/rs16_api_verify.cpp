@@ -8,7 +8,7 @@
 using namespace rs16;
 
 // The default path of a scrub whose encode ends in a pass with a comparing
-// form (rs16_engine::verify_fusable): the fused path only where it measured
+// form (EncodeForm::verify_fusable): the fused path only where it measured
 // faster than encode + compare in every alternating pair of every run, clean and
 // corrupted (include/rs16.h, "When to prefer it"; profiles/r18_verify.txt).
 // That is the batch form of the one-chunk high rate at 1024-row chunks (513 ..
@@ -20,19 +20,17 @@ using namespace rs16;
 // in one of three runs), not at 8192 rows and above nor in the multi-chunk
 // rates, where the two paths lie within 2 % of each other and the fused one lost
 // pairs.  Sizes in between are not measured.
-static bool fused_by_default(bool high, size_t k, size_t m, size_t S, size_t nstripes) {
-    (void)S;
-    const size_t chunk = next_pow2(m);
-    return high && k <= chunk && chunk == 1024 && nstripes >= 4;
+static bool fused_by_default(const EncodeForm& f, size_t nstripes) {
+    return f.one_chunk && f.chunk == 1024 && nstripes >= 4;
 }
 
 // 0: encode + compare, 1: the fused path (include/rs16.h); -1: unsupported shape.
 // Host arithmetic only: the entry points below call it, and so can a test.
 static int verify_path(const rs16_engine* e, bool high, size_t k, size_t m, size_t S, size_t nstripes) {
-    // (batched launches exist for the one-chunk high rate only: other shapes run stripe by stripe)
-    const size_t nst = high && k <= next_pow2(m) ? nstripes : 1;
-    if ((e->diag & DIAG_NO_FUSED_VERIFY) || !e->verify_fusable(high, k, m, S, nst)) return 0;
-    return (e->diag & DIAG_FORCE_FUSED_VERIFY) || fused_by_default(high, k, m, S, nstripes) ? 1 : 0;
+    // (encode_form counts the stripes of one launch: nstripes for the one-chunk high rate, else one)
+    const EncodeForm f = e->encode_form(high, k, m, S, nstripes);
+    if ((e->diag & DIAG_NO_FUSED_VERIFY) || !f.verify_fusable()) return 0;
+    return (e->diag & DIAG_FORCE_FUSED_VERIFY) || fused_by_default(f, nstripes) ? 1 : 0;
 }
 
 // Both forms: nstripes stripes with one check set, stripe i's arrays at + i

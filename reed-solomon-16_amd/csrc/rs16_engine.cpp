@@ -241,16 +241,43 @@ bool rs16_engine::col_chunks_ok(int L, uint32_t nch, size_t S, bool high) const 
            nch < col_img_count((uint32_t)L) && col_ok(L, S, 1);
 }
 
-ColArgs rs16_engine::col_args() const {
+ColArgs rs16_engine::col_args(const uint8_t* in, size_t S_in, uint8_t* out, size_t S_out, size_t S, size_t in_rows,
+                              size_t out_rows, size_t skew_ifft, size_t skew_fft) const {
     ColArgs a;
     std::memset(&a, 0, sizeof a);
     a.skew_tab = d_skew_tab;
     a.mul_tab = d_mul_tab;
     a.zero = d_zero_sink;
-    a.elog = (const uint32_t*)evset->elog.p;
     a.nstripes = 1;
     a.diag = (uint32_t)diag;
+    a.in = in;
+    a.S_in = S_in;
+    a.out = out;
+    a.S_out = S_out;
+    a.qrow = (uint32_t)(S / 8);
+    a.in_rows = (uint32_t)in_rows;
+    a.out_rows = (uint32_t)out_rows;
+    a.skew_ifft = (uint32_t)skew_ifft;
+    a.skew_fft = (uint32_t)skew_fft;
     return a;
+}
+
+// The one decision of how a shape is encoded: the branches of the three
+// encoders below, in the order they are tested here.
+EncodeForm rs16_engine::encode_form(bool high, size_t k, size_t m, size_t S, size_t nstripes) const {
+    EncodeForm f;
+    f.chunk = next_pow2(high ? m : k);
+    f.one_chunk = high && k <= f.chunk;
+    f.nch = (uint32_t)(((high ? k : m) + f.chunk - 1) / f.chunk);
+    const int L = f.L = ilog2(f.chunk);
+    f.lo = L <= 8 ? L : L / 2;  // (row_split above 2^8 rows; up to there one pass over all L bits)
+    f.hi = L - f.lo;
+    if (f.one_chunk) f.kind = col_ok(L, S, nstripes) ? f.COL : (L <= 8 ? f.ONE_PASS : f.THREE_PASS);
+    else if (L == 0) f.kind = f.ROWS;
+    else if (!high && f.nch == 1) f.kind = col_ok(L, S, 1) ? f.COL : f.PASSES;
+    else if (L == (int)COLM_L && f.nch <= COLM_MAX_CHUNKS && col_ok(L, S, 1)) f.kind = f.COLM;
+    else f.kind = col_chunks_ok(L, f.nch, S, high) ? f.COL_CHUNKS : f.PASSES;
+    return f;
 }
 
 // The column codec's tables (HostTables::col_img / col_v), uploaded on the
@@ -302,13 +329,7 @@ int rs16_engine::col(const ColArgs& args, int L, int mode, hipStream_t s, rs16_e
 // rs16_col.hip): nch chunks of originals (high) or of recovery (low).
 int rs16_engine::col_multi(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec,
                            uint32_t nch, bool high, hipStream_t s, rs16_error* err) {
-    ColArgs c = col_args();
-    c.in = d_orig;
-    c.out = d_rec;
-    c.S_in = c.S_out = S_user;
-    c.qrow = (uint32_t)(S / 8);
-    c.in_rows = (uint32_t)k;
-    c.out_rows = (uint32_t)m;
+    ColArgs c = col_args(d_orig, S_user, d_rec, S_user, S, k, m, 0, 0);
     c.nch = nch;
     // (colm_kernel records no timeline: the stamps pointer is not passed on)
     return profiled(PROF_COL_ENC, s, err, [&](uint64_t*) { return launch_col_multi(c, high, s); });
@@ -378,34 +399,25 @@ static void sink_args(PassArgs& a, const VerifySink& v) {
     a.bs_vfy_checked = 0;  // (one check set for all stripes)
 }
 
-// Whether the engine's encode of the shape ends in a pass-codec store pass that
-// has a comparing form (ENC_SINGLE_VFY at T >= 1, ENC_LAST_VFY at T >= 4): the
-// branches of encode_high_fused, encode_high_multi and encode_low_multi, in
-// their order.  nst: the stripes of one batched launch (encode_high_fused).
-bool rs16_engine::verify_fusable(bool high, size_t k, size_t m, size_t S, size_t nst) const {
-    if (high && k <= next_pow2(m)) {
-        const int L = ilog2(next_pow2(m));
-        return L >= 1 && !col_ok(L, S, nst);  // (L <= 8: one pass; above: lo = L / 2 >= 4)
-    }
-    const size_t chunk = next_pow2(high ? m : k);
-    const uint32_t nch = (uint32_t)(((high ? k : m) + chunk - 1) / chunk);
-    const int L = ilog2(chunk), lo = L <= 8 ? L : L / 2;
-    if (lo < 4) return false;  // (fft_to_recovery's last pass at T = lo; L = 0: the copy branches)
-    if (L == (int)COLM_L && nch <= COLM_MAX_CHUNKS && (high || nch > 1) && col_ok(L, S, 1)) return false;
-    if (!high && nch == 1 && col_ok(L, S, 1)) return false;
-    if ((high || nch > 1) && col_chunks_ok(L, nch, S, high)) return false;
-    return true;
-}
-
 // HighRateEncoder::encode for original_count <= chunk (src/rate/rate_high.rs:44-83):
 //   recovery = FFT(IFFT(originals zero-padded to chunk, skew = chunk), skew = 0)[0..m)
 // as three passes over the 2-D row factorisation (contiguous low bits /
 // strided high bits); IFFT-high and FFT-high share the strided pass.
-int rs16_engine::encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec, uint8_t* Z,
-                                   hipStream_t s, rs16_error* err, size_t nst, size_t bs_orig, size_t bs_rec,
-                                   const VerifySink* vs) {
-    const size_t chunk = next_pow2(m);
-    const int L = ilog2(chunk);
+int rs16_engine::encode_high_fused(const EncodeForm& f, size_t k, size_t m, size_t S, size_t S_user,
+                                   const uint8_t* d_orig, uint8_t* d_rec, uint8_t* Z, hipStream_t s, rs16_error* err,
+                                   size_t nst, size_t bs_orig, size_t bs_rec, const VerifySink* vs) {
+    const size_t chunk = f.chunk;
+    const int L = f.L, lo = f.lo, hi = f.hi;
+    // (a verify sink: the forms whose last launch compares -- never the column codec's)
+    if (vs && !f.verify_fusable()) return set_error(err, RS16_INVALID_ARGUMENT);
+    if (f.kind == f.COL) {
+        // 512 / 1024-row chunks: the whole encode in one launch (rs16_col.hip)
+        ColArgs c = col_args(d_orig, S_user, d_rec, S_user, S, k, m, chunk, 0);
+        c.nstripes = (uint32_t)nst;
+        c.bs_in = bs_orig;
+        c.bs_out = bs_rec;
+        return col(c, L, COL_ENC, s, err);
+    }
     PassArgs a = base_args(this, S);
     a.seg_a = d_orig;
     a.S_seg = S_user;
@@ -424,32 +436,13 @@ int rs16_engine::encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, 
         a.bs_seg = bs_seg;
         return tiles * ns;
     };
-    // (a verify sink: the shapes of verify_fusable only, whose last launch compares)
-    if (vs && !verify_fusable(true, k, m, S, nst)) return set_error(err, RS16_INVALID_ARGUMENT);
-    if (!vs && col_ok(L, S, nst)) {
-        // 512 / 1024-row chunks: the whole encode in one launch (rs16_col.hip)
-        ColArgs c = col_args();
-        c.in = d_orig;
-        c.out = d_rec;
-        c.S_in = c.S_out = S_user;
-        c.qrow = (uint32_t)(S / 8);
-        c.nstripes = ns;
-        c.bs_in = bs_orig;
-        c.bs_out = bs_rec;
-        c.in_rows = (uint32_t)k;
-        c.out_rows = (uint32_t)m;
-        c.skew_ifft = (uint32_t)chunk;
-        c.skew_fft = 0;
-        return col(c, L, COL_ENC, s, err);
-    }
-    if (L <= 8) {
+    if (f.kind == f.ONE_PASS) {
         a.out = d_rec;
         a.S_out = S_user;
         if (vs) sink_args(a, *vs);
         RS16_PASS(vs ? ENC_SINGLE_VFY : ENC_SINGLE, L, a, batch(1, 0, bs_rec, bs_orig), s);
         return RS16_OK;
     }
-    const int lo = row_split(L).lo, hi = row_split(L).hi;
     const size_t zs = chunk * S;
     // the form of Z between the three passes, one decision for all of them
     // (a verify sink: the work rows in the shards' own form -- the comparing
@@ -483,8 +476,9 @@ int rs16_engine::encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, 
 // FFT_high o IFFT_high = I), so no separate derivative pass is needed.
 int rs16_engine::decode_fused(const DecodeGeom& g, size_t S, const DecodeSegs& v, uint8_t* Z, uint8_t* U,
                               hipStream_t s, rs16_error* err) {
-    if (int rc = decode_eval(g, v.fl_a, v.fl_b, s, err, S)) return rc;
-    return decode_passes(g, S, v, Z, U, (uint32_t*)evset->rcount.p, 1, s, err);
+    DecodePlan plan;
+    if (int rc = decode_eval(g, v.fl_a, v.fl_b, ev_main, &plan, s, err, S)) return rc;
+    return decode_passes(g, S, v, Z, U, plan, (uint32_t*)ev_main.rcount.p, 1, s, err);
 }
 
 int rs16_engine::guard_eval(hipStream_t s, bool consume, rs16_error* err) {
@@ -495,27 +489,31 @@ int rs16_engine::guard_eval(hipStream_t s, bool consume, rs16_error* err) {
     return RS16_OK;
 }
 
-// Erasure logs e = eval_poly(erasure vector) into evset->elog (2-3 small kernels).
-int rs16_engine::decode_eval(const DecodeGeom& g, const uint8_t* flags_a, const uint8_t* flags_b, hipStream_t s,
-                             rs16_error* err, size_t S, size_t nstripes, uint32_t vary, size_t bs_fa, size_t bs_fb) {
+// Erasure logs e = eval_poly(erasure vector) into ev.elog (2-3 small kernels);
+// *plan: what the passes that follow need to know of it.
+int rs16_engine::decode_eval(const DecodeGeom& g, const uint8_t* flags_a, const uint8_t* flags_b, EvalBufs& ev,
+                             DecodePlan* plan, hipStream_t s, rs16_error* err, size_t S, size_t nstripes,
+                             uint32_t vary, size_t bs_fa, size_t bs_fb, bool prepare) {
     // (a prepared decode's outputs in ev_main are about to be overwritten)
-    if (evset == &ev_main && !preparing)
+    if (&ev == &ev_main && !prepare)
         if (int rc = guard_eval(s, false, err)) return rc;
-    // Any evaluation other than the preparation itself also overwrites the
-    // path state below (e_ident, elog_fused, eval_in_col, var_ns) that a
-    // prepared decode reads -- whichever eval set it writes to (the
-    // pipelined host path's lanes use their own): the preparation is gone.
-    if (!preparing) prep.valid = false;
+    // Any evaluation other than the preparation itself drops the preparation,
+    // whichever buffers it writes to (the pipelined host path's lanes use
+    // their own).  A contract of the split decode (include/rs16.h), no longer
+    // a necessity: the preparation's plan is a value of its own.
+    if (!prepare) prep.valid = false;
     const size_t nv = vary > 1 ? vary : 1;
-    RS16_HIP(evset->work32.reserve(nv * VARY_WORK * 4));
-    RS16_HIP(evset->elog.reserve(nv * VARY_WORK * 4));
-    RS16_HIP(evset->zflag.reserve(nv * VARY_ZFLAGS));
-    RS16_HIP(evset->rbits.reserve(nv * VARY_RBITS * 4));
-    RS16_HIP(evset->lost.reserve(nv * VARY_LOST * 4));
-    RS16_HIP(evset->rcount.reserve(GF_ORDER / 64 * 8));
-    var_ns = vary > 1 ? vary : 0;
-    var_bs_fa = vary > 1 ? bs_fa : 0;
-    var_bs_fb = vary > 1 ? bs_fb : 0;
+    RS16_HIP(ev.work32.reserve(nv * VARY_WORK * 4));
+    RS16_HIP(ev.elog.reserve(nv * VARY_WORK * 4));
+    RS16_HIP(ev.zflag.reserve(nv * VARY_ZFLAGS));
+    RS16_HIP(ev.rbits.reserve(nv * VARY_RBITS * 4));
+    RS16_HIP(ev.lost.reserve(nv * VARY_LOST * 4));
+    RS16_HIP(ev.rcount.reserve(GF_ORDER / 64 * 8));
+    DecodePlan& p = *plan = DecodePlan{};
+    p.ev = &ev;
+    p.var_ns = vary > 1 ? vary : 0;
+    p.var_bs_fa = vary > 1 ? bs_fa : 0;
+    p.var_bs_fb = vary > 1 ? bs_fb : 0;
     ErasureSpec es{};
     es.flags_a = flags_a;
     es.flags_b = flags_b;
@@ -527,28 +525,28 @@ int rs16_engine::decode_eval(const DecodeGeom& g, const uint8_t* flags_a, const 
     // the pass metadata: received bitmap, and zero flags of the first pass's
     // tiles (2^lo rows, lo = L/2) when the decode takes more than one pass
     const int L = ilog2(g.n);
-    es.rbits = (uint32_t*)evset->rbits.p;
-    es.zflags = L > 8 ? (uint8_t*)evset->zflag.p : nullptr;
+    es.rbits = (uint32_t*)ev.rbits.p;
+    es.zflags = L > 8 ? (uint8_t*)ev.zflag.p : nullptr;
     es.n = g.n;
     es.zlo = (uint32_t)(L / 2);
     // the lost originals' row range prunes the general multi-pass decode
     // (the half-transform decode restores every original: not needed)
     const bool prune = !half_decode(g) && L > 8;
-    es.lostpart = prune ? (uint32_t*)evset->lost.p : nullptr;
-    es.lostrange = prune ? (uint32_t*)evset->lost.p + 512 : nullptr;
+    es.lostpart = prune ? (uint32_t*)ev.lost.p : nullptr;
+    es.lostrange = prune ? (uint32_t*)ev.lost.p + 512 : nullptr;
     es.orig_b = g.high ? 1 : 0;
     es.lost_all = g.repair ? 1 : 0;  // (the repair stores the lost rows of both segments)
     es.wanted = g.select ? g.wanted : nullptr;  // (the selective decode: the interval of the wanted rows)
-    es.rcount = (uint32_t*)evset->rcount.p;
+    es.rcount = (uint32_t*)ev.rcount.p;
     es.diag = (uint32_t)diag;
     last_dec = g;
     last_dec_valid = true;
-    if (var_ns) {
+    if (p.var_ns) {
         // every stripe's own metadata; no received counts (rs16_decode_check
         // covers the single-pattern calls)
-        es.nstripes = var_ns;
-        es.bs_fa = var_bs_fa;
-        es.bs_fb = var_bs_fb;
+        es.nstripes = p.var_ns;
+        es.bs_fa = p.var_bs_fa;
+        es.bs_fb = p.var_bs_fb;
         es.bs_work = es.bs_elog = VARY_WORK;
         es.bs_rbits = VARY_RBITS;
         es.bs_zflags = VARY_ZFLAGS;
@@ -558,31 +556,28 @@ int rs16_engine::decode_eval(const DecodeGeom& g, const uint8_t* flags_a, const 
     }
     // A whole-half erasure: every log is 0, nothing to evaluate (the passes
     // count the received rows for rs16_decode_check)
-    e_ident = identity_logs(g, vary);
-    if (e_ident) {
-        eval_in_col = elog_fused = false;
-        return RS16_OK;
-    }
+    p.ident = identity_logs(g, vary);
+    if (p.ident) return RS16_OK;
     // High-rate half decodes of 2^9 / 2^10-row halves through the column
     // codec: it evaluates the polynomial itself (an n-point XOR convolution,
     // rs16_col.hip) and writes rcount; no kernel here.
     // (the repair takes the pass codec at every size: COL_DEC_GEN restores originals only)
-    eval_in_col = S && !g.repair && (half_decode(g) ? g.high && col_ok(ilog2(g.n) - 1, S, nstripes)
-                                                    : col_ok(ilog2(g.n), S, nstripes, true));
-    if (eval_in_col) return RS16_OK;
+    p.eval_in_col = S && !g.repair && (half_decode(g) ? g.high && col_ok(ilog2(g.n) - 1, S, nstripes)
+                                                      : col_ok(ilog2(g.n), S, nstripes, true));
+    if (p.eval_in_col) return RS16_OK;
     // The decode passes that read erasure logs finish eval_poly's last
     // 256-point FWHT themselves, for the 256-row block of their tile's rows
     // (one kernel less) -- except the one-pass half-transform decode, whose
     // gather and reveal rows lie in different blocks.
     const bool small = g.high && g.n <= 2048 && !(diag & DIAG_EVAL_FULL);
     // (the column codec's half decodes of 2^9 / 2^10 rows finish it too)
-    elog_fused = !(half_decode(g) && ilog2(g.n) - 1 <= 8);
-    uint32_t *work = (uint32_t*)evset->work32.p, *elog = (uint32_t*)evset->elog.p;
+    p.elog_fused = !(half_decode(g) && ilog2(g.n) - 1 <= 8);
+    uint32_t *work = (uint32_t*)ev.work32.p, *elog = (uint32_t*)ev.elog.p;
     return profiled(PROF_EVAL_POLY, s, err, [&](uint64_t* stamps) {
         es.stamps = stamps;
         // erasures are zero from row n on: only n/256 live blocks (rs16_misc.hip)
-        if (small) return launch_eval_poly_small(es, (uint32_t)g.n, work, elog, d_log_walsh, s, !elog_fused);
-        return launch_eval_poly_from_flags(es, work, elog, d_log_walsh, s, !elog_fused);
+        if (small) return launch_eval_poly_small(es, (uint32_t)g.n, work, elog, d_log_walsh, s, !p.elog_fused);
+        return launch_eval_poly_from_flags(es, work, elog, d_log_walsh, s, !p.elog_fused);
     });
 }
 
@@ -643,10 +638,12 @@ int rs16_engine::mid_tables(int L, const uint32_t** out, rs16_error* err) {
     return RS16_OK;
 }
 
-// The pass sequence of a decode, given what decode_eval left in evset->elog /
-// evset->work32 (erasure logs), evset->rbits (received rows) and evset->zflag (zero tiles).
+// The pass sequence of a decode, given the plan of its decode_eval and what that
+// left in the plan's buffers: elog / work32 (erasure logs), rbits (received
+// rows) and zflag (zero tiles).
 int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, const DecodeSegs& v, uint8_t* Z, uint8_t* U,
-                               uint32_t* rcount, size_t nst, hipStream_t s, rs16_error* err) {
+                               const DecodePlan& plan, uint32_t* rcount, size_t nst, hipStream_t s, rs16_error* err) {
+    const EvalBufs& ev = *plan.ev;
     PassArgs a = base_args(this, S);
     a.S_seg = a.S_rest = v.S_user;
     a.seg_a = v.seg_a;
@@ -656,15 +653,15 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, const DecodeSegs& 
     a.a_count = g.a_count;
     a.chunk = g.chunk;
     a.b_count = g.b_count;
-    a.elog = (const uint32_t*)evset->elog.p;
-    a.ework = elog_fused ? (const uint32_t*)evset->work32.p : nullptr;
+    a.elog = (const uint32_t*)ev.elog.p;
+    a.ework = plan.elog_fused ? (const uint32_t*)ev.work32.p : nullptr;
     a.rest = v.rest;
     a.rest_seg_b = g.high ? 1 : 0;
-    a.rbits = (const uint32_t*)evset->rbits.p;
+    a.rbits = (const uint32_t*)ev.rbits.p;
     a.skew_ifft = a.skew_fft = 0;
-    if (var_ns) {  // stripes with losses of their own (decode_eval's per-stripe metadata)
-        a.bs_fa = var_bs_fa;
-        a.bs_fb = var_bs_fb;
+    if (plan.var_ns) {  // stripes with losses of their own (decode_eval's per-stripe metadata)
+        a.bs_fa = plan.var_bs_fa;
+        a.bs_fb = plan.var_bs_fb;
         a.bs_elog = VARY_WORK;
         a.bs_rbits = VARY_RBITS;
         a.bs_zflags = VARY_ZFLAGS;
@@ -689,6 +686,18 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, const DecodeSegs& 
         a.bs_out = bs_out;
         return tiles * ns;
     };
+    // a column launch of the decode: col_args and what the two forms below share
+    auto col_dec = [&](const uint8_t* in, size_t bs_in, uint32_t in_rows, uint32_t out_rows, uint32_t src,
+                       uint32_t dst) {
+        ColArgs c = col_args(in, v.S_user, v.rest, v.S_user, S, in_rows, out_rows, src, dst);
+        c.elog = (const uint32_t*)ev.elog.p;
+        c.nstripes = ns;
+        c.bs_in = bs_in;
+        c.bs_out = v.bs_rest;
+        c.chunk = g.chunk;
+        c.bs_flags_o = plan.var_bs_fb;
+        return c;
+    };
     const int L = ilog2(g.n);
     if (half_decode(g)) {
         const uint32_t half = g.n / 2, src = g.high ? 0 : half, dst = g.high ? half : 0;
@@ -696,7 +705,7 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, const DecodeSegs& 
         a.row_base_in = a.skew_ifft = src;
         a.row_base_out = a.skew_fft = dst;
         const int Lh = L - 1;
-        if (e_ident) {
+        if (plan.ident) {
             // Identity multipliers (identity_logs): gather the received half
             // as it is -> IFFT -> FFT -> its rows are the restored originals,
             // i.e. the encoder's three passes with the half's twiddles; the
@@ -733,31 +742,21 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, const DecodeSegs& 
         // 2^6 .. 2^10-row halves: the whole decode in one launch (rs16_col.hip)
         // -- high rate with the polynomial in the kernel; the low rate from
         // 2^9 rows on, on eval_poly's output
-        const bool col_eval = eval_in_col && g.high;
+        const bool col_eval = plan.eval_in_col && g.high;
         if (!col_eval && Lh <= 8) {
             a.ework = nullptr;  // (decode_eval did the whole eval_poly)
             RS16_PASS(DEC_HALF_SINGLE, Lh, a, batch(1, 0, 0, 0), s);
             return RS16_OK;
         }
         if (col_eval || col_ok(Lh, S, ns)) {
-            ColArgs c = col_args();
-            c.in = g.high ? v.seg_a : v.seg_b;
+            ColArgs c = g.high ? col_dec(v.seg_a, v.bs_a, g.a_count, orig, src, dst)
+                               : col_dec(v.seg_b, v.bs_b, g.b_count, orig, src, dst);
             c.flags = g.high ? v.fl_a : v.fl_b;
-            c.in_rows = g.high ? g.a_count : g.b_count;
-            c.out = v.rest;
-            c.S_in = c.S_out = v.S_user;
-            c.qrow = (uint32_t)(S / 8);
-            c.nstripes = ns;
-            c.bs_in = g.high ? v.bs_a : v.bs_b;
-            c.bs_out = v.bs_rest;
-            c.out_rows = orig;
-            c.base_in = c.skew_ifft = src;
-            c.base_out = c.skew_fft = dst;
-            c.chunk = g.chunk;
+            c.base_in = src;
+            c.base_out = dst;
             c.e_pad = 1;  // (high rate: padding rows erased, nothing above the originals)
-            c.bs_flags = g.high ? var_bs_fa : var_bs_fb;
-            c.bs_flags_o = var_bs_fb;
-            c.bs_elog = var_ns ? VARY_WORK : 0;
+            c.bs_flags = g.high ? plan.var_bs_fa : plan.var_bs_fb;
+            c.bs_elog = plan.var_ns ? VARY_WORK : 0;
             if (col_eval) {
                 // eval_poly in the kernel (decode_eval launched nothing)
                 c.flags_o = v.fl_b;
@@ -766,7 +765,7 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, const DecodeSegs& 
                 c.rcount = rcount;
                 return col(c, Lh, COL_DEC_EVAL, s, err);
             }
-            c.elog = (const uint32_t*)evset->work32.p;  // (eval_poly without its last H_lo: elog_fused)
+            c.elog = (const uint32_t*)ev.work32.p;  // (eval_poly without its last H_lo: plan.elog_fused)
             return col(c, Lh, COL_DEC_EWORK, s, err);
         }
         const int lo = row_split(Lh).lo, hi = row_split(Lh).hi;
@@ -782,34 +781,23 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, const DecodeSegs& 
         RS16_PASS(DEC_HALF_LAST, lo, a, batch((orig + (1u << lo) - 1) >> lo, zs, 0, 0), s);
         return RS16_OK;
     }
-    if (eval_in_col) {
+    if (plan.eval_in_col) {
         // up to 2^11 work rows: the whole general decode in one launch,
         // polynomial and formal derivative in the kernel (rs16_col.hip);
         // segment A / B = recovery / originals (high rate) or originals /
         // recovery (low rate, rate_low.rs:168-247)
-        ColArgs c = col_args();
-        c.in = v.seg_a;
+        ColArgs c = col_dec(v.seg_a, v.bs_a, g.a_count, g.high ? g.b_count : g.a_count, 0, 0);
         c.flags = v.fl_a;
-        c.in_rows = g.a_count;
         c.in_b = v.seg_b;
         c.bs_in_b = v.bs_b;
         c.flags_o = v.fl_b;
         c.o_rows = g.b_count;
-        c.chunk = g.chunk;
         c.rev_a = g.high ? 0 : 1;
         c.e_pad = g.high ? 1 : 0;
         c.e_tail = g.high ? 0 : 1;
         c.e_k = g.high ? 0 : host_tables().col_k[L];
-        c.out = v.rest;
-        c.S_in = c.S_out = v.S_user;
-        c.qrow = (uint32_t)(S / 8);
-        c.nstripes = ns;
-        c.bs_in = v.bs_a;
-        c.bs_out = v.bs_rest;
-        c.out_rows = g.high ? g.b_count : g.a_count;
         c.rcount = rcount;
-        c.bs_flags = var_bs_fa;
-        c.bs_flags_o = var_bs_fb;
+        c.bs_flags = plan.var_bs_fa;
         c.wanted = g.select ? g.wanted : nullptr;  // (lost[] = lost and wanted; the polynomial follows the flags)
         return col(c, L, g.select ? COL_DEC_GEN_SEL : COL_DEC_GEN, s, err);
     }
@@ -821,8 +809,8 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, const DecodeSegs& 
     const int lo = L / 2, hi = L - lo;
     // One flag per DEC_FIRST tile (2^hi <= 256): tiles without a received
     // row are skipped by DEC_FIRST and read as zero by DEC_MID / DEC_LAST.
-    a.zflags = (const uint8_t*)evset->zflag.p;
-    a.lostrange = (const uint32_t*)evset->lost.p + 512;  // (written by decode_eval)
+    a.zflags = (const uint8_t*)ev.zflag.p;
+    a.lostrange = (const uint32_t*)ev.lost.p + 512;  // (written by decode_eval)
     // Launch only the tiles that can hold a received row: a segment with no
     // received shard contributes none (its tiles are flagged by block 0).
     const uint32_t tile = 1u << lo, ntiles = 1u << hi;
@@ -935,10 +923,11 @@ int rs16_engine::decode_passes(const DecodeGeom& g, size_t S, const DecodeSegs& 
 // The FFT half of the multi-chunk encoders: FFT of nch chunks of Z (batched
 // like the IFFTs below, skew_delta applied to absolute rows), recovery rows
 // [0, m) stored to d_rec.
-int rs16_engine::fft_to_recovery(size_t m, size_t S, size_t S_user, const uint8_t* src, uint8_t* Z, uint8_t* d_rec,
-                                 size_t chunk, uint32_t nch, uint32_t skew, hipStream_t s, rs16_error* err,
-                                 const VerifySink* vs) {
-    const int L = ilog2(chunk), lo = L <= 8 ? L : L / 2, hi = L - lo;
+int rs16_engine::fft_to_recovery(const EncodeForm& f, size_t m, size_t S, size_t S_user, const uint8_t* src,
+                                 uint8_t* Z, uint8_t* d_rec, uint32_t nch, uint32_t skew, hipStream_t s,
+                                 rs16_error* err, const VerifySink* vs) {
+    const size_t chunk = f.chunk;
+    const int lo = f.lo, hi = f.hi;
     PassArgs a = base_args(this, S);
     a.skew_fft = skew;
     // src != Z: every chunk's FFT reads the one chunk at src (the first pass only)
@@ -971,43 +960,29 @@ int rs16_engine::fft_to_recovery(size_t m, size_t S, size_t S_user, const uint8_
 // inside a chunk, so every chunk's IFFT runs in the same launches (tiles over
 // all chunks; the first pass gathers the originals, rows >= k read as zero),
 // then one XOR reduction, then the FFT.
-int rs16_engine::encode_high_multi(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec,
-                                   uint8_t* Z, hipStream_t s, rs16_error* err, const VerifySink* vs) {
-    const size_t chunk = next_pow2(m);
-    const uint32_t nch = (uint32_t)((k + chunk - 1) / chunk);
-    const int L = ilog2(chunk), lo = L <= 8 ? L : L / 2, hi = L - lo;
-    // (a verify sink: the shapes of verify_fusable only -- none of the branches before the passes)
-    if (vs && !verify_fusable(true, k, m, S, 1)) return set_error(err, RS16_INVALID_ARGUMENT);
-    if (L == 0) {  // one-row chunks: the single recovery row is the XOR of the originals
+int rs16_engine::encode_high_multi(const EncodeForm& f, size_t k, size_t m, size_t S, size_t S_user,
+                                   const uint8_t* d_orig, uint8_t* d_rec, uint8_t* Z, hipStream_t s, rs16_error* err,
+                                   const VerifySink* vs) {
+    const size_t chunk = f.chunk;
+    const uint32_t nch = f.nch;
+    const int L = f.L, lo = f.lo, hi = f.hi;
+    // (a verify sink: the passes only -- none of the forms before them)
+    if (vs && !f.verify_fusable()) return set_error(err, RS16_INVALID_ARGUMENT);
+    if (f.kind == f.ROWS) {  // one-row chunks: the single recovery row is the XOR of the originals
         if (Z != d_orig) RS16_HIP(hipMemcpy2DAsync(Z, S, d_orig, S_user, S, k, hipMemcpyDeviceToDevice, s));
         RS16_HIP(launch_xor_chunks(Z, S, nch, s));
         if (d_rec != Z) RS16_HIP(hipMemcpyAsync(d_rec, Z, S, hipMemcpyDeviceToDevice, s));
         return RS16_OK;
     }
-    if (!vs && L == (int)COLM_L && nch <= COLM_MAX_CHUNKS && col_ok(L, S, 1))
-        return col_multi(k, m, S, S_user, d_orig, d_rec, nch, true, s, err);
-    if (!vs && col_chunks_ok(L, nch, S, true)) {
+    if (f.kind == f.COLM) return col_multi(k, m, S, S_user, d_orig, d_rec, nch, true, s, err);
+    if (f.kind == f.COL_CHUNKS) {
         // 256 / 512 / 1024-row chunks: every chunk's IFFT into Z (one
         // workgroup per quad column and chunk), then the FFT of their XOR
-        ColArgs c = col_args();
-        c.in = d_orig;
-        c.S_in = S_user;
-        c.out = Z;
-        c.S_out = S;
-        c.qrow = (uint32_t)(S / 8);
-        c.in_rows = (uint32_t)k;
-        c.out_rows = (uint32_t)(nch * chunk);
-        c.skew_ifft = (uint32_t)chunk;
+        ColArgs c = col_args(d_orig, S_user, Z, S, S, k, nch * chunk, chunk, 0);
         c.nch = nch;
         if (int rc = col(c, L, COL_ENC_IFFT, s, err)) return rc;
-        c.in = Z;
-        c.S_in = S;
-        c.out = d_rec;
-        c.S_out = S_user;
-        c.in_rows = (uint32_t)(nch * chunk);
-        c.out_rows = (uint32_t)m;
-        c.skew_ifft = 0;
-        c.skew_fft = 0;
+        c = col_args(Z, S, d_rec, S_user, S, nch * chunk, m, 0, 0);
+        c.nch = nch;
         return col(c, L, COL_ENC_FFTX, s, err);
     }
     PassArgs a = base_args(this, S);
@@ -1024,7 +999,7 @@ int rs16_engine::encode_high_multi(size_t k, size_t m, size_t S, size_t S_user, 
         RS16_PASS(GEN_IFFT, hi, a, nch << lo, s);
     }
     RS16_HIP(launch_xor_chunks(Z, chunk * S, nch, s));
-    return fft_to_recovery(m, S, S_user, Z, Z, d_rec, chunk, 1, 0, s, err, vs);
+    return fft_to_recovery(f, m, S, S_user, Z, Z, d_rec, 1, 0, s, err, vs);
 }
 
 // LowRateEncoder::encode (src/rate/rate_low.rs:44-83): IFFT of the
@@ -1033,35 +1008,24 @@ int rs16_engine::encode_high_multi(size_t k, size_t m, size_t S, size_t S_user, 
 // (absolute rows, skew_delta = chunk), recovery = rows [0, m).  The copies
 // are not made: the transformed chunk goes to the scratch U and the FFT's
 // first pass reads it for every chunk (PassArgs::in_rows_mask).
-int rs16_engine::encode_low_multi(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec,
-                                  uint8_t* Z, uint8_t* U, hipStream_t s, rs16_error* err, const VerifySink* vs) {
-    const size_t chunk = next_pow2(k);
-    const uint32_t nch = (uint32_t)((m + chunk - 1) / chunk);
-    const int L = ilog2(chunk), lo = L <= 8 ? L : L / 2, hi = L - lo;
-    // (a verify sink: the shapes of verify_fusable only -- none of the branches before the passes)
-    if (vs && !verify_fusable(false, k, m, S, 1)) return set_error(err, RS16_INVALID_ARGUMENT);
-    if (L == 0) {  // one original: every transform is the identity, every recovery row a copy
+int rs16_engine::encode_low_multi(const EncodeForm& f, size_t k, size_t m, size_t S, size_t S_user,
+                                  const uint8_t* d_orig, uint8_t* d_rec, uint8_t* Z, uint8_t* U, hipStream_t s,
+                                  rs16_error* err, const VerifySink* vs) {
+    const size_t chunk = f.chunk;
+    const uint32_t nch = f.nch;
+    const int L = f.L, lo = f.lo, hi = f.hi;
+    // (a verify sink: the passes only -- none of the forms before them)
+    if (vs && !f.verify_fusable()) return set_error(err, RS16_INVALID_ARGUMENT);
+    if (f.kind == f.ROWS) {  // one original: every transform is the identity, every recovery row a copy
         if (Z != d_orig) RS16_HIP(hipMemcpyAsync(Z, d_orig, S, hipMemcpyDeviceToDevice, s));
         RS16_HIP(launch_copy_chunks(Z, S, nch, s));
         if (d_rec != Z) RS16_HIP(hipMemcpy2DAsync(d_rec, S_user, Z, S, S, m, hipMemcpyDeviceToDevice, s));
         return RS16_OK;
     }
-    if (nch == 1 && col_ok(L, S, 1)) {
-        // one recovery chunk of 512 / 1024 rows: one launch (rs16_col.hip)
-        ColArgs c = col_args();
-        c.in = d_orig;
-        c.out = d_rec;
-        c.S_in = c.S_out = S_user;
-        c.qrow = (uint32_t)(S / 8);
-        c.in_rows = (uint32_t)k;
-        c.out_rows = (uint32_t)m;
-        c.skew_ifft = 0;
-        c.skew_fft = (uint32_t)chunk;
-        return col(c, L, COL_ENC, s, err);
-    }
-    if (nch > 1 && L == (int)COLM_L && nch <= COLM_MAX_CHUNKS && col_ok(L, S, 1))
-        return col_multi(k, m, S, S_user, d_orig, d_rec, nch, false, s, err);
-    if (nch > 1 && col_chunks_ok(L, nch, S, false)) {
+    // one recovery chunk of 512 / 1024 rows: one launch (rs16_col.hip)
+    if (f.kind == f.COL) return col(col_args(d_orig, S_user, d_rec, S_user, S, k, m, 0, chunk), L, COL_ENC, s, err);
+    if (f.kind == f.COLM) return col_multi(k, m, S, S_user, d_orig, d_rec, nch, false, s, err);
+    if (f.kind == f.COL_CHUNKS) {
         // 256 / 512 / 1024-row chunks: one launch, one workgroup per (quad
         // column, recovery chunk), each running the originals' IFFT itself.
         // Every chunk's workgroups read the originals, and chunk 0's write
@@ -1079,16 +1043,7 @@ int rs16_engine::encode_low_multi(size_t k, size_t m, size_t S, size_t S_user, c
             src = U;
             s_in = S;
         }
-        ColArgs c = col_args();
-        c.in = src;
-        c.out = d_rec;
-        c.S_in = s_in;
-        c.S_out = S_user;
-        c.qrow = (uint32_t)(S / 8);
-        c.in_rows = (uint32_t)k;
-        c.out_rows = (uint32_t)m;
-        c.skew_ifft = 0;
-        c.skew_fft = (uint32_t)chunk;
+        ColArgs c = col_args(src, s_in, d_rec, S_user, S, k, m, 0, chunk);
         c.nch = nch;
         return col(c, L, COL_ENC, s, err);
     }
@@ -1108,5 +1063,5 @@ int rs16_engine::encode_low_multi(size_t k, size_t m, size_t S, size_t S_user, c
         a.lo = lo;
         RS16_PASS(GEN_IFFT, hi, a, 1u << lo, s);
     }
-    return fft_to_recovery(m, S, S_user, U, Z, d_rec, chunk, nch, (uint32_t)chunk, s, err, vs);
+    return fft_to_recovery(f, m, S, S_user, U, Z, d_rec, nch, (uint32_t)chunk, s, err, vs);
 }

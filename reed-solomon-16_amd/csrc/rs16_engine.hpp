@@ -125,6 +125,28 @@ struct DecodeSegs {
     size_t S_user = 0;
 };
 
+// How a shape is encoded (rs16_engine::encode_form): the chunk geometry -- nch
+// chunks of chunk = 2^L rows, the passes' row split lo + hi = L -- and which
+// branch of the encoders runs.  one_chunk: the one-chunk high rate (k <= chunk:
+// encode_high_fused, the shape with batched launches and column slices), whose
+// kinds are COL, ONE_PASS (L <= 8) and THREE_PASS; the multi-chunk high rate
+// and the low rate have ROWS (L == 0: the XOR of the rows / the copies), COL
+// (the low rate's one recovery chunk in one column launch), COLM, COL_CHUNKS
+// and PASSES.
+struct EncodeForm {
+    enum Kind { COL, ONE_PASS, THREE_PASS, ROWS, COLM, COL_CHUNKS, PASSES } kind;
+    bool one_chunk;
+    size_t chunk;
+    uint32_t nch;
+    int L, lo, hi;
+    // The encode ends in a pass-codec store pass that has a comparing form
+    // (ENC_SINGLE_VFY at T >= 1, ENC_LAST_VFY at T >= 4, fft_to_recovery's last
+    // pass at T = lo): the shapes a VerifySink may be given for.
+    bool verify_fusable() const {
+        return kind == ONE_PASS ? L >= 1 : kind == THREE_PASS || (kind == PASSES && lo >= 4);
+    }
+};
+
 }  // namespace rs16
 
 struct rs16_encoder;
@@ -161,9 +183,8 @@ struct rs16_engine {
     // transform size L (mid_tables; built on first use)
     rs16::DevBuf mid_tab[17];
     // The decode's eval_poly outputs / pass metadata (written by decode_eval,
-    // read by decode_passes).  `evset` points at the set the next decode uses:
-    // ev_main, or one of the pipelined host path's per-lane sets (so that
-    // two lanes' decodes never share them).
+    // read by decode_passes): ev_main, or one of the pipelined host path's
+    // per-lane sets (so that two lanes' decodes never share them).
     struct EvalBufs {
         rs16::DevBuf work32, elog;
         rs16::DevBuf zflag;   // per DEC_FIRST tile, 1 = no received row (tile skipped, rows zero)
@@ -173,7 +194,16 @@ struct rs16_engine {
         void release() { work32.release(), elog.release(), zflag.release(), rbits.release(), lost.release(), rcount.release(); }
     };
     EvalBufs ev_main, ev_lane[2];
-    EvalBufs* evset = &ev_main;
+    // What one decode_eval left behind, the value decode_passes works from: the
+    // buffers it wrote to and what it decided about them.
+    struct DecodePlan {
+        EvalBufs* ev = nullptr;
+        bool ident = false;        // every erasure log is 0 (identity_logs): no eval_poly kernel ran
+        bool elog_fused = false;   // the final 256-point FWHT is left to the passes (ev->work32)
+        bool eval_in_col = false;  // eval_poly is left to the column codec (COL_DEC_EVAL / COL_DEC_GEN)
+        uint32_t var_ns = 0;       // stripes with losses of their own (0: shared) ...
+        uint64_t var_bs_fa = 0, var_bs_fb = 0;  // ... and their flags' strides
+    };
     // Split decode (rs16_decode_prepare / rs16_decode_device_prepared): the
     // prepared received pattern, whose eval_poly went to ev_main on the
     // prepare's stream; prep_ev marks its end.  While prep_pending, any other
@@ -185,10 +215,10 @@ struct rs16_engine {
         const uint8_t* fl_a = nullptr;
         const uint8_t* fl_b = nullptr;
         int nslices = 1;
+        DecodePlan plan;  // of its evaluation, which the prepared decode's passes get
     } prep;
     hipEvent_t prep_ev = nullptr;
     bool prep_pending = false;
-    bool preparing = false;
     // order stream s after a pending preparation's eval_poly (whose outputs
     // the caller is about to overwrite or read) and drop the preparation
     // unless it is the one being consumed
@@ -285,9 +315,6 @@ struct rs16_engine {
     // id stamp_prof get stamp_buf (RS16_STAMPS builds record into it)
     void* stamp_buf = nullptr;
     int stamp_prof = -1;
-    bool elog_fused = false;  // last decode_eval left the final 256-point FWHT to the passes (ws_work32)
-    bool eval_in_col = false; // last decode_eval left eval_poly to the column codec (COL_DEC_EVAL)
-    bool e_ident = false;     // last decode_eval found every erasure log 0 (identity_logs): no eval_poly kernel
     struct ProfRec {
         int id;
         hipEvent_t a, b;
@@ -304,51 +331,55 @@ struct rs16_engine {
     int fft(uint8_t* data, size_t S, size_t pos, size_t size, size_t skew_delta, hipStream_t s, rs16_error* err);
     int ifft(uint8_t* data, size_t S, size_t pos, size_t size, size_t skew_delta, hipStream_t s, rs16_error* err);
 
-    // Fused HighRate single-chunk encode: originals rows [0,k) of d_orig ->
-    // recovery rows [0,m) of d_rec, using Z (chunk rows) as work.
+    // The one decision of how a shape is encoded (EncodeForm): nstripes is the
+    // stripes of one batched launch, which only the one-chunk high rate has
+    // (other shapes run stripe by stripe: their column limits count one stripe).
+    rs16::EncodeForm encode_form(bool high, size_t k, size_t m, size_t S, size_t nstripes) const;
+    // Fused HighRate single-chunk encode (f.one_chunk): originals rows [0,k) of
+    // d_orig -> recovery rows [0,m) of d_rec, using Z (chunk rows) as work.
     // S = row width worked on (a column slice of the caller's arrays when
     // S < S_user), S_user = row stride of d_orig / d_rec (Z: stride S).
-    int encode_high_fused(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec, uint8_t* Z,
-                          hipStream_t s, rs16_error* err, size_t nstripes = 1, size_t bs_orig = 0, size_t bs_rec = 0,
-                          const rs16::VerifySink* vs = nullptr);
+    // f (here and in the multi-chunk encoders): encode_form of the call's shape.
+    int encode_high_fused(const rs16::EncodeForm& f, size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig,
+                          uint8_t* d_rec, uint8_t* Z, hipStream_t s, rs16_error* err, size_t nstripes = 1,
+                          size_t bs_orig = 0, size_t bs_rec = 0, const rs16::VerifySink* vs = nullptr);
     // vs (here and in the multi-chunk encoders): the last launch is the
     // comparing program (ENC_SINGLE_VFY / ENC_LAST_VFY) on the sink, d_rec is
-    // not used, and the work rows keep the shards' form; only for the shapes
-    // of verify_fusable (others: RS16_INVALID_ARGUMENT, nothing launched).
-    bool verify_fusable(bool high, size_t k, size_t m, size_t S, size_t nstripes) const;
+    // not used, and the work rows keep the shards' form; only for the forms of
+    // EncodeForm::verify_fusable (others: RS16_INVALID_ARGUMENT, nothing launched).
     // Fused decode (both rates) of one stripe: v's seg_a / seg_b gather
     // sources with device flags; lost originals written to v.rest; Z, U work
     // (n rows each; Z may alias the sources when they live at their work
     // positions).  S = row width (Z, U: stride S)
     int decode_fused(const rs16::DecodeGeom& g, size_t S, const rs16::DecodeSegs& v, uint8_t* Z, uint8_t* U,
                      hipStream_t s, rs16_error* err);
-    // decode_fused = decode_eval (erasure logs into ws_elog) + decode_passes.
+    // decode_fused = decode_eval (erasure logs into ev.elog, what it decided
+    // into *plan) + decode_passes (given that plan).
     // S / nstripes: the width of the decode_passes launches that follow (0:
     // unknown); when the column codec will run them as a high-rate half
     // decode it computes eval_poly itself and no kernel is launched here.
     // vary > 1: nstripes = vary stripes with losses of their own, stripe i's
     // flags at flags_a / flags_b + i bs_fa / bs_fb bytes: one grid row of the
-    // eval kernels per stripe, per-stripe metadata (VARY_* strides below),
-    // which the decode_passes that follow read (var_* state).
+    // eval kernels per stripe, per-stripe metadata (VARY_* strides below).
+    // prepare: the evaluation of rs16_decode_prepare, which keeps the
+    // preparation it is making.
     // Every erasure log of the decode is 0 (a whole-half erasure, DESIGN.md
     // 3.13): the multipliers are identities and eval_poly is not launched.
     bool identity_logs(const rs16::DecodeGeom& g, uint32_t vary) const;
     // Device tables of the L-bit general decode's middle-pass matrix
     // (mid_matrix_entries), uploaded on first use.
     int mid_tables(int L, const uint32_t** out, rs16_error* err);
-    int decode_eval(const rs16::DecodeGeom& g, const uint8_t* flags_a, const uint8_t* flags_b, hipStream_t s,
-                    rs16_error* err, size_t S = 0, size_t nstripes = 1, uint32_t vary = 0, size_t bs_fa = 0,
-                    size_t bs_fb = 0);
+    int decode_eval(const rs16::DecodeGeom& g, const uint8_t* flags_a, const uint8_t* flags_b, EvalBufs& ev,
+                    DecodePlan* plan, hipStream_t s, rs16_error* err, size_t S = 0, size_t nstripes = 1,
+                    uint32_t vary = 0, size_t bs_fa = 0, size_t bs_fb = 0, bool prepare = false);
     // per-stripe decode metadata of a batch with losses of its own
     static constexpr uint32_t VARY_WORK = rs16::GF_ORDER, VARY_RBITS = rs16::GF_ORDER / 32, VARY_ZFLAGS = 256,
                               VARY_LOST = 520;
-    uint32_t var_ns = 0;           // last decode_eval: stripes with losses of their own (0: shared)
-    uint64_t var_bs_fa = 0, var_bs_fb = 0;
     // rcount: where a column decode that evaluates the polynomial itself
-    // writes the received counts (ErasureSpec::rcount layout): ws_rcount on
+    // writes the received counts (ErasureSpec::rcount layout): ev_main.rcount on
     // the call's own stream, a buffer of their own for concurrent slots.
     int decode_passes(const rs16::DecodeGeom& g, size_t S, const rs16::DecodeSegs& v, uint8_t* Z, uint8_t* U,
-                      uint32_t* rcount, size_t nstripes, hipStream_t s, rs16_error* err);
+                      const DecodePlan& plan, uint32_t* rcount, size_t nstripes, hipStream_t s, rs16_error* err);
     // The half-transform decode applies (every original lost, originals
     // segment = one half of the work rows).
     static bool half_decode(const rs16::DecodeGeom& g);
@@ -369,19 +400,26 @@ struct rs16_engine {
     int col_multi(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec, uint32_t nch,
                   bool high, hipStream_t s, rs16_error* err);
     int col_tables(hipStream_t s, rs16_error* err);
-    rs16::ColArgs col_args() const;
+    // A column launch of one stripe and one chunk: in_rows rows at `in` (pitch
+    // S_in) -> out_rows rows at `out` (pitch S_out), S bytes of each, the two
+    // transforms' skew deltas.  The callers add what differs (stripes, chunks,
+    // the decodes' flags and logs).
+    rs16::ColArgs col_args(const uint8_t* in, size_t S_in, uint8_t* out, size_t S_out, size_t S, size_t in_rows,
+                           size_t out_rows, size_t skew_ifft, size_t skew_fft) const;
     // Multi-chunk encoders (high rate with k > chunk, low rate): every chunk's
     // transform in one batched set of launches.  d_orig rows have pitch
     // S_user, Z is the work space (work_count x S; may be d_orig), the
     // recovery rows [0, m) go to d_rec (pitch S_user; may be Z).
-    int encode_high_multi(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec,
-                          uint8_t* Z, hipStream_t s, rs16_error* err, const rs16::VerifySink* vs = nullptr);
+    int encode_high_multi(const rs16::EncodeForm& f, size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig,
+                          uint8_t* d_rec, uint8_t* Z, hipStream_t s, rs16_error* err,
+                          const rs16::VerifySink* vs = nullptr);
     // U: chunk x S bytes for the transformed originals, owned by the call's
     // stream (the engine's ws_u on the engine-ordered paths, a slot's own
     // buffer on concurrent slots); required -- there is no fallback.
-    int encode_low_multi(size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig, uint8_t* d_rec,
-                         uint8_t* Z, uint8_t* U, hipStream_t s, rs16_error* err, const rs16::VerifySink* vs = nullptr);
-    int fft_to_recovery(size_t m, size_t S, size_t S_user, const uint8_t* src, uint8_t* Z, uint8_t* d_rec,
-                        size_t chunk, uint32_t nch, uint32_t skew, hipStream_t s, rs16_error* err,
+    int encode_low_multi(const rs16::EncodeForm& f, size_t k, size_t m, size_t S, size_t S_user, const uint8_t* d_orig,
+                         uint8_t* d_rec, uint8_t* Z, uint8_t* U, hipStream_t s, rs16_error* err,
+                         const rs16::VerifySink* vs = nullptr);
+    int fft_to_recovery(const rs16::EncodeForm& f, size_t m, size_t S, size_t S_user, const uint8_t* src, uint8_t* Z,
+                        uint8_t* d_rec, uint32_t nch, uint32_t skew, hipStream_t s, rs16_error* err,
                         const rs16::VerifySink* vs = nullptr);
 };

@@ -366,13 +366,13 @@ def test_lifecycle_repair_leaves_no_path_state():
         x_r = DeviceArray(eng, m * sb)
         rs16.encode_device(k, m, sb, d_o.ptr, x_r.ptr, engine=eng)
         assert np.array_equal(x_r.download(shape=(m, sb)), recovery)
-        # every original lost: the identity decode (e_ident)
+        # every original lost: the identity decode (DecodePlan::ident)
         d_fo = DeviceArray.from_numpy(eng, np.zeros(k, np.uint8))
         d_fr = DeviceArray.from_numpy(eng, np.ones(m, np.uint8))
         d_x = DeviceArray.from_numpy(eng, np.full((k, sb), 0xA5, np.uint8))
         rs16.decode_device(k, m, sb, d_x.ptr, d_fo.ptr, x_r.ptr, d_fr.ptr, 0, m, engine=eng, check=True)
         assert np.array_equal(d_x.download(shape=(k, sb)), original)
-        # the repair again, then a general decode and a column-codec decode (eval_in_col)
+        # the repair again, then a general decode and a column-codec decode (DecodePlan::eval_in_col)
         d_o, d_r = repair(eng, k, m, sb, *pattern(k, m, "d"))
         check_whole(d_o, d_r, k, m, sb)
         for kk, mm in ((4096, 4096), (1000, 1000)):
