@@ -46,6 +46,8 @@
 //     before it writes any, so in / out may alias (the work-buffer API).
 //   * Workgroups are dealt to XCDs so that the 16 quad columns of a 128-byte
 //     line run on one XCD (one HBM fetch per line and XCD).
+#include <atomic>
+
 #include "rs16_internal.hpp"
 #include "rs16_fwht.hpp"
 #include "rs16_colops.hpp"
@@ -66,7 +68,8 @@ using namespace colops;
 //   A   the IFFT's tables of groups >= G2 (layer kb at group N - 2^(L-kb),
 //       group j = row >> (kb+1); G2 = 3N/4 = the first group of layer 2)
 //   B   the FFT's, likewise
-//   ELOG the decoder's erasure logs / polynomial scratch (2N x 4 bytes)
+//   ELOG the decoder's erasure logs / polynomial scratch (2N x 4 bytes; the
+//       general decoder's 2^11-row transform, COL_DEC_GEN only: N x 4)
 // (an encode launches ELOG bytes, the IFFT-only encode B: more workgroups
 // per CU)
 template <int L> struct ColSmem {
@@ -76,21 +79,24 @@ template <int L> struct ColSmem {
     static constexpr int A = IMG + N * 8;
     static constexpr int B = A + (N - 1 - G0) * 80;
     static constexpr int ELOG = B + (N - 1 - G0) * 80;
-    static constexpr int BYTES = ELOG + 2 * N * 4;
-    static_assert(L >= (int)COL_LMIN && L <= (int)COL_LMAX, "the column codec covers 2^6 .. 2^10 rows");
+    static constexpr int BYTES = ELOG + (L == (int)COL_LGEN ? N : 2 * N) * 4;
+    static_assert(L >= (int)COL_LMIN && L <= (int)COL_LGEN, "the column codec covers 2^6 .. 2^11 rows");
 };
 
-// The general decoder's 2^11-row transform (COL_DEC_GEN only): the same
-// layout (its logs: N x 4 bytes).
-template <> struct ColSmem<11> {
-    static constexpr int N = 2048;
-    static constexpr int G0 = N - N / 4;  // first group of layer 2
-    static constexpr int IMG = 0;
-    static constexpr int A = IMG + N * 8;
-    static constexpr int B = A + (N - 1 - G0) * 80;
-    static constexpr int ELOG = B + (N - 1 - G0) * 80;
-    static constexpr int BYTES = ELOG + N * 4;
+// Workgroup -> (stripe, byte offset of its quad column in a row), XCD-aware:
+// consecutive columns on one XCD (workgroups are dealt to the 8 XCDs
+// round-robin).  (The two fields by value: with ColArgs by reference the
+// COL_ENC_FFTX kernels compile to other code.)
+struct ColWg {
+    uint32_t st, offL;
 };
+__device__ __forceinline__ ColWg col_wg(uint32_t qrow, uint32_t nstripes) {
+    const uint32_t total = qrow * nstripes;
+    uint32_t g = blockIdx.x;
+    if ((total & 7u) == 0) g = (g & 7u) * (total >> 3) + (g >> 3);
+    const uint32_t st = g / qrow, q = g - st * qrow;
+    return {st, (q >> 3) * 64u + (q & 7u) * 4u};
+}
 
 // LDS byte offset of the table of layer kb for row r, direction FFT or not.
 template <int L, bool FFT> __device__ __forceinline__ uint32_t tab_off(int kb, uint32_t r) {
@@ -158,12 +164,9 @@ __device__ __forceinline__ uint32_t fold65535(uint32_t u) {
 }
 __device__ __forceinline__ uint32_t mod65535(int v) { return fold65535((uint32_t)(v + 65535 * 4096)); }
 
-// In-place n-point integer FWHT of the workgroup's points p = t + NT j
-// (x[j] in thread t): register layers (bits of j), lane layers (shuffles),
-// wave layers through the LDS scratch `sx` (n ints).  Ends with a barrier
-// (sx free again).
-template <int NT, int PTS> __device__ __forceinline__ void fwht_points(int (&x)[PTS], int* sx) {
-    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+// The integer FWHT's layers inside a thread and inside a wave.  Register
+// layers: the bits of j of x[j].
+template <int PTS> __device__ __forceinline__ void fwht_regs(int (&x)[PTS]) {
 #pragma unroll
     for (int d = 1; d < PTS; d <<= 1)
 #pragma unroll
@@ -173,33 +176,40 @@ template <int NT, int PTS> __device__ __forceinline__ void fwht_points(int (&x)[
                 x[j] = u + v;
                 x[j + d] = u - v;
             }
-#define RS16_LANE(D)                                              \
-    if constexpr ((D) < NT) {                                     \
-        _Pragma("unroll") for (int j = 0; j < PTS; j++) {         \
-            const int p = xshfl<(D)>(x[j]);                       \
-            x[j] = (lane & (D)) ? p - x[j] : x[j] + p;            \
-        }                                                         \
-    }
-    RS16_LANE(1) RS16_LANE(2) RS16_LANE(4) RS16_LANE(8)
-#undef RS16_LANE
-    // lane bits 4 and 5: trade places with register bit 0 (v_permlane16_swap /
-    // v_permlane32_swap, no LDS), butterfly the register pairs, trade back
+}
+// Lane layers of lane bits [B, NB): bits 0-3 by DPP shuffles; bits 4 and 5
+// trade places with register bit 0 (permlane_swap), butterfly the register
+// pairs, trade back.
+template <int PTS, int NB, int B = 0> __device__ __forceinline__ void fwht_lanes(int (&x)[PTS]) {
+    if constexpr (B < NB) {
+        if constexpr (B < 4) {
+            const uint32_t lane = threadIdx.x & 63;
 #pragma unroll
-    for (int lb = 4; lb <= 5 && (1 << lb) < NT; lb++)
+            for (int j = 0; j < PTS; j++) {
+                const int p = xshfl<(1 << B)>(x[j]);
+                x[j] = (lane & (1u << B)) ? p - x[j] : x[j] + p;
+            }
+        } else {
 #pragma unroll
-        for (int j = 0; j < PTS; j += 2) {
-            auto sw = [&]() {
-                const auto r = lb == 4 ? __builtin_amdgcn_permlane16_swap((uint32_t)x[j], (uint32_t)x[j + 1], false, false)
-                                       : __builtin_amdgcn_permlane32_swap((uint32_t)x[j], (uint32_t)x[j + 1], false, false);
-                x[j] = (int)r[0];
-                x[j + 1] = (int)r[1];
-            };
-            sw();
-            const int u = x[j], v = x[j + 1];
-            x[j] = u + v;
-            x[j + 1] = u - v;
-            sw();
+            for (int j = 0; j < PTS; j += 2) {
+                permlane_swap<B>(x[j], x[j + 1]);
+                const int u = x[j], v = x[j + 1];
+                x[j] = u + v;
+                x[j + 1] = u - v;
+                permlane_swap<B>(x[j], x[j + 1]);
+            }
         }
+        fwht_lanes<PTS, NB, B + 1>(x);
+    }
+}
+
+// In-place n-point integer FWHT of the workgroup's points p = t + NT j
+// (x[j] in thread t): register layers, lane layers, wave layers through the
+// LDS scratch `sx` (n ints).  Ends with a barrier (sx free again).
+template <int NT, int PTS> __device__ __forceinline__ void fwht_points(int (&x)[PTS], int* sx) {
+    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+    fwht_regs(x);
+    fwht_lanes<PTS, NT >= 64 ? 6 : (NT == 32 ? 5 : 4)>(x);
     constexpr int NW = NT / 64;
     if constexpr (NW > 1) {
 #pragma unroll
@@ -235,48 +245,6 @@ template <int NT> struct XLay {
     }
     static __device__ __forceinline__ uint32_t sw(uint32_t p) { return p ^ ((p >> 6) & 63u); }
 };
-// register layers, then lane layers of lane bits [B0, B1)
-template <int PTS, int B0, int B1, bool REG> __device__ __forceinline__ void fwht_lanes(int (&x)[PTS]) {
-    const uint32_t lane = threadIdx.x & 63;
-    if constexpr (REG) {
-#pragma unroll
-        for (int d = 1; d < PTS; d <<= 1)
-#pragma unroll
-            for (int j = 0; j < PTS; j++)
-                if (!(j & d)) {
-                    const int u = x[j], v = x[j + d];
-                    x[j] = u + v;
-                    x[j + d] = u - v;
-                }
-    }
-#define RS16_LANE(B)                                              \
-    if constexpr ((B) >= B0 && (B) < B1) {                        \
-        _Pragma("unroll") for (int j = 0; j < PTS; j++) {         \
-            const int p = xshfl<(1 << (B))>(x[j]);                \
-            x[j] = (lane & (1u << (B))) ? p - x[j] : x[j] + p;    \
-        }                                                         \
-    }
-    RS16_LANE(0) RS16_LANE(1) RS16_LANE(2) RS16_LANE(3)
-#undef RS16_LANE
-#pragma unroll
-    for (int lb = 4; lb <= 5; lb++) {
-        if (lb < B0 || lb >= B1) continue;
-#pragma unroll
-        for (int j = 0; j < PTS; j += 2) {
-            auto swp = [&]() {
-                const auto r = lb == 4 ? __builtin_amdgcn_permlane16_swap((uint32_t)x[j], (uint32_t)x[j + 1], false, false)
-                                       : __builtin_amdgcn_permlane32_swap((uint32_t)x[j], (uint32_t)x[j + 1], false, false);
-                x[j] = (int)r[0];
-                x[j + 1] = (int)r[1];
-            };
-            swp();
-            const int u = x[j], v = x[j + 1];
-            x[j] = u + v;
-            x[j + 1] = u - v;
-            swp();
-        }
-    }
-}
 // layout O -> X (TO_X) or X -> O through sx; barrier after the writes
 template <int NT, int PTS, bool TO_X> __device__ __forceinline__ void fwht_xpose(int (&x)[PTS], int* sx) {
     using X = XLay<NT>;
@@ -346,17 +314,19 @@ template <int L, int PTS, int NT_ = (1 << L) / 4, bool XP = false> struct ColEva
         if constexpr (XP) {
             constexpr int WB = XLay<NT>::WB;
             // H(e): every bit but the wave bits in layout O, those in X
-            fwht_lanes<PTS, 0, 6, true>(x);
+            fwht_regs(x);
+            fwht_lanes<PTS, 6>(x);
             fwht_xpose<NT, PTS, true>(x, sx);
-            fwht_lanes<PTS, 0, WB, false>(x);
+            fwht_lanes<PTS, WB>(x);
 #pragma unroll
             for (int j = 0; j < PTS; j++) x[j] = (int)fold65535(mod65535(x[j]) * vt[j]);
             // H(.): every bit but point bits [0, WB) in X, those in O
-            fwht_lanes<PTS, 0, 6, true>(x);
+            fwht_regs(x);
+            fwht_lanes<PTS, 6>(x);
             __syncthreads();  // (every thread has read its X points)
             fwht_xpose<NT, PTS, false>(x, sx);
             __syncthreads();  // (elds overwrites sx)
-            fwht_lanes<PTS, 0, WB, false>(x);
+            fwht_lanes<PTS, WB>(x);
 #pragma unroll
             for (int j = 0; j < PTS; j++) elds[t + NT * j] = mod65535(x[j] + (int)a.e_k);
             return;
@@ -372,28 +342,45 @@ template <int L, int PTS, int NT_ = (1 << L) / 4, bool XP = false> struct ColEva
     }
 };
 
+// Row maps: MP::row(t, m) = the row of thread t's register m, MP::REG = the
+// mask of the row bits that are bits of m.  BMap: the block over row bits (B0, B1) of the
+// radix-4 kernel (brow); RMap (below): the radix-2 kernels'.
+template <int B0, int B1> struct BMap {
+    static __device__ __forceinline__ uint32_t row(uint32_t t, int m) { return brow<B0, B1>(t, m); }
+    static constexpr uint32_t REG = (1u << B0) | (1u << B1);
+};
+// LDS image index of a row: swizzled (radix-4 kernel) or plain (radix-2: map M)
+struct SwzIdx {
+    static __device__ __forceinline__ uint32_t at(uint32_t r) { return swz(r); }
+};
+struct RowIdx {
+    static __device__ __forceinline__ uint32_t at(uint32_t r) { return r; }
+};
+
 // The formal derivative (Engine::formal_derivative, src/engine.rs:233-238) of
 // the whole column, in the closed form out[j] = d[j] ^ XOR{ d[j | 2^b] : bit b
 // of j is 0 }, between the general decoder's IFFT and FFT:
-// register bits from registers, every other bit from an LDS image of d.
-template <int L, int B0, int B1>
-__device__ __forceinline__ void col_fd(uint32_t (&XL)[4], uint32_t (&XH)[4], uint32_t t, uint8_t* smem) {
-    uint2* img = (uint2*)(smem + ColSmem<L>::IMG);
+// register bits from registers, every other bit from an LDS image of d.  (The
+// caller's next barrier frees the image again.)
+template <int L, class MP, class IDX, int R>
+__device__ __forceinline__ void col_fd(uint32_t (&XL)[R], uint32_t (&XH)[R], uint32_t t, uint8_t* img8) {
+    uint2* img = (uint2*)img8;
     __syncthreads();  // (every wave is past its IFFT tables and earlier image reads)
 #pragma unroll
-    for (int m = 0; m < 4; m++) img[swz(brow<B0, B1>(t, m))] = make_uint2(XL[m], XH[m]);
+    for (int m = 0; m < R; m++) img[IDX::at(MP::row(t, m))] = make_uint2(XL[m], XH[m]);
     __syncthreads();
-    uint32_t AL[4], AH[4];
+    uint32_t AL[R], AH[R];
 #pragma unroll
-    for (int m = 0; m < 4; m++) {
-        const uint32_t j = brow<B0, B1>(t, m);
+    for (int m = 0; m < R; m++) {
+        const uint32_t j = MP::row(t, m);
         uint32_t al = XL[m], ah = XH[m];
         if (!(m & 1)) al ^= XL[m | 1], ah ^= XH[m | 1];
-        if (!(m & 2)) al ^= XL[m | 2], ah ^= XH[m | 2];
+        if constexpr (R == 4)
+            if (!(m & 2)) al ^= XL[m | 2], ah ^= XH[m | 2];
 #pragma unroll
         for (int b = 0; b < L; b++) {
-            if (b == B0 || b == B1) continue;
-            const uint2 v = img[swz(j | (1u << b))];
+            if ((MP::REG >> b) & 1u) continue;
+            const uint2 v = img[IDX::at(j | (1u << b))];
             const bool take = !((j >> b) & 1u);
             al ^= take ? v.x : 0u;
             ah ^= take ? v.y : 0u;
@@ -402,7 +389,12 @@ __device__ __forceinline__ void col_fd(uint32_t (&XL)[4], uint32_t (&XH)[4], uin
         AH[m] = ah;
     }
 #pragma unroll
-    for (int m = 0; m < 4; m++) XL[m] = AL[m], XH[m] = AH[m];
+    for (int m = 0; m < R; m++) XL[m] = AL[m], XH[m] = AH[m];
+}
+// (the radix-4 kernel: its next image access has no barrier of its own)
+template <int L, int B0, int B1>
+__device__ __forceinline__ void col_fd4(uint32_t (&XL)[4], uint32_t (&XH)[4], uint32_t t, uint8_t* smem) {
+    col_fd<L, BMap<B0, B1>, SwzIdx>(XL, XH, t, smem + ColSmem<L>::IMG);
     __syncthreads();  // (the image is free again)
 }
 
@@ -416,13 +408,8 @@ __global__ __launch_bounds__((1 << L) / 4) void col_kernel(ColArgs a) {
     const uint32_t t = threadIdx.x;
     RS16_STAMP(a, 0);
 
-    // workgroup -> (stripe, quad column), XCD-aware: consecutive columns on
-    // one XCD (workgroups are dealt to the 8 XCDs round-robin)
-    const uint32_t total = a.qrow * a.nstripes;
-    uint32_t g = blockIdx.x;
-    if ((total & 7u) == 0) g = (g & 7u) * (total >> 3) + (g >> 3);
-    const uint32_t st = g / a.qrow, q = g - st * a.qrow;
-    const uint32_t offL = (q >> 3) * 64u + (q & 7u) * 4u;
+    const ColWg wg = col_wg(a.qrow, a.nstripes);
+    const uint32_t st = wg.st, offL = wg.offL;
     const uint8_t* in = a.in + st * a.bs_in + offL;
     uint8_t* out = a.out + st * a.bs_out + offL;
     // stripes with losses of their own (all strides 0 when shared)
@@ -592,7 +579,7 @@ __global__ __launch_bounds__((1 << L) / 4) void col_kernel(ColArgs a) {
     exchange<8, 9, 8, 10>(XL, XH, t, smem);
     compute<false, false, true>(XL, XH, tb);
     RS16_STAMP(a, 5);
-    col_fd<L, 8, 10>(XL, XH, t, smem);
+    col_fd4<L, 8, 10>(XL, XH, t, smem);
     load_tabs<L, true, 8, 10, false, true>(tb, t, smem);
     compute<true, false, true>(XL, XH, tb);
     load_tabs<L, true, 8, 9, true, true>(ta, t, smem);
@@ -629,7 +616,7 @@ __global__ __launch_bounds__((1 << L) / 4) void col_kernel(ColArgs a) {
     if constexpr (L == 6) {
         // the FFT's first block keeps the row bits (4, 5)
         RS16_STAMP(a, 5);
-        if constexpr (GEN) col_fd<L, 4, 5>(XL, XH, t, smem);
+        if constexpr (GEN) col_fd4<L, 4, 5>(XL, XH, t, smem);
         load_tabs<L, true, 4, 5, true, true>(ta, t, smem);
         RS16_STAMP(a, 6);
     } else if constexpr (L == 7) {
@@ -638,7 +625,7 @@ __global__ __launch_bounds__((1 << L) / 4) void col_kernel(ColArgs a) {
         swap_bit<1, 4>(XH);
         compute<false, false, true>(XL, XH, tb);
         RS16_STAMP(a, 5);
-        if constexpr (GEN) col_fd<L, 4, 6>(XL, XH, t, smem);
+        if constexpr (GEN) col_fd4<L, 4, 6>(XL, XH, t, smem);
         load_tabs<L, true, 4, 6, false, true>(tb, t, smem);
         compute<true, false, true>(XL, XH, tb);
         load_tabs<L, true, 4, 5, true, true>(ta, t, smem);
@@ -651,14 +638,14 @@ __global__ __launch_bounds__((1 << L) / 4) void col_kernel(ColArgs a) {
         compute<false, true, true>(XL, XH, tb);
         if constexpr (L == 8) {
             RS16_STAMP(a, 5);
-            if constexpr (GEN) col_fd<L, 6, 7>(XL, XH, t, smem);
+            if constexpr (GEN) col_fd4<L, 6, 7>(XL, XH, t, smem);
             load_tabs<L, true, 6, 7, true, true>(ta, t, smem);
         } else if constexpr (L == 10) {
             load_tabs<L, false, 8, 9, true, true>(ta, t, smem);
             exchange<6, 7, 8, 9>(XL, XH, t, smem);
             compute<false, true, true>(XL, XH, ta);
             RS16_STAMP(a, 5);
-            if constexpr (GEN) col_fd<L, 8, 9>(XL, XH, t, smem);
+            if constexpr (GEN) col_fd4<L, 8, 9>(XL, XH, t, smem);
             // the FFT's first block keeps the row bits: no exchange
             load_tabs<L, true, 8, 9, true, true>(tb, t, smem);
             compute<true, true, true>(XL, XH, tb);
@@ -670,7 +657,7 @@ __global__ __launch_bounds__((1 << L) / 4) void col_kernel(ColArgs a) {
             exchange<6, 7, 7, 8>(XL, XH, t, smem);
             compute<false, false, true>(XL, XH, ta);
             RS16_STAMP(a, 5);
-            if constexpr (GEN) col_fd<L, 7, 8>(XL, XH, t, smem);
+            if constexpr (GEN) col_fd4<L, 7, 8>(XL, XH, t, smem);
             load_tabs<L, true, 7, 8, false, true>(tb, t, smem);
             compute<true, false, true>(XL, XH, tb);
             load_tabs<L, true, 6, 7, true, true>(ta, t, smem);
@@ -744,6 +731,7 @@ __global__ __launch_bounds__((1 << L) / 4) void col_kernel(ColArgs a) {
 // ---------------------------------------------------------------------------
 template <int RB, int... P> struct RMap {
     static constexpr int BITS = sizeof...(P);
+    static constexpr uint32_t REG = 1u << RB;
     static __device__ __forceinline__ uint32_t row(uint32_t t, uint32_t m) {
         uint32_t r = m << RB;
         int i = 0;
@@ -786,23 +774,9 @@ template <> struct SMap<9, 7> { using M = RMap<7, 0, 1, 2, 3, 8, 4, 5, 6>; };
 template <> struct SMap<10, 7> { using M = RMap<7, 0, 1, 2, 3, 8, 9, 4, 5, 6>; };
 
 // Trade the register bit with lane bit LB (rows m = 0, 1; see swap_bit).
-template <int LB> __device__ __forceinline__ void swap2(uint32_t (&X)[2]) {
-    if constexpr (LB == 4 || LB == 5) {
-        const auto r = LB == 4 ? __builtin_amdgcn_permlane16_swap(X[0], X[1], false, false)
-                               : __builtin_amdgcn_permlane32_swap(X[0], X[1], false, false);
-        X[0] = r[0];
-        X[1] = r[1];
-    } else {
-        const bool hi = (threadIdx.x >> LB) & 1u;
-        const uint32_t u = (uint32_t)xshfl<(1 << LB)>((int)X[0]);
-        const uint32_t v = (uint32_t)xshfl<(1 << LB)>((int)X[1]);
-        X[1] = hi ? X[1] : u;
-        X[0] = hi ? v : X[0];
-    }
-}
 template <int LB> __device__ __forceinline__ void swap2(uint32_t (&XL)[2], uint32_t (&XH)[2]) {
-    swap2<LB>(XL);
-    swap2<LB>(XH);
+    swap_bit<0, LB>(XL);
+    swap_bit<0, LB>(XH);
 }
 template <bool FFT> __device__ __forceinline__ void bfly2(uint32_t (&XL)[2], uint32_t (&XH)[2], const uint32_t (&w)[20]) {
     if (FFT) {
@@ -840,37 +814,6 @@ __device__ __forceinline__ void exchange2(uint32_t (&XL)[2], uint32_t (&XH)[2], 
     }
 }
 
-// The formal derivative (closed form, col_fd) of the radix-2 kernel's rows
-// at the middle, where the register holds row bit RB: that term from the
-// register pair, every other bit's from an LDS image of the column.
-template <class MP, int L, int RB>
-__device__ __forceinline__ void col2_fd(uint32_t (&XL)[2], uint32_t (&XH)[2], uint32_t t, uint8_t* img8) {
-    uint2* img = (uint2*)img8;
-    __syncthreads();  // (every wave is past its earlier image reads)
-#pragma unroll
-    for (int m = 0; m < 2; m++) img[MP::row(t, m)] = make_uint2(XL[m], XH[m]);
-    __syncthreads();
-    uint32_t AL[2], AH[2];
-#pragma unroll
-    for (int m = 0; m < 2; m++) {
-        const uint32_t j = MP::row(t, m);
-        uint32_t al = XL[m], ah = XH[m];
-        if (m == 0) al ^= XL[1], ah ^= XH[1];
-#pragma unroll
-        for (int b = 0; b < L; b++) {
-            if (b == RB) continue;
-            const uint2 v = img[j | (1u << b)];
-            const bool take = !((j >> b) & 1u);
-            al ^= take ? v.x : 0u;
-            ah ^= take ? v.y : 0u;
-        }
-        AL[m] = al;
-        AH[m] = ah;
-    }
-#pragma unroll
-    for (int m = 0; m < 2; m++) XL[m] = AL[m], XH[m] = AH[m];
-}
-
 template <int L, int MODE>
 __global__ __launch_bounds__((1 << L) / 2) void col2_kernel(ColArgs a) {
     // (SEL: the general decode restoring the read set only, a.wanted)
@@ -890,11 +833,8 @@ __global__ __launch_bounds__((1 << L) / 2) void col2_kernel(ColArgs a) {
     const uint32_t t = threadIdx.x;
     RS16_STAMP(a, 0);
 
-    const uint32_t total = a.qrow * a.nstripes;
-    uint32_t g = blockIdx.x;
-    if ((total & 7u) == 0) g = (g & 7u) * (total >> 3) + (g >> 3);
-    const uint32_t st = g / a.qrow, q = g - st * a.qrow;
-    const uint32_t offL = (q >> 3) * 64u + (q & 7u) * 4u;
+    const ColWg wg = col_wg(a.qrow, a.nstripes);
+    const uint32_t st = wg.st, offL = wg.offL;
     const uint8_t* in = a.in + st * a.bs_in + offL;
     uint8_t* out = a.out + st * a.bs_out + offL;
     if (a.flags) a.flags += st * a.bs_flags;
@@ -1124,7 +1064,7 @@ __global__ __launch_bounds__((1 << L) / 2) void col2_kernel(ColArgs a) {
         tab2<L, true, 10, S10>(wb, t, smem);
         swap2<5>(XL, XH);
         bfly2<false>(XL, XH, wa);  // IFFT 10
-        col2_fd<S10, L, 10>(XL, XH, t, img);
+        col_fd<L, S10, RowIdx>(XL, XH, t, img);
         tab2<L, true, 9, S9>(wa, t, smem);
         bfly2<true>(XL, XH, wb);   // FFT 10
         tab2<L, true, 8, S8>(wb, t, smem);
@@ -1159,7 +1099,7 @@ __global__ __launch_bounds__((1 << L) / 2) void col2_kernel(ColArgs a) {
                 store_mid();
                 return;
             }
-            if constexpr (GEN) col2_fd<S9, L, 9>(XL, XH, t, img);
+            if constexpr (GEN) col_fd<L, S9, RowIdx>(XL, XH, t, img);
         } else {
             tab2<L, true, 9, S9>(wa, t, smem);
         }
@@ -1185,7 +1125,7 @@ __global__ __launch_bounds__((1 << L) / 2) void col2_kernel(ColArgs a) {
                 store_mid();
                 return;
             }
-            if constexpr (GEN) col2_fd<S8, L, 8>(XL, XH, t, img);
+            if constexpr (GEN) col_fd<L, S8, RowIdx>(XL, XH, t, img);
         } else {
             tab2<L, true, 8, S8>(wb, t, smem);
         }
@@ -1204,7 +1144,7 @@ __global__ __launch_bounds__((1 << L) / 2) void col2_kernel(ColArgs a) {
                 store_mid();
                 return;
             }
-            if constexpr (GEN) col2_fd<MM, L, 7>(XL, XH, t, img);
+            if constexpr (GEN) col_fd<L, MM, RowIdx>(XL, XH, t, img);
         } else {
             tab2<L, true, 7, MM>(wa, t, smem);
         }
@@ -1320,11 +1260,8 @@ __global__ __launch_bounds__(1024) void colm_kernel(ColArgs a) {
     using S6 = typename SMap<7, 6>::M;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t t = threadIdx.x, lane = t & 63, c = __builtin_amdgcn_readfirstlane(t >> 6);
-    const uint32_t total = a.qrow * a.nstripes;
-    uint32_t g = blockIdx.x;
-    if ((total & 7u) == 0) g = (g & 7u) * (total >> 3) + (g >> 3);
-    const uint32_t st = g / a.qrow, q = g - st * a.qrow;
-    const uint32_t offL = (q >> 3) * 64u + (q & 7u) * 4u;
+    const ColWg wg = col_wg(a.qrow, a.nstripes);
+    const uint32_t st = wg.st, offL = wg.offL;
     const uint8_t* in = a.in + st * a.bs_in + offL;
     uint8_t* out = a.out + st * a.bs_out + offL;
     const uint32_t sk_i = HI ? (c + 1) * CM_N : 0u, sk_f = HI ? 0u : (c + 1) * CM_N;
@@ -1429,26 +1366,83 @@ __global__ __launch_bounds__(1024) void colm_kernel(ColArgs a) {
 
 int col_rows_ok(uint32_t L) { return L >= COL_LMIN && L <= COL_LMAX; }
 
+// Raise fn's dynamic-LDS limit to `bytes`, once per (kernel, device): the
+// limit is a per-device attribute, so it is set for the current device the
+// first time this process launches fn there with that many bytes (engines on
+// several GPUs).  Lock-free and idempotent: a racing second call, or a kernel
+// beyond the table, sets it again.
+static hipError_t ensure_dynamic_lds(const void* fn, int bytes) {
+    constexpr int MAX_DEV = 64, MAX_FN = 8;  // (the 2^11-row kernels and colm_kernel: 6)
+    struct Slot {
+        std::atomic<const void*> fn;
+        std::atomic<int> set[MAX_DEV];
+    };
+    static Slot slots[MAX_FN];
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return e;
+    std::atomic<int>* set = nullptr;
+    for (Slot& sl : slots) {
+        const void* cur = sl.fn.load(std::memory_order_acquire);
+        if (!cur && sl.fn.compare_exchange_strong(cur, fn)) cur = fn;  // (a lost race leaves the winner in cur)
+        if (cur != fn) continue;
+        if (dev >= 0 && dev < MAX_DEV) set = &sl.set[dev];
+        break;
+    }
+    if (set && set->load(std::memory_order_acquire) >= bytes) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess && set) set->store(bytes, std::memory_order_release);
+    return e;
+}
+
 hipError_t launch_col_multi(const ColArgs& a, bool high, hipStream_t s) {
     if (a.nch == 0 || a.nch > COLM_MAX_CHUNKS) return hipErrorInvalidValue;
     if (a.qrow == 0 || a.nstripes == 0 || a.out_rows == 0) return hipSuccess;
     const int bytes = (int)(a.nch * 2 * CM_TAB_BYTES + (high ? a.nch * CM_N * 8 : 0));
     const auto fn = high ? colm_kernel<true> : colm_kernel<false>;
-    // the LDS limit is a per-device attribute: set it for the current device
-    // the first time this process launches there (engines on several GPUs)
-    constexpr int MAX_DEV = 64;
-    static bool attr[MAX_DEV][2] = {};  // (idempotent: a racing second call sets it again)
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev)) return e;
-    if (dev < 0 || dev >= MAX_DEV || !attr[dev][high]) {
-        const int most = (int)(COLM_MAX_CHUNKS * 2 * CM_TAB_BYTES + COLM_MAX_CHUNKS * CM_N * 8);
-        hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, most);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < MAX_DEV) attr[dev][high] = true;
-    }
+    const int most = (int)(COLM_MAX_CHUNKS * 2 * CM_TAB_BYTES + COLM_MAX_CHUNKS * CM_N * 8);
+    if (hipError_t e = ensure_dynamic_lds((const void*)fn, most)) return e;
     hipLaunchKernelGGL(fn, dim3(a.qrow * a.nstripes), dim3(64 * a.nch), bytes, s, a);
     return hipGetLastError();
 }
+
+namespace {
+// The kernel of a launch, its workgroup size and its LDS bytes, from (L, mode,
+// form): radix-2 (col2_kernel, 2 rows per thread) or radix-4 (col_kernel),
+// `chunks` = a multi-chunk encode (no erasure logs in LDS; COL_ENC_IFFT: no
+// FFT tables either).  fn = nullptr: the combination has no kernel.
+typedef void (*ColFn)(ColArgs);
+struct ColForm {
+    ColFn fn = nullptr;
+    uint32_t threads = 0;
+    int lds = 0;
+};
+template <int L, int MODE> constexpr ColForm col_form(bool radix2, bool chunks) {
+    constexpr bool GEN = MODE == COL_DEC_GEN || MODE == COL_DEC_GEN_SEL;
+    constexpr bool LOK = L <= (int)COL_LMAX || GEN;  // (2^11 rows: the general decoder only)
+    if (radix2) {
+        if constexpr (LOK && L >= (int)COL_LCHUNK && MODE != COL_DEC_EWORK)
+            return {col2_kernel<L, MODE>, (1u << L) / 2,
+                    MODE == COL_ENC_IFFT ? ColSmem<L>::B : (chunks ? ColSmem<L>::ELOG : ColSmem<L>::BYTES)};
+    } else {
+        // (the ework decoder needs 4 waves: L >= 9)
+        if constexpr (LOK && MODE != COL_ENC_IFFT && MODE != COL_ENC_FFTX && (MODE != COL_DEC_EWORK || L >= 9))
+            return {col_kernel<L, MODE>, (1u << L) / 4, ColSmem<L>::BYTES};
+    }
+    return {};
+}
+template <int L> ColForm col_form(int mode, bool radix2, bool chunks) {
+    switch (mode) {
+        case COL_ENC: return col_form<L, COL_ENC>(radix2, chunks);
+        case COL_DEC_EWORK: return col_form<L, COL_DEC_EWORK>(radix2, chunks);
+        case COL_DEC_EVAL: return col_form<L, COL_DEC_EVAL>(radix2, chunks);
+        case COL_DEC_GEN: return col_form<L, COL_DEC_GEN>(radix2, chunks);
+        case COL_ENC_IFFT: return col_form<L, COL_ENC_IFFT>(radix2, chunks);
+        case COL_ENC_FFTX: return col_form<L, COL_ENC_FFTX>(radix2, chunks);
+        case COL_DEC_GEN_SEL: return col_form<L, COL_DEC_GEN_SEL>(radix2, chunks);
+    }
+    return {};
+}
+}  // namespace
 
 hipError_t launch_col(const ColArgs& a, uint32_t L, int mode, hipStream_t s) {
     if (L < COL_LMIN || L > COL_LGEN || mode < COL_ENC || mode > COL_DEC_GEN_SEL) return hipErrorInvalidValue;
@@ -1461,53 +1455,24 @@ hipError_t launch_col(const ColArgs& a, uint32_t L, int mode, hipStream_t s) {
                    (mode != COL_ENC && mode < COL_ENC_IFFT)))
         return hipErrorInvalidValue;
     if (a.qrow == 0 || a.nstripes == 0 || a.out_rows == 0) return hipSuccess;
-    typedef void (*ColFn)(ColArgs);
-#define RS16_COL_ROW(L)                                                                                   \
-    {col_kernel<L, COL_ENC>, L >= 9 ? col_kernel<L, COL_DEC_EWORK> : nullptr, col_kernel<L, COL_DEC_EVAL>, \
-     col_kernel<L, COL_DEC_GEN>}
-    static const ColFn fns[6][4] = {RS16_COL_ROW(6),  RS16_COL_ROW(7), RS16_COL_ROW(8), RS16_COL_ROW(9),
-                                    RS16_COL_ROW(10), {nullptr, nullptr, nullptr, col_kernel<11, COL_DEC_GEN>}};
-#undef RS16_COL_ROW
-    static const int lds[6] = {ColSmem<6>::BYTES, ColSmem<7>::BYTES,  ColSmem<8>::BYTES,
-                               ColSmem<9>::BYTES, ColSmem<10>::BYTES, ColSmem<11>::BYTES};
-    // (COL_DEC_GEN_SEL: the same geometry and LDS as COL_DEC_GEN, kernels of its own)
-    static const ColFn fns_sel[6] = {col_kernel<6, COL_DEC_GEN_SEL>, col_kernel<7, COL_DEC_GEN_SEL>,
-                                     col_kernel<8, COL_DEC_GEN_SEL>, col_kernel<9, COL_DEC_GEN_SEL>,
-                                     col_kernel<10, COL_DEC_GEN_SEL>, col_kernel<11, COL_DEC_GEN_SEL>};
-    ColFn fn = sel ? fns_sel[L - COL_LMIN] : (mode <= COL_DEC_GEN ? fns[L - COL_LMIN][mode] : nullptr);
-    if (!fn && !chunks) return hipErrorInvalidValue;  // (the ework decoder needs 4 waves: L >= 9)
-    uint32_t threads = (1u << L) / 4, rows = 1;
-    if (chunks) {
-        static const ColFn fnc[3][3] = {{col2_kernel<8, COL_ENC>, col2_kernel<8, COL_ENC_IFFT>, col2_kernel<8, COL_ENC_FFTX>},
-                                        {col2_kernel<9, COL_ENC>, col2_kernel<9, COL_ENC_IFFT>, col2_kernel<9, COL_ENC_FFTX>},
-                                        {col2_kernel<10, COL_ENC>, col2_kernel<10, COL_ENC_IFFT>, col2_kernel<10, COL_ENC_FFTX>}};
-        fn = fnc[L - COL_LCHUNK][mode == COL_ENC ? 0 : mode - COL_ENC_IFFT + 1];
-        threads = (1u << L) / 2;
-        rows = mode == COL_ENC_FFTX ? 1 : a.nch;  // (one grid row per chunk)
-    } else if (mode != COL_DEC_EWORK && L >= 8 && !(a.diag & DIAG_COL_RADIX4)) {
-        // the encode and the half decode of 2^8 .. 2^10 rows: the radix-2
-        // form (2 rows per thread), unless RS16_DIAG_COL_RADIX4
-        static const ColFn fns2[4][3] = {
-            {col2_kernel<8, COL_ENC>, col2_kernel<8, COL_DEC_EVAL>, col2_kernel<8, COL_DEC_GEN>},
-            {col2_kernel<9, COL_ENC>, col2_kernel<9, COL_DEC_EVAL>, col2_kernel<9, COL_DEC_GEN>},
-            {col2_kernel<10, COL_ENC>, col2_kernel<10, COL_DEC_EVAL>, col2_kernel<10, COL_DEC_GEN>},
-            {nullptr, nullptr, col2_kernel<11, COL_DEC_GEN>}};
-        static const ColFn fns2_sel[4] = {col2_kernel<8, COL_DEC_GEN_SEL>, col2_kernel<9, COL_DEC_GEN_SEL>,
-                                          col2_kernel<10, COL_DEC_GEN_SEL>, col2_kernel<11, COL_DEC_GEN_SEL>};
-        fn = sel ? fns2_sel[L - 8] : fns2[L - 8][mode == COL_ENC ? 0 : (mode == COL_DEC_EVAL ? 1 : 2)];
-        threads = (1u << L) / 2;
+    // the encode and the decodes of 2^8 .. 2^11 rows: the radix-2 form,
+    // unless RS16_DIAG_COL_RADIX4 (a multi-chunk encode has no other)
+    const bool radix2 = chunks || (mode != COL_DEC_EWORK && L >= COL_LCHUNK && !(a.diag & DIAG_COL_RADIX4));
+    ColForm f;
+    switch (L) {
+        case 6: f = col_form<6>(mode, radix2, chunks); break;
+        case 7: f = col_form<7>(mode, radix2, chunks); break;
+        case 8: f = col_form<8>(mode, radix2, chunks); break;
+        case 9: f = col_form<9>(mode, radix2, chunks); break;
+        case 10: f = col_form<10>(mode, radix2, chunks); break;
+        case 11: f = col_form<11>(mode, radix2, chunks); break;
     }
-    int bytes = lds[L - COL_LMIN];
-    if (chunks) {
-        static const int enc[3] = {ColSmem<8>::ELOG, ColSmem<9>::ELOG, ColSmem<10>::ELOG};
-        static const int ifo[3] = {ColSmem<8>::B, ColSmem<9>::B, ColSmem<10>::B};
-        bytes = (mode == COL_ENC_IFFT ? ifo : enc)[L - COL_LCHUNK];
-    }
-    if (bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(fn, dim3(a.qrow * a.nstripes, rows), dim3(threads), bytes, s, a);
+    if (!f.fn) return hipErrorInvalidValue;
+    if (f.lds > 65536)
+        if (hipError_t e = ensure_dynamic_lds((const void*)f.fn, f.lds)) return e;
+    // (one grid row per chunk; the FFT of the chunks' XOR is one)
+    const uint32_t rows = chunks && mode != COL_ENC_FFTX ? a.nch : 1;
+    hipLaunchKernelGGL(f.fn, dim3(a.qrow * a.nstripes, rows), dim3(f.threads), f.lds, s, a);
     return hipGetLastError();
 }
 

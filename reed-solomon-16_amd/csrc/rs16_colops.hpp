@@ -29,8 +29,9 @@ template <int B0, int B1> __device__ __forceinline__ uint32_t brow(uint32_t t, i
     return lo | (mid << (B0 + 1)) | (hi << (B1 + 1)) | ((uint32_t)(m & 1) << B0) | ((uint32_t)(m >> 1) << B1);
 }
 
-__device__ __forceinline__ void lds_table(uint32_t (&t)[20], const uint8_t* smem, uint32_t off) {
-    const u32x4* p = (const u32x4*)(smem + off);
+// An 80-byte v_perm table (rs16_gf.hpp) at p, LDS or global: five 16-byte loads.
+__device__ __forceinline__ void load_table(uint32_t (&t)[20], const void* p8) {
+    const u32x4* p = (const u32x4*)p8;
 #pragma unroll
     for (int i = 0; i < 5; i++) {
         const u32x4 v = p[i];
@@ -40,16 +41,15 @@ __device__ __forceinline__ void lds_table(uint32_t (&t)[20], const uint8_t* smem
         t[4 * i + 3] = v.w;
     }
 }
+__device__ __forceinline__ void lds_table(uint32_t (&t)[20], const uint8_t* smem, uint32_t off) {
+    load_table(t, smem + off);
+}
 __device__ __forceinline__ void glb_table(uint32_t (&t)[20], const uint32_t* tabs, uint32_t entry) {
-    const u32x4* p = (const u32x4*)(tabs + (size_t)entry * TAB_DWORDS);
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        const u32x4 v = p[i];
-        t[4 * i] = v.x;
-        t[4 * i + 1] = v.y;
-        t[4 * i + 2] = v.z;
-        t[4 * i + 3] = v.w;
-    }
+    load_table(t, tabs + (size_t)entry * TAB_DWORDS);
+}
+// (a table image: table g at g x 80 bytes)
+__device__ __forceinline__ void img_table(uint32_t (&t)[20], const uint8_t* img, uint32_t g) {
+    load_table(t, img + (size_t)g * 80);
 }
 
 // LDS-DMA copy of `bytes` (a multiple of 16) from src to the LDS at dst by
@@ -77,22 +77,27 @@ __device__ __forceinline__ void dma_copy_rt(const uint8_t* src, uint8_t* dst, ui
     for (uint32_t i = 0; i * NT * 16 < bytes; i++) dma_copy_step<NT>(src, dst, bytes, i);
 }
 
+// Trade a with the partner's b across lane bit LB = 4 (v_permlane16_swap:
+// odd 16-lane rows of the first operand <-> even rows of the second) or 5
+// (v_permlane32_swap: upper 32 lanes <-> lower 32): no LDS.
+template <int LB, class T> __device__ __forceinline__ void permlane_swap(T& a, T& b) {
+    static_assert(LB == 4 || LB == 5, "lane bits 0-3 trade by DPP (xshfl)");
+    const auto r = LB == 4 ? __builtin_amdgcn_permlane16_swap((uint32_t)a, (uint32_t)b, false, false)
+                           : __builtin_amdgcn_permlane32_swap((uint32_t)a, (uint32_t)b, false, false);
+    a = (T)r[0];
+    b = (T)r[1];
+}
 // Trade register bit RB (register pairs m, m | 2^RB) with lane bit LB of
 // the wave: afterwards register bit RB holds the row bit lane bit LB held,
 // and the other way round (lane with LB = 0 takes the partner's m into its
 // m | 2^RB, lane with LB = 1 the partner's m | 2^RB into its m).
-template <int RB, int LB> __device__ __forceinline__ void swap_bit(uint32_t (&X)[4]) {
+template <int RB, int LB, int R> __device__ __forceinline__ void swap_bit(uint32_t (&X)[R]) {
 #pragma unroll
-    for (int m = 0; m < 4; m++) {
+    for (int m = 0; m < R; m++) {
         if (m & (1 << RB)) continue;
         const int m1 = m | (1 << RB);
         if constexpr (LB == 4 || LB == 5) {
-            // v_permlane16_swap: odd 16-lane rows of the first operand <-> even
-            // rows of the second; v_permlane32_swap: upper 32 lanes <-> lower 32
-            const auto r = LB == 4 ? __builtin_amdgcn_permlane16_swap(X[m], X[m1], false, false)
-                                   : __builtin_amdgcn_permlane32_swap(X[m], X[m1], false, false);
-            X[m] = r[0];
-            X[m1] = r[1];
+            permlane_swap<LB>(X[m], X[m1]);
         } else {
             const bool hi = (threadIdx.x >> LB) & 1u;
             const uint32_t u = (uint32_t)xshfl<(1 << LB)>((int)X[m]);   // partner's m
@@ -111,18 +116,6 @@ template <int LB0, int LB1> __device__ __forceinline__ void wave_exchange(uint32
     swap_bit<1, LB1>(XH);
 }
 
-// The (0, 1) block's tables, from the image (table g at g x 80 bytes).
-__device__ __forceinline__ void img_table(uint32_t (&t)[20], const uint8_t* img, uint32_t g) {
-    const u32x4* p = (const u32x4*)(img + (size_t)g * 80);
-#pragma unroll
-    for (int i = 0; i < 5; i++) {
-        const u32x4 v = p[i];
-        t[4 * i] = v.x;
-        t[4 * i + 1] = v.y;
-        t[4 * i + 2] = v.z;
-        t[4 * i + 3] = v.w;
-    }
-}
 // The twiddle tables of one block: the layers on row bits B0 (if D0) and B1
 // (if D1) of the thread's 4 rows (register m <-> bit B0 = m & 1, bit B1 =
 // m >> 1).  Read from LDS one block ahead of their use.

@@ -16,7 +16,9 @@ three texts are hashed and compared:
 
 Only the function index of local labels is normalised (.LBB<n>_ -> .LBB_) and
 comments are stripped.  The script hashes text; it inspects no instruction.
-Prints the counts and every differing symbol; exit status 1 on any difference.
+Prints the counts and every differing symbol -- for a kernel whose desc
+differs, also the descriptor lines that differ, "- " the first build's and
+"+ " the second's; exit status 1 on any difference.
 """
 import hashlib
 import re
@@ -36,7 +38,7 @@ def digest(lines):
 
 
 def kernels_of(path):
-    """{symbol: {"code": h, "desc": h, "meta": h}} of one .s file."""
+    """{symbol: {"code": h, "desc": h, "meta": h, "desc_lines": [...]}} of one .s file."""
     lines = path.read_text().splitlines()
     out = {}
     # descriptor blocks name the kernels; the code of `sym` starts at "sym:"
@@ -58,7 +60,8 @@ def kernels_of(path):
             while not re.match(r"\.Lfunc_end\d+:", lines[end]):
                 end += 1
             code = [clean(l) for l in lines[start:i] + lines[j + 1:end]]
-            out[sym] = {"code": digest([l for l in code if l.strip()]), "desc": digest(desc)}
+            out[sym] = {"code": digest([l for l in code if l.strip()]), "desc": digest(desc),
+                        "desc_lines": desc}
             i = j
         i += 1
     # metadata note: a YAML list under amdhsa.kernels, one "  - " item per kernel
@@ -111,6 +114,14 @@ def main():
         diff = [k for k in ("code", "desc", "meta") if a[sym].get(k) != b[sym].get(k)]
         if diff:
             print(f"differs ({', '.join(diff)}): {sym} ({a[sym]['file']} / {b[sym]['file']})")
+            if "desc" in diff:
+                da, db = a[sym]["desc_lines"], b[sym]["desc_lines"]
+                for l in da:
+                    if l not in db:
+                        print(f"    - {l}")
+                for l in db:
+                    if l not in da:
+                        print(f"    + {l}")
             bad += 1
         else:
             same += 1
