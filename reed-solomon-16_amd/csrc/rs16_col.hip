@@ -156,13 +156,9 @@ __device__ __forceinline__ void exchange(uint32_t (&XL)[4], uint32_t (&XH)[4], u
 // H_n(H_n(e) . V) with the constant V = n^-1 H_n(W[0, n)) (HostTables::col_v):
 // two n-point transforms per workgroup instead of a separate kernel.  Exact
 // integers (|H_n(e)| <= n, |H_n(Y)| <= n 65535), reduced mod 65535 (65535 and
-// 0 are the same log to every consumer, exp[65535] == exp[0]).
+// 0 are the same log to every consumer, exp[65535] == exp[0]; fold65535 /
+// mod65535, rs16_fwht.hpp).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t fold65535(uint32_t u) {
-    u = (u & 0xFFFFu) + (u >> 16);
-    return (u & 0xFFFFu) + (u >> 16);
-}
-__device__ __forceinline__ uint32_t mod65535(int v) { return fold65535((uint32_t)(v + 65535 * 4096)); }
 
 // The integer FWHT's layers inside a thread and inside a wave.  Register
 // layers: the bits of j of x[j].

@@ -569,14 +569,12 @@ int rs16_engine::decode_eval(const DecodeGeom& g, const uint8_t* flags_a, const 
     // 256-point FWHT themselves, for the 256-row block of their tile's rows
     // (one kernel less) -- except the one-pass half-transform decode, whose
     // gather and reveal rows lie in different blocks.
-    const bool small = g.high && g.n <= 2048 && !(diag & DIAG_EVAL_FULL);
     // (the column codec's half decodes of 2^9 / 2^10 rows finish it too)
     p.elog_fused = !(half_decode(g) && ilog2(g.n) - 1 <= 8);
     uint32_t *work = (uint32_t*)ev.work32.p, *elog = (uint32_t*)ev.elog.p;
     return profiled(PROF_EVAL_POLY, s, err, [&](uint64_t* stamps) {
         es.stamps = stamps;
-        // erasures are zero from row n on: only n/256 live blocks (rs16_misc.hip)
-        if (small) return launch_eval_poly_small(es, (uint32_t)g.n, work, elog, d_log_walsh, s, !p.elog_fused);
+        // (the form -- small, fused, two-kernel -- is the launcher's choice, rs16_eval.hip)
         return launch_eval_poly_from_flags(es, work, elog, d_log_walsh, s, !p.elog_fused);
     });
 }

@@ -1,7 +1,7 @@
-// rs16_misc.hip -- elementwise engine ops (mul, xor, formal derivative) and the
-// FWHT / eval_poly kernels of the MI355X GF(2^16) Reed-Solomon engine.
-#include <algorithm>
-
+// rs16_eval.hip -- the erasure-locator evaluation of the MI355X GF(2^16)
+// Reed-Solomon engine: the received flags of a decode to its erasure logs
+// (eval_poly) and its pass metadata, in three forms chosen by one launcher,
+// and the exact engine-level fwht / eval_poly.
 #include <cstdlib>
 
 #include "rs16_internal.hpp"
@@ -10,108 +10,7 @@
 
 namespace rs16 {
 
-typedef const __attribute__((address_space(4))) uint32_t* cu32p;
 typedef const __attribute__((address_space(4))) uint8_t* cu8p;
-
-// ---------------------------------------------------------------------------
-// Elementwise engine ops.
-// ---------------------------------------------------------------------------
-// Engine::mul: x[] *= log_m (NoSimd::mul, src/engine/engine_nosimd.rs:65-79).
-__global__ void __launch_bounds__(256) mul_kernel(uint8_t* x, size_t nquads, uint32_t entry, const uint32_t* mul_tab) {
-    cu32p t = (cu32p)mul_tab + (size_t)entry * TAB_DWORDS;
-    uint32_t tt[20];
-#pragma unroll
-    for (int i = 0; i < 20; i++) tt[i] = t[i];
-    for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < nquads; q += (size_t)gridDim.x * blockDim.x) {
-        const size_t off = (q >> 3) * 64 + (q & 7) * 4;
-        uint32_t yl = *(uint32_t*)(x + off), yh = *(uint32_t*)(x + off + 32);
-        uint32_t ol = 0, oh = 0;
-        mul_xor(ol, oh, yl, yh, tt);
-        *(uint32_t*)(x + off) = ol;
-        *(uint32_t*)(x + off + 32) = oh;
-    }
-}
-hipError_t launch_mul(uint8_t* x, size_t bytes, uint32_t entry, const uint32_t* mul_tab, hipStream_t s) {
-    const size_t nq = bytes / 8;
-    if (!nq) return hipSuccess;
-    const unsigned grid = (unsigned)std::min<size_t>((nq + 255) / 256, 4096);
-    hipLaunchKernelGGL(mul_kernel, dim3(grid), dim3(256), 0, s, x, nq, entry, mul_tab);
-    return hipGetLastError();
-}
-
-// Engine::xor: x[] ^= y[] (src/engine/engine_nosimd.rs:81-88), 16 B per lane.
-__global__ void __launch_bounds__(256) xor_kernel(uint4* x, const uint4* y, size_t n16) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) {
-        uint4 a = x[i], b = y[i];
-        x[i] = make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);
-    }
-}
-hipError_t launch_xor(uint8_t* x, const uint8_t* y, size_t bytes, hipStream_t s) {
-    const size_t n16 = bytes / 16;
-    if (!n16) return hipSuccess;
-    const unsigned grid = (unsigned)std::min<size_t>((n16 + 255) / 256, 8192);
-    hipLaunchKernelGGL(xor_kernel, dim3(grid), dim3(256), 0, s, (uint4*)x, (const uint4*)y, n16);
-    return hipGetLastError();
-}
-
-// Multi-chunk encodes: w[0, cb) ^= XOR of the nch - 1 chunks behind it
-// (HighRateEncoder's xor_within accumulation, src/rate/rate_high.rs:56-74),
-// and chunk 0 copied into chunks 1 .. nch - 1 (LowRateEncoder's per-chunk
-// copy of the transformed originals, src/rate/rate_low.rs:56-74); 16 B per lane.
-__global__ void __launch_bounds__(256) xor_chunks_kernel(uint4* w, size_t c16, uint32_t nch) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < c16; i += (size_t)gridDim.x * blockDim.x) {
-        uint4 a = w[i];
-        for (uint32_t c = 1; c < nch; c++) {
-            const uint4 b = w[c * c16 + i];
-            a.x ^= b.x; a.y ^= b.y; a.z ^= b.z; a.w ^= b.w;
-        }
-        w[i] = a;
-    }
-}
-__global__ void __launch_bounds__(256) copy_chunks_kernel(uint4* w, size_t c16, uint32_t nch) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < c16; i += (size_t)gridDim.x * blockDim.x) {
-        const uint4 a = w[i];
-        for (uint32_t c = 1; c < nch; c++) w[c * c16 + i] = a;
-    }
-}
-hipError_t launch_xor_chunks(uint8_t* w, size_t chunk_bytes, uint32_t nch, hipStream_t s) {
-    const size_t c16 = chunk_bytes / 16;
-    if (!c16 || nch < 2) return hipSuccess;
-    const unsigned grid = (unsigned)std::min<size_t>((c16 + 255) / 256, 8192);
-    hipLaunchKernelGGL(xor_chunks_kernel, dim3(grid), dim3(256), 0, s, (uint4*)w, c16, nch);
-    return hipGetLastError();
-}
-hipError_t launch_copy_chunks(uint8_t* w, size_t chunk_bytes, uint32_t nch, hipStream_t s) {
-    const size_t c16 = chunk_bytes / 16;
-    if (!c16 || nch < 2) return hipSuccess;
-    const unsigned grid = (unsigned)std::min<size_t>((c16 + 255) / 256, 8192);
-    hipLaunchKernelGGL(copy_chunks_kernel, dim3(grid), dim3(256), 0, s, (uint4*)w, c16, nch);
-    return hipGetLastError();
-}
-
-// Engine::formal_derivative (src/engine.rs:233-238), closed form, out of place:
-// out[j] = in[j] ^ XOR_{b : j_b = 0, 2^b < n} in[j | 2^b]   (n a power of two).
-__global__ void __launch_bounds__(256) fd_kernel(uint4* out, const uint4* in, uint32_t n, size_t row16) {
-    const size_t total = (size_t)n * row16;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t j = (uint32_t)(i / row16);
-        const size_t col = i - (size_t)j * row16;
-        uint4 acc = in[i];
-        for (uint32_t b = 1; b < n; b <<= 1)
-            if (!(j & b)) {
-                uint4 v = in[(size_t)(j | b) * row16 + col];
-                acc.x ^= v.x; acc.y ^= v.y; acc.z ^= v.z; acc.w ^= v.w;
-            }
-        out[i] = acc;
-    }
-}
-hipError_t launch_formal_derivative(uint8_t* out, const uint8_t* in, size_t n, size_t S, hipStream_t s) {
-    const size_t row16 = S / 16, total = n * row16;
-    if (!total) return hipSuccess;
-    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 8192);
-    hipLaunchKernelGGL(fd_kernel, dim3(grid), dim3(256), 0, s, (uint4*)out, (const uint4*)in, (uint32_t)n, row16);
-    return hipGetLastError();
-}
 
 // ---------------------------------------------------------------------------
 // FWHT over Z/65535 (reference Engine::fwht, NoSimd::fwht_private
@@ -137,6 +36,23 @@ __device__ __forceinline__ void fwht256_lds(uint32_t* s) {
     __syncthreads();
 }
 
+// Contiguous 256-point FWHT of u16 or u32 words into u32 words.
+// (grid row y: in / out displaced by y bs_in / bs_out words -- the stripes of
+// a batch with losses of their own)
+template <typename IN>
+__global__ void __launch_bounds__(256) fwht_lo_kernel(const IN* in, uint32_t* out, uint32_t bs_in, uint32_t bs_out) {
+    __shared__ uint32_t s[256];
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    in += blockIdx.y * bs_in;
+    out += blockIdx.y * bs_out;
+    s[threadIdx.x] = in[idx];
+    fwht256_lds(s);
+    out[idx] = s[threadIdx.x];
+}
+
+// ---------------------------------------------------------------------------
+// ErasureSpec: the erasure vector and what the kernels below write beside it.
+// ---------------------------------------------------------------------------
 // Stripe y = blockIdx.y of a batch with losses of its own (ErasureSpec::nstripes):
 // its flags and its outputs.
 __device__ __forceinline__ void stripe_spec(ErasureSpec& e) {
@@ -173,6 +89,33 @@ __device__ __forceinline__ bool orig_row(const ErasureSpec& e, uint32_t i) {
 __device__ __forceinline__ bool wanted_row(const ErasureSpec& e, uint32_t i) {
     return !e.wanted || ((cu8p)e.wanted)[i - (e.orig_b ? e.chunk : 0u)] != 0;
 }
+
+// ---- the lost originals' row range [lo, hi), {~0u, 0} if none ----
+// The wave's range from its lanes'.
+// (Macros, and below the lane tests in the callers: as functions taking lo and
+// hi by reference, or with the tests inside, the same text compiles
+// eval_fused_kernel to other code.)
+#define RS16_RANGE_WAVE(lo, hi)                                  \
+    _Pragma("unroll") for (int d = 1; d < 64; d <<= 1) {         \
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, d));          \
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, d));          \
+    }
+// [lo, hi) extended by the rows of the set 0x80 bytes of m, the mask of rows
+// r .. r + 3 (rows ascending from call to call: hi is the last one's).
+#define RS16_RANGE_BYTES(lo, hi, m, r)                               \
+    if (m) {                                                         \
+        lo = min(lo, (r) + (uint32_t)(__builtin_ctz(m) >> 3));       \
+        hi = (r) + (uint32_t)((31 - __builtin_clz(m)) >> 3) + 1u;    \
+    }
+// A 256-thread workgroup's range to e.lostrange: one lane of wave wv puts the
+// wave's range into lr (LDS), and after a barrier one thread stores the four's.
+__device__ __forceinline__ void lost_range_put(uint32_t (&lr)[2][4], uint32_t wv, uint32_t lo, uint32_t hi) {
+    lr[0][wv] = lo, lr[1][wv] = hi;
+}
+__device__ __forceinline__ void lost_range_store(const ErasureSpec& e, const uint32_t (&lr)[2][4]) {
+    e.lostrange[0] = min(min(lr[0][0], lr[0][1]), min(lr[0][2], lr[0][3]));
+    e.lostrange[1] = max(max(lr[1][0], lr[1][1]), max(lr[1][2], lr[1][3]));
+}
 // First / one past the last lost-original row of block blk (rows base +
 // 64 j + bit of lmask[j]), ~0u / 0 if none, by lane 0 of the wave.
 __device__ __forceinline__ void lost_part_wave(const ErasureSpec& e, uint32_t blk, uint32_t base,
@@ -194,16 +137,14 @@ __device__ __forceinline__ void lost_range_wave(const ErasureSpec& e) {
     const uint32_t lane = threadIdx.x & 63;
     const uint4 p0 = ((const uint4*)e.lostpart)[2 * lane], p1 = ((const uint4*)e.lostpart)[2 * lane + 1];
     uint32_t lo = min(min(p0.x, p0.z), min(p1.x, p1.z)), hi = max(max(p0.y, p0.w), max(p1.y, p1.w));
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        lo = min(lo, (uint32_t)__shfl_xor((int)lo, d));
-        hi = max(hi, (uint32_t)__shfl_xor((int)hi, d));
-    }
+    RS16_RANGE_WAVE(lo, hi)
     if (lane == 0) {
         e.lostrange[0] = lo;
         e.lostrange[1] = hi;
     }
 }
+
+// ---- the pass metadata of a 256-row block at row base ----
 // Received rows of the 64-row chunk at row r0 by segment (A = rows < a_count),
 // from the chunk's ballot: lane 0 writes rcount (ErasureSpec).
 __device__ __forceinline__ void chunk_counts(const ErasureSpec& e, uint32_t r0, uint64_t rcv, uint64_t rcv_a) {
@@ -213,9 +154,20 @@ __device__ __forceinline__ void chunk_counts(const ErasureSpec& e, uint32_t r0, 
         e.rcount[2 * (r0 >> 6) + 1] = (uint32_t)__popcll(rcv) - ca;
     }
 }
+// Tile t of the block (rows [t ts, (t + 1) ts) of it, ts = 2^zlo, t < 256 / ts)
+// holds no received row, from the block's received bitmap in words of W:
+// word(i) = rows 8 sizeof(W) i .. of the block.
+template <typename W, typename F> __device__ __forceinline__ bool ztile_empty(F word, uint32_t t, uint32_t ts) {
+    constexpr uint32_t B = 8 * sizeof(W);
+    bool any = false;
+    for (uint32_t r = t * ts; r < (t + 1) * ts; r += B) {
+        const W m = ts >= B ? ~(W)0 : (((W)1 << ts) - 1) << (r & (B - 1));
+        any |= (word(r / B) & m) != 0;
+    }
+    return !any;
+}
 // Received-row bitmap and zero-tile flags of rows [base, base + 256) by one
-// wave, from the ballots rmask[j] of rows base + 64 j + lane: rbits words,
-// zflags per tile of 2^zlo rows.
+// wave, from the ballots rmask[j] of rows base + 64 j + lane.
 __device__ __forceinline__ void block_flags_wave(const ErasureSpec& e, uint32_t base, const uint64_t (&rmask)[4]) {
     const uint32_t lane = threadIdx.x & 63;
     if (base >= e.n) return;
@@ -223,58 +175,21 @@ __device__ __forceinline__ void block_flags_wave(const ErasureSpec& e, uint32_t 
         e.rbits[(base >> 5) + lane] = (uint32_t)(rmask[lane >> 1] >> (32 * (lane & 1)));
     if (e.zflags) {
         const uint32_t ts = 1u << e.zlo, ntile = e.n >> e.zlo;
-        // tile t of this block: rows [t ts, (t + 1) ts), t < 256 / ts
         for (uint32_t t = lane; t < 256u / ts; t += 64) {
-            bool any = false;
-            for (uint32_t r = t * ts; r < (t + 1) * ts; r += 64) {
-                const uint32_t w = r >> 6, sh = r & 63, len = ts < 64 ? ts : 64;
-                const uint64_t m = len == 64 ? ~0ull : ((1ull << len) - 1) << sh;
-                any |= (rmask[w] & m) != 0;
-            }
-            if ((base >> e.zlo) + t < ntile) e.zflags[(base >> e.zlo) + t] = any ? 0 : 1;
+            const bool empty = ztile_empty<uint64_t>([&](uint32_t w) { return rmask[w]; }, t, ts);
+            if ((base >> e.zlo) + t < ntile) e.zflags[(base >> e.zlo) + t] = empty ? 1 : 0;
         }
     }
 }
 
-// MODE 0: in = u32 work; MODE 1: build erasures from flags; MODE 2: in = u16 data.
-// OUT 0: u32 work/out; OUT 1: u16 data.
-template <int MODE, int OUT>
-__global__ void __launch_bounds__(256) fwht_hi_kernel(ErasureSpec e, const uint32_t* in32, const uint16_t* in16,
-                                                       uint32_t* out32, uint16_t* out16) {
-    __shared__ uint32_t s[256];
-    const uint32_t idx = blockIdx.x + 256u * threadIdx.x;  // bits 8-15 vary within the block
-    uint32_t v;
-    if (MODE == 0) v = in32[idx];
-    else if (MODE == 1) v = erasure_at(e, idx);
-    else v = in16[idx];
-    s[threadIdx.x] = v;
-    fwht256_lds(s);
-    if (OUT == 0) out32[idx] = s[threadIdx.x];
-    else out16[idx] = (uint16_t)s[threadIdx.x];
-}
-
-// Contiguous 256-point FWHT; if MULW, then multiply by log_walsh mod 65535 and
-// do the contiguous FWHT again (the middle of eval_poly).
-// (grid row y: in32 / out32 displaced by y bs_in / bs_out words -- the
-// stripes of a batch with losses of their own)
-template <bool MULW, int IN16, int OUT16>
-__global__ void __launch_bounds__(256) fwht_lo_kernel(const uint32_t* in32, const uint16_t* in16, uint32_t* out32,
-                                                       uint16_t* out16, const uint16_t* log_walsh, uint32_t bs_in = 0,
-                                                       uint32_t bs_out = 0) {
-    __shared__ uint32_t s[256];
-    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
-    if (in32) in32 += blockIdx.y * bs_in;
-    if (out32) out32 += blockIdx.y * bs_out;
-    s[threadIdx.x] = IN16 ? in16[idx] : in32[idx];
-    fwht256_lds(s);
-    if (MULW) {
-        s[threadIdx.x] = (uint32_t)(((uint64_t)s[threadIdx.x] * log_walsh[idx]) % GF_MODULUS);
-        fwht256_lds(s);
-    }
-    if (OUT16) out16[idx] = (uint16_t)s[threadIdx.x];
-    else out32[idx] = s[threadIdx.x];
-}
-
+// ---------------------------------------------------------------------------
+// eval_poly(e) = FWHT(LogWalsh . FWHT(e)) with FWHT = H_lo H_hi (row bits 0-7
+// and 8-15; the two commute): H_lo(e) from the flags, then H_hi . LW . H_hi,
+// then the last H_lo.  With last_lo == false the last H_lo is left to the
+// consumer: the 65536-row decode passes (256-row tiles = one H_lo block each)
+// finish it per tile in LDS (rs16_pass.hpp), saving a kernel.
+// ---------------------------------------------------------------------------
+// The two-kernel form, for any segment boundaries and flag addresses.
 // Contiguous 256-point FWHT of the erasure vector built from the received
 // flags, one wave per 256-row block; the same wave writes the block's
 // received bitmap (ballots) and zero-tile flags.
@@ -314,26 +229,16 @@ __global__ void __launch_bounds__(64) fwht_hi_mulw_kernel(ErasureSpec e, const u
 #pragma unroll
     for (int j = 0; j < 4; j++) v[j] = in32[blockIdx.x + 256u * (lane + 64u * j)];
     fwht256_wave(v);
+    // v, lw <= 65535: the product fits 32 bits
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-        // v, lw <= 65535: the product fits 32 bits; two folds reduce it mod
-        // 65535 (65535 may stand for 0: same residue)
-        uint32_t p = v[j] * lw[j];
-        p = (p & 0xFFFFu) + (p >> 16);
-        v[j] = (p & 0xFFFFu) + (p >> 16);
-    }
+    for (int j = 0; j < 4; j++) v[j] = fold65535(v[j] * lw[j]);
     fwht256_wave(v);
 #pragma unroll
     for (int j = 0; j < 4; j++) out32[blockIdx.x + 256u * (lane + 64u * j)] = v[j];
     if (blockIdx.x == 0 && e.lostrange) lost_range_wave(e);
 }
 
-// eval_poly(e) = FWHT(LogWalsh . FWHT(e)) with FWHT = H_lo H_hi (row bits 0-7
-// and 8-15; the two commute): H_lo(e) from the flags, then H_hi . LW . H_hi,
-// then the last H_lo.  With last_lo == false the last H_lo is left to the
-// consumer: the 65536-row decode passes (256-row tiles = one H_lo block each)
-// finish it per tile in LDS (rs16_pass.hpp), saving a kernel.
-// One-kernel eval_poly for block-aligned segments (eval_fused_ok): workgroup
+// The one-kernel form for block-aligned segments (eval_fused_ok): workgroup
 // j computes column j of H_lo(e) for all 256 blocks itself -- thread t reads
 // block t's 256 flag bytes (16 x 16-byte loads, L2-resident after the first
 // workgroup of an XCD) and, e being 0/1, x[t] = sum_r (-1)^|j&r| e[256t + r];
@@ -431,6 +336,17 @@ __global__ void __launch_bounds__(256) eval_fused_kernel(ErasureSpec e, uint32_t
         }
         if (j == 0 && e.lostrange) {  // (uniform: workgroup 0 of a general decode)
             const bool want = e.lost_all || (e.orig_b ? reg == 2 : reg == 0);  // (fl: reg is 0 or 2)
+            // [lo, hi) over the block's rows: MASK = the lost rows among rows
+            // 4 q .. 4 q + 3, whose flag bytes are the dword f
+#define RS16_SCAN(MASK)                                                         \
+    _Pragma("unroll") for (int i = 0; i < 16; i++) {                            \
+        const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};                 \
+        _Pragma("unroll") for (int c = 0; c < 4; c++) {                         \
+            const int q = 4 * i + c;                                            \
+            const uint32_t f = w[c], m = (MASK), r = base + 4u * q;             \
+            RS16_RANGE_BYTES(lo, hi, m, r)                                      \
+        }                                                                       \
+    }
             if (e.wanted) {
                 // A selective decode: the lost rows that are wanted.  The
                 // block's 256 bytes of the read set (the block lies whole in the
@@ -440,47 +356,19 @@ __global__ void __launch_bounds__(256) eval_fused_kernel(ErasureSpec e, uint32_t
                 uint32_t wd[65];
                 uint32_t sh = 0;
                 if (want) sh = wanted_block(wd, e.wanted + (base - (e.orig_b ? e.chunk : 0u)));
-#pragma unroll
-                for (int i = 0; i < 16; i++) {
-                    const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
-#pragma unroll
-                    for (int c = 0; c < 4; c++) {
-                        const int q = 4 * i + c;
-                        const uint32_t wq = want ? __builtin_amdgcn_alignbyte(wd[q + 1], wd[q], sh) : 0u;
-                        const uint32_t m = ~nz80(w[c]) & nz80(wq);  // erased and wanted bytes
-                        const uint32_t r = base + 4u * q;
-                        if (m) {
-                            lo = min(lo, r + (uint32_t)(__builtin_ctz(m) >> 3));
-                            hi = r + (uint32_t)((31 - __builtin_clz(m)) >> 3) + 1u;
-                        }
-                    }
-                }
+                // erased and wanted bytes
+                RS16_SCAN(~nz80(f) & nz80(want ? __builtin_amdgcn_alignbyte(wd[q + 1], wd[q], sh) : 0u))
             } else {
-#pragma unroll
-                for (int i = 0; i < 16; i++) {
-                    const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
-#pragma unroll
-                    for (int c = 0; c < 4; c++) {
-                        const uint32_t m = want ? ~nz80(w[c]) & 0x80808080u : 0u;  // erased bytes
-                        const uint32_t r = base + 4u * (4 * i + c);
-                        if (m) {
-                            lo = min(lo, r + (uint32_t)(__builtin_ctz(m) >> 3));
-                            hi = r + (uint32_t)((31 - __builtin_clz(m)) >> 3) + 1u;
-                        }
-                    }
-                }
+                RS16_SCAN(want ? ~nz80(f) & 0x80808080u : 0u)  // erased bytes
             }
+#undef RS16_SCAN
         }
     }
     RS16_STAMP(e, 1);
     xs[t] = (j == 0 ? 256 * all : 0) + (acc >> 7);
     if (j == 0 && e.lostrange) {
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            lo = min(lo, (uint32_t)__shfl_xor((int)lo, d));
-            hi = max(hi, (uint32_t)__shfl_xor((int)hi, d));
-        }
-        if (lane == 0) lr[0][wv] = lo, lr[1][wv] = hi;
+        RS16_RANGE_WAVE(lo, hi)
+        if (lane == 0) lost_range_put(lr, wv, lo, hi);
     }
     // ---- wave 1: block j's received bitmap and zero-tile flags ----
     if (wv == 1) {
@@ -496,10 +384,7 @@ __global__ void __launch_bounds__(256) eval_fused_kernel(ErasureSpec e, uint32_t
         block_flags_wave(e, b0, rmask);
     }
     __syncthreads();
-    if (j == 0 && e.lostrange && t == 0) {
-        e.lostrange[0] = min(min(lr[0][0], lr[0][1]), min(lr[0][2], lr[0][3]));
-        e.lostrange[1] = max(max(lr[1][0], lr[1][1]), max(lr[1][2], lr[1][3]));
-    }
+    if (j == 0 && e.lostrange && t == 0) lost_range_store(e, lr);
     if (wv != 0) return;
     RS16_STAMP(e, 2);
     // ---- wave 0: y = H_hi(x) exactly, w = y * LW mod 65535, z = H_hi(w) ----
@@ -521,16 +406,9 @@ __global__ void __launch_bounds__(256) eval_fused_kernel(ErasureSpec e, uint32_t
         y[0] = a + c, y[2] = a - c, y[1] = b + d, y[3] = b - d;
     }
     uint32_t v[4];
+    // |y| <= 65536: y + 2 * 65535 >= 0, folded to [0, 65535]
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        // |y| <= 65536: y + 2 * 65535 >= 0, folded to [0, 65535]
-        uint32_t u = (uint32_t)(y[i] + 2 * 65535);
-        u = (u & 0xFFFFu) + (u >> 16);
-        u = (u & 0xFFFFu) + (u >> 16);
-        uint32_t p = u * lw[i];
-        p = (p & 0xFFFFu) + (p >> 16);
-        v[i] = (p & 0xFFFFu) + (p >> 16);
-    }
+    for (int i = 0; i < 4; i++) v[i] = fold65535(fold65535((uint32_t)(y[i] + 2 * 65535)) * lw[i]);
     RS16_STAMP(e, 3);
     fwht256_wave(v);
     RS16_STAMP(e, 10);
@@ -538,32 +416,14 @@ __global__ void __launch_bounds__(256) eval_fused_kernel(ErasureSpec e, uint32_t
     for (int i = 0; i < 4; i++) out32[(lane + 64u * i) * 256u + j] = v[i];
     RS16_STAMP_END(e);
 }
-// Segment boundaries on 256-row blocks and 16-byte aligned flag arrays.
-static bool eval_fused_ok(const ErasureSpec& e) {
-    const auto al = [](const uint8_t* p) { return ((uintptr_t)p & 15) == 0; };
-    return e.a_count % 256 == 0 && e.chunk % 256 == 0 && e.b_count % 256 == 0 && al(e.flags_a) && al(e.flags_b);
-}
 
-hipError_t launch_eval_poly_from_flags(const ErasureSpec& e, uint32_t* work, uint32_t* out_elog,
-                                       const uint16_t* log_walsh, hipStream_t s, bool last_lo) {
-    const uint32_t ns = e.nstripes > 1 ? e.nstripes : 1;
-    if (!(e.diag & DIAG_EVAL_TWO_KERNEL) && eval_fused_ok(e) && (ns == 1 || (e.bs_fa % 16 == 0 && e.bs_fb % 16 == 0))) {
-        hipLaunchKernelGGL(eval_fused_kernel, dim3(256, ns), dim3(256), 0, s, e, work, log_walsh);
-    } else {
-        hipLaunchKernelGGL(fwht_lo_flags_kernel, dim3(256, ns), dim3(64), 0, s, e, work);
-        hipLaunchKernelGGL(fwht_hi_mulw_kernel, dim3(256, ns), dim3(64), 0, s, e, work, work, log_walsh);
-    }
-    if (last_lo)
-        hipLaunchKernelGGL((fwht_lo_kernel<false, 0, 0>), dim3(256, ns), dim3(256), 0, s, work, nullptr, out_elog, nullptr,
-                           nullptr, e.bs_work, e.bs_elog);
-    return hipGetLastError();
-}
-// eval_poly of a high-rate decode with n <= 2048 work rows:
-// the erasure vector is zero from row n on (rate_high.rs:183-197, the
-// truncation of the first fwht), so with H = H_lo H_hi only the NB = n/256
-// blocks of row bits 8-15 below n carry input, and only rows < n of the
-// output are consumed.  One 256-thread workgroup per low index j (row bits
-// 0-7), thread t = row t of every block and h = t of the middle vector:
+// The small form: eval_poly of a high-rate decode with n <= 2048 work rows
+// (SURVEY §8 A10): the erasure vector is zero from row n on
+// (rate_high.rs:183-197, the truncation of the first fwht), so with
+// H = H_lo H_hi only the NB = n/256 blocks of row bits 8-15 below n carry
+// input, and only rows < n of the output are consumed.  One 256-thread
+// workgroup per low index j (row bits 0-7), thread t = row t of every block
+// and h = t of the middle vector:
 //   x[h']  = sum_t (-1)^|j&t| e[256h' + t]            (H_lo of the NB live blocks)
 //   w[h]   = LW[256h + j] * sum_h' (-1)^|h&h'| x[h']   (H_hi, x LogWalsh)
 //   z[h''] = sum_h (-1)^|h''&h| w[h],   h'' < NB       (H_hi, live outputs only)
@@ -579,11 +439,6 @@ hipError_t launch_eval_poly_from_flags(const ErasureSpec& e, uint32_t* work, uin
 // (The kernel is short and runs once per CU: its time is instruction-fetch
 // bound, so it is written for few executed instructions, 4 waves sharing
 // each fetched line.)
-__device__ __forceinline__ uint32_t fold65535(uint32_t u) {
-    u = (u & 0xFFFFu) + (u >> 16);
-    return (u & 0xFFFFu) + (u >> 16);
-}
-__device__ __forceinline__ uint32_t mod65535(int v) { return fold65535((uint32_t)(v + 65535 * 4096)); }
 template <int NB>
 __global__ void __launch_bounds__(256) eval_small_kernel(ErasureSpec e, const uint16_t* log_walsh, uint32_t* z) {
     __shared__ int part[2][4][NB];  // per-wave parts of x and z
@@ -624,8 +479,8 @@ __global__ void __launch_bounds__(256) eval_small_kernel(ErasureSpec e, const ui
             }
         }
         if ((uint32_t)hp == j) {
-            // workgroups j < NB: the pass metadata of block j (rows >= n
-            // lie past both segments: never received)
+            // workgroups j < NB: the pass metadata of block j, each wave its
+            // 64 rows' (rows >= n lie past both segments: never received)
             const uint64_t rb = __ballot(rcv);
             chunk_counts(e, (uint32_t)hp * 256u + wv * 64u, rb, __ballot(rcv && in_a));
             if (lane == 0) {
@@ -638,25 +493,15 @@ __global__ void __launch_bounds__(256) eval_small_kernel(ErasureSpec e, const ui
             }
         }
     }
-    if (j == 0 && lane == 0) {
-        lpart[0][wv] = wlo;
-        lpart[1][wv] = whi;
-    }
+    if (j == 0 && lane == 0) lost_range_put(lpart, wv, wlo, whi);  // (from ballots: the wave's range already)
     RS16_STAMP(e, 1);
     __syncthreads();
-    if (j == 0 && t == 0 && e.lostrange) {
-        e.lostrange[0] = min(min(lpart[0][0], lpart[0][1]), min(lpart[0][2], lpart[0][3]));
-        e.lostrange[1] = max(max(lpart[1][0], lpart[1][1]), max(lpart[1][2], lpart[1][3]));
-    }
+    if (j == 0 && t == 0 && e.lostrange) lost_range_store(e, lpart);
     if (j < NB && e.zflags) {
         const uint32_t base = j * 256u, ts = 1u << e.zlo, ntile = e.n >> e.zlo;
         if (t < 256u / ts && (base >> e.zlo) + t < ntile) {
-            bool any = false;
-            for (uint32_t r = t * ts; r < (t + 1) * ts; r += 32) {
-                const uint32_t m = ts >= 32 ? 0xFFFFFFFFu : ((1u << ts) - 1) << (r & 31);
-                any |= (words[r >> 5] & m) != 0;
-            }
-            e.zflags[(base >> e.zlo) + t] = any ? 0 : 1;
+            const bool empty = ztile_empty<uint32_t>([&](uint32_t w) { return words[w]; }, t, ts);
+            e.zflags[(base >> e.zlo) + t] = empty ? 1 : 0;
         }
     }
     // y = sum_h' (-1)^|h&h'| x[h'] for h = t (h & h' = lane & h' for h' < 8)
@@ -682,28 +527,59 @@ __global__ void __launch_bounds__(256) eval_small_kernel(ErasureSpec e, const ui
     RS16_STAMP_END(e);
 }
 
-hipError_t launch_eval_poly_small(const ErasureSpec& e, uint32_t n, uint32_t* work, uint32_t* out_elog,
-                                  const uint16_t* log_walsh, hipStream_t s, bool last_lo) {
-    const uint32_t nb = n <= 256 ? 1 : n / 256;
+// ---------------------------------------------------------------------------
+// The launcher: which form evaluates the spec, then that form's launch.
+// ---------------------------------------------------------------------------
+// Segment boundaries on 256-row blocks and every stripe's flag arrays 16-byte aligned.
+static bool eval_fused_ok(const ErasureSpec& e) {
+    const auto al = [](const uint8_t* p) { return ((uintptr_t)p & 15) == 0; };
+    const bool strides = e.nstripes <= 1 || (e.bs_fa % 16 == 0 && e.bs_fb % 16 == 0);
+    return e.a_count % 256 == 0 && e.chunk % 256 == 0 && e.b_count % 256 == 0 && al(e.flags_a) && al(e.flags_b) &&
+           strides;
+}
+enum EvalForm { EVAL_SMALL, EVAL_FUSED, EVAL_TWO_KERNEL };
+static EvalForm eval_form(const ErasureSpec& e) {
+    // the high rate (tail_fill == 0: erasures are zero from row n on) with at
+    // most 8 live blocks
+    if (e.tail_fill == 0 && e.n <= 2048 && !(e.diag & DIAG_EVAL_FULL)) return EVAL_SMALL;
+    return eval_fused_ok(e) && !(e.diag & DIAG_EVAL_TWO_KERNEL) ? EVAL_FUSED : EVAL_TWO_KERNEL;
+}
+hipError_t launch_eval_poly_from_flags(const ErasureSpec& e, uint32_t* work, uint32_t* out_elog,
+                                       const uint16_t* log_walsh, hipStream_t s, bool last_lo) {
     const uint32_t ns = e.nstripes > 1 ? e.nstripes : 1;
-    switch (nb) {
-        case 1: hipLaunchKernelGGL(eval_small_kernel<1>, dim3(256, ns), dim3(256), 0, s, e, log_walsh, work); break;
-        case 2: hipLaunchKernelGGL(eval_small_kernel<2>, dim3(256, ns), dim3(256), 0, s, e, log_walsh, work); break;
-        case 4: hipLaunchKernelGGL(eval_small_kernel<4>, dim3(256, ns), dim3(256), 0, s, e, log_walsh, work); break;
-        case 8: hipLaunchKernelGGL(eval_small_kernel<8>, dim3(256, ns), dim3(256), 0, s, e, log_walsh, work); break;
-        default: return hipErrorInvalidValue;
+    uint32_t nb = 256;  // live 256-row blocks of the result
+    switch (eval_form(e)) {
+        case EVAL_SMALL: {
+            nb = e.n <= 256 ? 1 : e.n / 256;
+            const auto k = nb == 1   ? eval_small_kernel<1>
+                           : nb == 2 ? eval_small_kernel<2>
+                           : nb == 4 ? eval_small_kernel<4>
+                                     : eval_small_kernel<8>;
+            hipLaunchKernelGGL(k, dim3(256, ns), dim3(256), 0, s, e, log_walsh, work);
+            break;
+        }
+        case EVAL_FUSED:
+            hipLaunchKernelGGL(eval_fused_kernel, dim3(256, ns), dim3(256), 0, s, e, work, log_walsh);
+            break;
+        case EVAL_TWO_KERNEL:
+            hipLaunchKernelGGL(fwht_lo_flags_kernel, dim3(256, ns), dim3(64), 0, s, e, work);
+            hipLaunchKernelGGL(fwht_hi_mulw_kernel, dim3(256, ns), dim3(64), 0, s, e, work, work, log_walsh);
+            break;
     }
     if (last_lo)
-        hipLaunchKernelGGL((fwht_lo_kernel<false, 0, 0>), dim3(nb, ns), dim3(256), 0, s, work, nullptr, out_elog, nullptr,
-                           nullptr, e.bs_work, e.bs_elog);
+        hipLaunchKernelGGL(fwht_lo_kernel<uint32_t>, dim3(nb, ns), dim3(256), 0, s, work, out_elog, e.bs_work,
+                           e.bs_elog);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------
 // Engine-level fwht / eval_poly (the C ABI ops): the layers run in the
 // reference's order -- ascending distance, H_lo (bits 0-7) before H_hi
 // (bits 8-15) -- with its add_mod / sub_mod, so every output is the
 // reference's u16 bit for bit (NoSimd's radix-4 fwht_4 is two plain layers,
 // src/engine/engine_nosimd.rs:135-150; Naive, engine_naive.rs:75-92), not
 // only the same residue.  The log_walsh product is canonical (% 65535).
+// ---------------------------------------------------------------------------
 template <bool MULW>
 __global__ void __launch_bounds__(256) fwht_hi_exact_kernel(const uint32_t* in32, uint32_t* out32, uint16_t* out16,
                                                             const uint16_t* log_walsh) {
@@ -717,14 +593,14 @@ __global__ void __launch_bounds__(256) fwht_hi_exact_kernel(const uint32_t* in32
     else out32[idx] = v;
 }
 hipError_t launch_eval_poly_u16(uint16_t* data, uint32_t* work, const uint16_t* log_walsh, hipStream_t s) {
-    hipLaunchKernelGGL((fwht_lo_kernel<false, 1, 0>), dim3(256), dim3(256), 0, s, nullptr, data, work, nullptr, nullptr);
+    hipLaunchKernelGGL(fwht_lo_kernel<uint16_t>, dim3(256), dim3(256), 0, s, data, work, 0u, 0u);
     hipLaunchKernelGGL(fwht_hi_exact_kernel<true>, dim3(256), dim3(256), 0, s, work, work, nullptr, log_walsh);
-    hipLaunchKernelGGL((fwht_lo_kernel<false, 0, 0>), dim3(256), dim3(256), 0, s, work, nullptr, work, nullptr, nullptr);
+    hipLaunchKernelGGL(fwht_lo_kernel<uint32_t>, dim3(256), dim3(256), 0, s, work, work, 0u, 0u);
     hipLaunchKernelGGL(fwht_hi_exact_kernel<false>, dim3(256), dim3(256), 0, s, work, nullptr, data, nullptr);
     return hipGetLastError();
 }
 hipError_t launch_fwht_u16(uint16_t* data, uint32_t* work, hipStream_t s) {
-    hipLaunchKernelGGL((fwht_lo_kernel<false, 1, 0>), dim3(256), dim3(256), 0, s, nullptr, data, work, nullptr, nullptr);
+    hipLaunchKernelGGL(fwht_lo_kernel<uint16_t>, dim3(256), dim3(256), 0, s, data, work, 0u, 0u);
     hipLaunchKernelGGL(fwht_hi_exact_kernel<false>, dim3(256), dim3(256), 0, s, work, nullptr, data, nullptr);
     return hipGetLastError();
 }

@@ -44,4 +44,15 @@ __device__ __forceinline__ void fwht256_wave(uint32_t (&v)[4]) {
     v[3] = sub_mod(b, d);
 }
 
+// Integers to residues mod 65535 by folding the high half onto the low one
+// (2^16 == 1), for the kernels that transform exact integer sums: u < 2^32 to
+// [0, 65535] in two folds, and a signed sum |v| < 2^28 made non-negative
+// first.  65535 may stand for 0: the same residue, and the same log to every
+// consumer (exp[65535] == exp[0]).
+__device__ __forceinline__ uint32_t fold65535(uint32_t u) {
+    u = (u & 0xFFFFu) + (u >> 16);
+    return (u & 0xFFFFu) + (u >> 16);
+}
+__device__ __forceinline__ uint32_t mod65535(int v) { return fold65535((uint32_t)(v + 65535 * 4096)); }
+
 }  // namespace rs16

@@ -648,11 +648,12 @@ struct ErasureSpec {           // builds the erasure vector of rate_{high,low}.r
     uint32_t bs_work, bs_elog, bs_rbits, bs_zflags, bs_lost;
     uint32_t diag;             // the engine's diagnostic switches (DiagFlags; host side)
 };
+// The erasure logs of e into work (last_lo == false: without the last
+// 256-point FWHT, which the consumer finishes) or out_elog, by the form the
+// spec admits -- high-rate decodes with n <= 2048 rows (tail_fill == 0) write
+// rows [0, n) only.
 hipError_t launch_eval_poly_from_flags(const ErasureSpec& e, uint32_t* work, uint32_t* out_elog,
                                        const uint16_t* log_walsh, hipStream_t s, bool last_lo);
-// high-rate decodes with n <= 2048 rows (tail_fill == 0): 2 kernels, rows [0, n) of out_elog
-hipError_t launch_eval_poly_small(const ErasureSpec& e, uint32_t n, uint32_t* work, uint32_t* out_elog,
-                                  const uint16_t* log_walsh, hipStream_t s, bool last_lo);
 hipError_t launch_eval_poly_u16(uint16_t* data, uint32_t* work, const uint16_t* log_walsh, hipStream_t s);
 hipError_t launch_fwht_u16(uint16_t* data, uint32_t* work, hipStream_t s);
 

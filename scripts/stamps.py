@@ -10,7 +10,7 @@ own clock).  Phases (rs16_pass.hpp RS16_STAMP): 0 start, 1 loads issued,
 direction done, 6 formal derivative (the wave-staged encoder passes: wave
 0's first butterfly, reported as "start->first butterfly"), 7 layout-B FFT
 layers, 8 layout switch, 9 last layers, 10 stores issued, 11 stores done; EVAL_POLY (the
-n <= 2048 eval kernel, rs16_misc.hip): 0 start, 1 flags in, 2 sums done,
+n <= 2048 eval kernel, rs16_eval.hip): 0 start, 1 flags in, 2 sums done,
 10 store issued, 11 store done.  Programs: RS16_STAMP_PROGS (comma list);
 size: argv[1] (k = m); loss pattern: RS16_STAMPS_LOSS, RS16_STAMPS_SCATTER
 (below)."""

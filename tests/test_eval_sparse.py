@@ -1,4 +1,4 @@
-"""The algebra of the sparse eval_poly kernel (rs16_misc.hip eval_small_kernel,
+"""The algebra of the sparse eval_poly kernel (rs16_eval.hip eval_small_kernel,
 DESIGN.md §3.3) against the oracle's eval_poly (src/engine.rs:207-218): for a
 high-rate erasure vector that is zero from row n on (rate_high.rs:183-197),
 rows [0, n) of FWHT(LogWalsh . FWHT(e)) follow from the n/256 live blocks of
@@ -36,7 +36,7 @@ def test_sparse_eval_matches_oracle(n):
 
 
 def _nz80(f):
-    """rs16_misc.hip nz80: 0x80 in every nonzero byte of u32 words."""
+    """rs16_eval.hip nz80: 0x80 in every nonzero byte of u32 words."""
     return (((f & 0x7F7F7F7F) + 0x7F7F7F7F) | f) & 0x80808080
 
 

@@ -242,7 +242,7 @@ def lost_pattern(k, m, pattern):
 def test_decode_lost_range_pruning(eng, k, m, sb, pattern):
     # The general decode prunes DEC_MID's FFT / stores and DEC_LAST's tiles to
     # the lost originals' row range computed on the device by the eval_poly
-    # kernels (rs16_misc.hip lost_part_wave / lost_range_wave, eval_small);
+    # kernels (rs16_eval.hip lost_part_wave / lost_range_wave, eval_small);
     # every lost original must still come back bit-exactly, and received
     # originals must stay untouched.
     original = generate_original(k, sb, 13)

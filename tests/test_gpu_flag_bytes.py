@@ -4,7 +4,7 @@ flag arrays need no alignment, and no byte before or behind a flag array is
 read as a flag.  Every other GPU test uploads flags of 0 and 1 only.
 
 The device and the host read the caller's flag bytes in a dozen separately
-written places (rs16_misc.hip: erasure_at / received_at, nz80 + sdot4 in
+written places (rs16_eval.hip: erasure_at / received_at, nz80 + sdot4 in
 eval_fused_kernel, eval_small_kernel; rs16_col.hip: ColEval::prep and the
 gathers of col_kernel / col2_kernel; rs16_pass.hpp: RcvCount; the reveal's
 row_lost_original in rs16_pass_common.hpp; rs16_api_host.cpp: the host counts,
