@@ -602,7 +602,7 @@ int rs16_verify_device_batch(rs16_engine* eng, size_t original_count, size_t rec
  * UNLOCATABLE unless encode(E) equals the syndrome in all recovery_count rows of
  * the block.  The engine keeps E, both encodes and the counts: (original_count +
  * 2 recovery_count) x shard_bytes beside the encode's work space.
- * Not provided: a batch form, host-memory forms, more than one corrupt shard
+ * Not provided: host-memory forms, more than one corrupt shard
  * per codeword, and skipping the second encode when no block names an original
  * (the host would have to wait for the device to know).
  * When to prefer it (measured on one MI355X at 1 KiB shards, clean and with
@@ -631,6 +631,106 @@ enum { RS16_LOCATE_CLEAN = 0, RS16_LOCATE_ORIGINAL = 1, RS16_LOCATE_RECOVERY = 2
 int rs16_locate_device(rs16_locate_plan* plan, size_t shard_bytes, const void* d_original, const void* d_recovery,
                        uint8_t* d_block_status, uint32_t* d_block_shard, void* d_block_fix, void* stream,
                        rs16_error* err);
+/* Heal: fix located blocks in place; locate and heal stripe batches.  The last
+ * link of scrub -> locate -> fix, in the form the other operations have: a
+ * rotting device holds the same index of every stripe, so a scrub flags many
+ * stripes of one geometry at once.
+ *
+ * rs16_locate_device_batch is rs16_locate_device for nstripes stripes of the
+ * plan's geometry: stripe i's originals at d_original + i original_stride, its
+ * recovery at d_recovery + i recovery_stride (bytes, as rs16_encode_device_batch
+ * takes them), its status at d_block_status + i status_stride (bytes, >= B),
+ * its shard entries at d_block_shard + i shard_stride (ENTRIES, >= B) and its
+ * fix at d_block_fix + i fix_stride (bytes, >= 64 B; d_block_fix may be NULL).
+ * Stripe i's status, shard and fix are what rs16_locate_device gives on stripe i
+ * alone.  Every entry of each stripe's used range is written; bytes between the
+ * strides are never written.  Both shard arrays are READ ONLY.
+ *
+ * rs16_heal_device runs the locate's sequence and then XORs, in place, the 64
+ * fix bytes of every block that ends RS16_LOCATE_ORIGINAL into the named
+ * original when heal_mask has RS16_HEAL_ORIGINAL, and of every block that ends
+ * RS16_LOCATE_RECOVERY into the named recovery shard when it has
+ * RS16_HEAL_RECOVERY.  "Ends" means after the confirm kernel: a block
+ * downgraded to UNLOCATABLE is never written.  CLEAN blocks, UNLOCATABLE blocks
+ * and blocks of a kind outside the mask are not written, and no byte of any
+ * other shard or block is.  d_block_status and d_block_shard may be NULL; when
+ * given they report what was found BEFORE the fix, exactly as the locate would.
+ * d_counts (required) gets four uint32: d_counts[RS16_LOCATE_*] = the number of
+ * the stripe's blocks with each final status, all four written whatever they
+ * held; the host reads 16 bytes per stripe to learn whether anything stayed
+ * UNLOCATABLE (a healed stripe scrubs clean exactly when that count is 0).
+ * rs16_heal_device_batch is the same for nstripes stripes: the strides above
+ * less the fix's, and stripe i's counts at d_counts + i counts_stride (ENTRIES,
+ * >= 4).
+ * The guarantee is the locate's: with at most recovery_count - 1 corrupt shards
+ * per element position a heal never writes a wrong shard.
+ *
+ * Errors, in this order: those of rs16_locate_device, the NULL or detached plan
+ * first (for the heal a NULL d_block_status or d_block_shard is no error); for
+ * the heal a heal_mask of 0 or with unknown bits, then a NULL d_counts:
+ * InvalidArgument; for the batch forms a stride of a shard array that is no
+ * multiple of 64 or smaller than its stripe, then an output stride below its
+ * minimum, then nstripes > 65535: InvalidArgument.  nstripes == 0 is RS16_OK
+ * with nothing launched and nothing written.
+ * Like rs16_locate_device the calls are asynchronous on `stream`, ordered on the
+ * engine's scratch, and no decode: a pending rs16_decode_prepare and the report
+ * of rs16_decode_check survive them.  Column slices do not apply.
+ * Work space: the engine's buffers of the locate, grown to nstripes x
+ * (original_count + 2 recovery_count) x shard_bytes, nstripes x the pairs (16
+ * copies of shard_bytes / 2 x 8 bytes up to 64 KiB shards, one above),
+ * nstripes x B candidates and, for the heal, nstripes x B x 64 bytes of fix
+ * (plus nstripes x B x 5 bytes for the status and shard entries the caller did
+ * not ask for), beside the encode's work space.  The batch is never grouped or
+ * chunked: an allocation failure is RS16_DEVICE_ERROR, and the caller splits.
+ * The sequence on the device: both encodes through the engine's batch encode
+ * (the one-chunk high rate in launches that cover all stripes, other shapes
+ * stripe by stripe), the scan and the confirm kernel with the stripes in grid z
+ * (the scan still aims at about 2048 workgroups in all), the decide kernel over
+ * all stripes' blocks numbered through, and for the heal a clear of the counts
+ * and one more kernel (16 lanes per block, one dword each).
+ * When to prefer it (measured on one MI355X at 1 KiB shards, clean and with one
+ * original corrupted per stripe, against N rs16_locate_device calls of the
+ * library as it was before the batch forms, each build in a process of its
+ * own, five alternating pairs; DESIGN.md 3.20, profiles/r20_heal.txt): from 4
+ * flagged stripes of one geometry on, locate them in one call.  N x 1000:1000:
+ * 48.4 / 58.6 / 130.1 us clean and 52.8 / 62.7 / 138.1 corrupted for N = 4 / 8 /
+ * 32 (12.1 / 7.3 / 4.1 us per stripe) against loops of 96.9 / 192.9 / 793.9 and
+ * 109.3 / 216.7 / 908.1 -- 2.0 / 3.3 / 6.1 x and 2.1 / 3.5 / 6.6 x, faster in every
+ * pair.  4 x 32768:32768: 467.8 and 484.4 us against 530.4 and 583.5 (1.13 x /
+ * 1.20 x, every pair): the encodes dominate there and gain nothing from the
+ * batch; the four short kernels are paid once.  The batch of 1000:1000 stripes
+ * encodes through the pass kernels, not the column codec (three launches for
+ * all stripes), so one stripe through the batch call costs what the single call
+ * costs (24.3 / 27.3 us) and two or three are not measured.  The heal adds one
+ * clear and one kernel: +3.1 .. +4.6 us per CALL over the locate at every size
+ * measured, whatever the stripe count, against a download, a host loop and one
+ * 64-byte XOR launch per dirty block.  rs16_locate_device itself is unchanged:
+ * 24.39 (24.27 .. 24.44) against 24.45 (24.40 .. 24.50) us clean and 27.40
+ * against 27.31 corrupted at 1000:1000; at 32768:32768 134.3 against 134.5 clean,
+ * and corrupted 142.4 against 143.0 in one geometry of the run and 148.7 against
+ * 143.6 in the other (the same call on other buffers).  Its status, shard and
+ * fix are byte-equal to the earlier library's.  Sizes in between are not
+ * measured. */
+int rs16_locate_device_batch(rs16_locate_plan* plan, size_t shard_bytes, size_t nstripes, const void* d_original,
+                             size_t original_stride, const void* d_recovery, size_t recovery_stride,
+                             uint8_t* d_block_status, size_t status_stride, uint32_t* d_block_shard,
+                             size_t shard_stride, void* d_block_fix, size_t fix_stride, void* stream,
+                             rs16_error* err);
+enum { RS16_HEAL_ORIGINAL = 1, RS16_HEAL_RECOVERY = 2 }; /* which arrays the heal may write */
+int rs16_heal_device(rs16_locate_plan* plan, size_t shard_bytes, void* d_original, void* d_recovery, int heal_mask,
+                     uint8_t* d_block_status, uint32_t* d_block_shard, uint32_t* d_counts, void* stream,
+                     rs16_error* err);
+int rs16_heal_device_batch(rs16_locate_plan* plan, size_t shard_bytes, size_t nstripes, void* d_original,
+                           size_t original_stride, void* d_recovery, size_t recovery_stride, int heal_mask,
+                           uint8_t* d_block_status, size_t status_stride, uint32_t* d_block_shard,
+                           size_t shard_stride, uint32_t* d_counts, size_t counts_stride, void* stream,
+                           rs16_error* err);
+/* Host arithmetic only, for tests: the scan launch's shape {cw, rsub, gx, gy,
+ * rows_per_wg} for nstripes stripes -- cw column lanes by rsub rows per
+ * workgroup pass, gx workgroups over the columns, gy over the rows of
+ * rows_per_wg each.  0, or -1 for a shard size, recovery count or stripe count
+ * that no locate takes. */
+int rs16_host_locate_scan_shape(size_t shard_bytes, size_t recovery_count, size_t nstripes, uint32_t out[5]);
 /* Checked mode of the engine's last decode: waits for `stream` and compares
  * the received counts that decode was given with the rows the device flags
  * mark received (the eval_poly kernels count them per 64-row chunk as they

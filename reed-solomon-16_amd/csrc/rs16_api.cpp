@@ -317,7 +317,7 @@ extern "C" const char* rs16_prog_name(int prog) {
                                   "DEC_MID_DIRECT", "DEC_TILE_LAST",
                                   "DEC_LAST_SEL", "DEC_SINGLE_SEL", "DEC_TILE_LAST_SEL", "COL_DEC_SEL",
                                   "ENC_LAST_VFY", "ENC_SINGLE_VFY", "VERIFY_CMP",
-                                  "LOCATE_SCAN", "LOCATE_DECIDE", "LOCATE_CONFIRM",
+                                  "LOCATE_SCAN", "LOCATE_DECIDE", "LOCATE_CONFIRM", "LOCATE_APPLY",
                                   "DEC_LAST_ALL", "DEC_SINGLE_ALL", "REPAIR_COPY"};
     static_assert(sizeof names / sizeof names[0] == NUM_PROF, "profiling names");
     return (prog >= 0 && prog < NUM_PROF) ? names[prog] : "?";
@@ -459,7 +459,7 @@ extern "C" void rs16_engine_free(rs16_engine* e) {
     for (auto& l : e->ev_lane) l.release();
     e->ws_flags.release();
     e->ws_rep.release();
-    e->ws_loc_e.release(), e->ws_loc_rep.release(), e->ws_loc_acc.release(), e->ws_loc_cand.release();
+    e->ws_loc_e.release(), e->ws_loc_rep.release(), e->ws_loc_acc.release(), e->ws_loc_cand.release(), e->ws_loc_fix.release();
     e->hp_flags.release();
     for (auto& sl : e->hslot) {
         if (sl.s) (void)hipStreamSynchronize(sl.s), (void)hipStreamDestroy(sl.s);

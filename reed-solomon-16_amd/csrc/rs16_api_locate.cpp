@@ -1,6 +1,7 @@
 // rs16_api_locate.cpp -- C ABI (include/rs16.h): locating the one corrupt shard
 // of each 64-byte column block of a stripe (rs16_locate_plan,
-// rs16_locate_device).
+// rs16_locate_device / _batch) and fixing it in place (rs16_heal_device /
+// _batch).
 #include "rs16_api.hpp"
 
 using namespace rs16;
@@ -125,64 +126,163 @@ extern "C" int rs16_locate_plan_rows(rs16_locate_plan* p, uint16_t* out, rs16_er
 }
 
 // A work buffer of the locate that must keep its contents between calls: grown
-// if needed, *regrown set when that lost them.
-static hipError_t keep(DevBuf& b, size_t bytes, bool* regrown) {
-    if (bytes > b.cap) *regrown = true;
+// if needed, *clean reset when that lost them (at once: a later step of the
+// call may fail).
+static hipError_t keep(DevBuf& b, size_t bytes, bool* clean) {
+    if (bytes > b.cap) *clean = false;
     return b.reserve(bytes);
 }
 
-extern "C" int rs16_locate_device(rs16_locate_plan* p, size_t S, const void* d_original, const void* d_recovery,
-                                  uint8_t* d_block_status, uint32_t* d_block_shard, void* d_block_fix, void* stream,
-                                  rs16_error* err) {
+// What the heal adds to a locate (nullptr: a locate): the arrays it may write
+// are the call's shard arrays, by the mask; the counts are the caller's.
+struct Heal {
+    int mask;
+    uint32_t* counts;
+    size_t counts_stride;  // entries
+};
+
+// The used range of each stripe's entries of an output array cleared, the bytes
+// between the strides left alone.
+static hipError_t clear_strided(void* p, size_t stride, size_t used, size_t nstripes, hipStream_t s) {
+    if (nstripes == 1 || stride == used) return hipMemsetAsync(p, 0, (nstripes - 1) * stride + used, s);
+    return hipMemset2DAsync(p, stride, 0, used, nstripes, s);
+}
+
+// All four entry points: nstripes stripes of the plan's geometry, stripe i's
+// arrays at + i o_stride / r_stride and its outputs at + i st_stride (bytes) /
+// sh_stride (entries) / fx_stride (bytes) (the single calls: one stripe).  The
+// engine's buffers hold every stripe's share side by side: both encodes and E at
+// their natural strides, nslots copies of the pairs and B candidates per
+// stripe, and for the heal B x 64 bytes of fix per stripe and, where the caller
+// gave none, status and shard.
+static int locate(rs16_locate_plan* p, size_t S, bool batched, size_t nstripes, const void* d_original,
+                  size_t o_stride, const void* d_recovery, size_t r_stride, uint8_t* d_status, size_t st_stride,
+                  uint32_t* d_shard, size_t sh_stride, void* d_fix, size_t fx_stride, const Heal* heal, void* stream,
+                  rs16_error* err) {
     if (!p || !p->eng) return set_error(err, RS16_INVALID_ARGUMENT);
     const size_t k = p->k, m = p->m;
     const bool high = p->high;
     if (int rc = rs16_validate(high ? RS16_RATE_HIGH : RS16_RATE_LOW, k, m, S, err)) return rc;
-    if (!d_original || !d_recovery || !d_block_status || !d_block_shard || !shard_aligned(d_original) ||
-        !shard_aligned(d_recovery))
+    if (!batched) o_stride = k * S, r_stride = m * S;  // (one stripe: the kernels still ask for whole strides)
+    if (!d_original || !d_recovery || !shard_aligned(d_original) || !shard_aligned(d_recovery) ||
+        (!heal && (!d_status || !d_shard)))
         return set_error(err, RS16_INVALID_ARGUMENT);
+    if (heal && (heal->mask == 0 || (heal->mask & ~(RS16_HEAL_ORIGINAL | RS16_HEAL_RECOVERY)) || !heal->counts))
+        return set_error(err, RS16_INVALID_ARGUMENT);
+    const size_t B = S / 64;
+    if (batched && (!batch_layout_ok(k, m, S, nstripes, o_stride, r_stride) || (d_status && st_stride < B) ||
+                    (d_shard && sh_stride < B) || (d_fix && fx_stride < 64 * B) ||
+                    (heal && heal->counts_stride < 4) || nstripes > 65535))
+        return set_error(err, RS16_INVALID_ARGUMENT);
+    if (nstripes == 0) return set_error(err, RS16_OK);
     rs16_engine* e = p->eng;
     hipStream_t s;
     if (int rc = begin_ordered(e, stream, &s, err)) return rc;
-    RS16_HIP(e->ws_rep.reserve(m * S));
-    RS16_HIP(e->ws_loc_rep.reserve(m * S));
-    RS16_HIP(e->ws_loc_cand.reserve(S / 64 * 4));
-    bool regrown = false;
-    RS16_HIP(keep(e->ws_loc_e, k * S, &regrown));
+    RS16_HIP(e->ws_rep.reserve(nstripes * m * S));
+    RS16_HIP(e->ws_loc_rep.reserve(nstripes * m * S));
+    // per stripe B candidates and, for a heal without the caller's, B shard entries and B status bytes
+    RS16_HIP(e->ws_loc_cand.reserve(nstripes * B * (heal ? 9 : 4)));
+    if (heal) RS16_HIP(e->ws_loc_fix.reserve(nstripes * B * 64));
+    RS16_HIP(keep(e->ws_loc_e, nstripes * k * S, &e->loc_clean));
     // copies of the scan's pairs, which its row walkers spread over: shards up
     // to 64 KiB have few lanes per row and many walkers per column
     const uint32_t nslots = S <= 65536 ? LOCATE_MAX_SLOTS : 1;
-    RS16_HIP(keep(e->ws_loc_acc, nslots * (S / 2) * 8, &regrown));
-    if (regrown || !e->loc_clean) {
-        e->loc_clean = false;
+    RS16_HIP(keep(e->ws_loc_acc, nstripes * nslots * (S / 2) * 8, &e->loc_clean));
+    // Both are zero as a whole between calls, so a call may lay its stripes
+    // over them as it likes: one stripe after a batch, a batch after one stripe.
+    if (!e->loc_clean) {
         RS16_HIP(hipMemsetAsync(e->ws_loc_e.p, 0, e->ws_loc_e.cap, s));
         RS16_HIP(hipMemsetAsync(e->ws_loc_acc.p, 0, e->ws_loc_acc.cap, s));
     }
     e->loc_clean = false;  // until the confirm kernel, which puts the last of it back, is enqueued
     const uint16_t* tab = (const uint16_t*)p->tab.p;
     LocateArgs a{};
-    a.enc = (const uint8_t*)e->ws_rep.p;
-    a.rec = (const uint8_t*)d_recovery;
-    a.enc2 = (const uint8_t*)e->ws_loc_rep.p;
-    a.E = (uint8_t*)e->ws_loc_e.p;
-    a.acc = (unsigned long long*)e->ws_loc_acc.p;
+    a.enc = (const uint8_t*)e->ws_rep.p, a.bs_enc = m * S;
+    a.rec = (const uint8_t*)d_recovery, a.bs_rec = r_stride;
+    a.enc2 = (const uint8_t*)e->ws_loc_rep.p, a.bs_enc2 = m * S;
+    a.E = (uint8_t*)e->ws_loc_e.p, a.bs_E = k * S;
+    a.acc = (unsigned long long*)e->ws_loc_acc.p, a.bs_acc = nslots * (S / 2);
     a.nslots = nslots;
-    a.cand = (uint32_t*)e->ws_loc_cand.p;
+    a.cand = (uint32_t*)e->ws_loc_cand.p, a.bs_cand = B;
     a.log = tab, a.exp = tab + GF_ORDER, a.ratio = tab + 2 * (size_t)GF_ORDER, a.log_m0 = tab + 3 * (size_t)GF_ORDER;
-    a.status = d_block_status, a.shard = d_block_shard, a.fix = (uint8_t*)d_block_fix;
-    a.S = S, a.k = (uint32_t)k, a.m = (uint32_t)m, a.blocks = (uint32_t)(S / 64);
+    a.status = d_status, a.bs_status = st_stride;
+    a.shard = d_shard, a.bs_shard = sh_stride;
+    a.fix = (uint8_t*)d_fix, a.bs_fix = fx_stride;
+    if (heal) {
+        if (!d_shard) a.shard = a.cand + nstripes * B, a.bs_shard = B;
+        if (!d_status) a.status = (uint8_t*)(a.cand + 2 * nstripes * B), a.bs_status = B;
+        a.fix = (uint8_t*)e->ws_loc_fix.p, a.bs_fix = 64 * B;
+        a.orig_w = heal->mask & RS16_HEAL_ORIGINAL ? (uint8_t*)d_original : nullptr, a.bs_orig = o_stride;
+        a.rec_w = heal->mask & RS16_HEAL_RECOVERY ? (uint8_t*)d_recovery : nullptr;
+        a.counts = heal->counts, a.bs_counts = heal->counts_stride;
+    }
+    a.S = S, a.k = (uint32_t)k, a.m = (uint32_t)m, a.blocks = (uint32_t)B, a.nstripes = (uint32_t)nstripes;
     // the syndromes' first half, then what they say ...
-    if (int rc = encode_stripes(e, high, k, m, S, 1, (const uint8_t*)d_original, 0, (uint8_t*)e->ws_rep.p, 0, s, err))
+    if (int rc = encode_stripes(e, high, k, m, S, nstripes, (const uint8_t*)d_original, o_stride,
+                                (uint8_t*)e->ws_rep.p, a.bs_enc, s, err))
         return rc;
     if (int rc = e->profiled(PROF_LOCATE_SCAN, s, err, [&](uint64_t*) { return launch_locate_scan(a, s); })) return rc;
     if (int rc = e->profiled(PROF_LOCATE_DECIDE, s, err, [&](uint64_t*) { return launch_locate_decide(a, s); }))
         return rc;
     // ... and the check of every ORIGINAL candidate against all m rows.  Always
     // run: whether any block names an original is known on the device only.
-    if (int rc = encode_stripes(e, high, k, m, S, 1, a.E, 0, (uint8_t*)e->ws_loc_rep.p, 0, s, err)) return rc;
+    if (int rc = encode_stripes(e, high, k, m, S, nstripes, a.E, a.bs_E, (uint8_t*)e->ws_loc_rep.p, a.bs_enc2, s, err))
+        return rc;
     if (int rc = e->profiled(PROF_LOCATE_CONFIRM, s, err, [&](uint64_t*) { return launch_locate_confirm(a, s); }))
         return rc;
     e->loc_clean = true;
+    if (heal) {
+        // after both encodes and every read of the stored shards: the fix goes in place
+        RS16_HIP(clear_strided(heal->counts, 4 * heal->counts_stride, 16, nstripes, s));
+        if (int rc = e->profiled(PROF_LOCATE_APPLY, s, err, [&](uint64_t*) { return launch_locate_apply(a, s); }))
+            return rc;
+    }
     if (int rc = e->scratch_done(s, err)) return rc;
     return set_error(err, RS16_OK);
+}
+
+extern "C" int rs16_locate_device(rs16_locate_plan* p, size_t S, const void* d_original, const void* d_recovery,
+                                  uint8_t* d_block_status, uint32_t* d_block_shard, void* d_block_fix, void* stream,
+                                  rs16_error* err) {
+    return locate(p, S, false, 1, d_original, 0, d_recovery, 0, d_block_status, S / 64, d_block_shard, S / 64,
+                  d_block_fix, S, nullptr, stream, err);
+}
+
+extern "C" int rs16_locate_device_batch(rs16_locate_plan* p, size_t S, size_t nstripes, const void* d_original,
+                                        size_t original_stride, const void* d_recovery, size_t recovery_stride,
+                                        uint8_t* d_block_status, size_t status_stride, uint32_t* d_block_shard,
+                                        size_t shard_stride, void* d_block_fix, size_t fix_stride, void* stream,
+                                        rs16_error* err) {
+    return locate(p, S, true, nstripes, d_original, original_stride, d_recovery, recovery_stride, d_block_status,
+                  status_stride, d_block_shard, shard_stride, d_block_fix, fix_stride, nullptr, stream, err);
+}
+
+extern "C" int rs16_heal_device(rs16_locate_plan* p, size_t S, void* d_original, void* d_recovery, int heal_mask,
+                                uint8_t* d_block_status, uint32_t* d_block_shard, uint32_t* d_counts, void* stream,
+                                rs16_error* err) {
+    const Heal heal{heal_mask, d_counts, 4};
+    return locate(p, S, false, 1, d_original, 0, d_recovery, 0, d_block_status, S / 64, d_block_shard, S / 64, nullptr,
+                  0, &heal, stream, err);
+}
+
+extern "C" int rs16_heal_device_batch(rs16_locate_plan* p, size_t S, size_t nstripes, void* d_original,
+                                      size_t original_stride, void* d_recovery, size_t recovery_stride, int heal_mask,
+                                      uint8_t* d_block_status, size_t status_stride, uint32_t* d_block_shard,
+                                      size_t shard_stride, uint32_t* d_counts, size_t counts_stride, void* stream,
+                                      rs16_error* err) {
+    const Heal heal{heal_mask, d_counts, counts_stride};
+    return locate(p, S, true, nstripes, d_original, original_stride, d_recovery, recovery_stride, d_block_status,
+                  status_stride, d_block_shard, shard_stride, nullptr, 0, &heal, stream, err);
+}
+
+// The scan launch's shape {cw, rsub, gx, gy, rows_per_wg} for nstripes stripes
+// of recovery_count rows of shard_bytes (include/rs16.h); 0, or -1 for sizes no
+// locate takes.  Host arithmetic only.
+extern "C" int rs16_host_locate_scan_shape(size_t S, size_t m, size_t nstripes, uint32_t out[5]) {
+    if (!out || S == 0 || S % 64 || S >= ((size_t)1 << 32) || m == 0 || m >= GF_ORDER || nstripes == 0 ||
+        nstripes > 65535)
+        return -1;
+    const LocateScanShape sh = locate_scan_shape(S, (uint32_t)m, (uint32_t)nstripes);
+    out[0] = sh.cw, out[1] = sh.rsub, out[2] = sh.gx, out[3] = sh.gy, out[4] = sh.rows_per_wg;
+    return 0;
 }

@@ -172,12 +172,15 @@ struct rs16_engine {
     // the repair's recovery-only path: the re-encoded recovery shards of the
     // call's stripes (recovery_count x shard_bytes each), reserved on first use
     rs16::DevBuf ws_rep;
-    // rs16_locate_device: the candidate errors of the originals (k x S), their
-    // encode (m x S), the per-element (count, row sum) pairs of the scan and
-    // the per-block candidates.  ws_loc_e and the pairs are all zero between
-    // calls (loc_clean): the kernels put back what they wrote, and a call that
-    // finds the buffers regrown or a previous call cut short clears them whole.
-    rs16::DevBuf ws_loc_e, ws_loc_rep, ws_loc_acc, ws_loc_cand;
+    // rs16_locate_device / _batch, rs16_heal_device / _batch, per stripe of the
+    // call: the candidate errors of the originals (k x S), their encode (m x S),
+    // the per-element (count, row sum) pairs of the scan, the per-block
+    // candidates (for a heal also the status and shard entries the caller did
+    // not ask for) and the heal's fix (B x 64).  ws_loc_e and the pairs are all
+    // zero as a whole between calls (loc_clean), whatever the stripes of the
+    // next call: the kernels put back what they wrote, and a call that finds the
+    // buffers regrown or a previous call cut short clears them whole.
+    rs16::DevBuf ws_loc_e, ws_loc_rep, ws_loc_acc, ws_loc_cand, ws_loc_fix;
     bool loc_clean = false;
     // the general decode's middle pass as v_perm tables of its matrix, per
     // transform size L (mid_tables; built on first use)

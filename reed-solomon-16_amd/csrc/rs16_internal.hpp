@@ -171,6 +171,7 @@ enum ProfId : int {
     PROF_LOCATE_SCAN,     // per element position: rows with a nonzero syndrome element, the sum of those rows
     PROF_LOCATE_DECIDE,   // per block: status, shard, fix; an ORIGINAL candidate's error into the error array
     PROF_LOCATE_CONFIRM,  // encode(error array) against the syndrome in every row of the ORIGINAL blocks
+    PROF_LOCATE_APPLY,    // the heal: each located block's fix XORed into the named shard, the blocks counted by status
     // The repair's programs (rs16_repair_device; rs16_pass_repair.hip), behind
     // every other id.  The first two are pass programs with kernels
     // (launch_pass takes them), the third is the copy kernel of the
@@ -539,9 +540,11 @@ hipError_t launch_verify_cmp(const uint8_t* enc, const uint8_t* rec, const uint8
                              uint64_t bs_rows, uint64_t bs_cols, uint32_t nstripes, hipStream_t s);
 
 // Locating the one corrupt shard of each 64-byte column block
-// (rs16_locate_device; rs16_locate.hip).  The syndrome of row j is enc[j] ^
-// rec[j], never stored.  Element p of a row (p < S / 2) is element p & 31 of
-// block p >> 5: low byte at 64 (p >> 5) + (p & 31), high byte 32 further.
+// (rs16_locate_device / _batch, rs16_heal_device / _batch; rs16_locate.hip).
+// The syndrome of row j is enc[j] ^ rec[j], never stored.  Element p of a row
+// (p < S / 2) is element p & 31 of block p >> 5: low byte at 64 (p >> 5) +
+// (p & 31), high byte 32 further.  The members describe stripe 0; stripe i of
+// the nstripes lies at + i times the array's stripe stride (bs_*).
 constexpr uint32_t LOCATE_MAX_SLOTS = 16;  // copies of the scan's pairs (LocateArgs::nslots)
 struct LocateArgs {
     const uint8_t* enc;     // the engine's encode of the stored originals (m x S)
@@ -565,18 +568,33 @@ struct LocateArgs {
     uint8_t* fix;           // blocks x 64 bytes, nullptr: none
     uint64_t S;
     uint32_t k, m, blocks;
+    uint32_t nstripes;      // <= 65535
+    // stripe strides: bytes of enc / enc2 / rec / E / status / fix, pairs of
+    // acc (nslots S / 2 at least), entries of cand / shard
+    uint64_t bs_enc, bs_enc2, bs_rec, bs_E, bs_acc, bs_cand, bs_status, bs_shard, bs_fix;
+    // The heal (locate_apply_kernel) only: the arrays it may write (nullptr:
+    // that kind is not healed; rec_w is rec, stride bs_rec), and per stripe the
+    // four block counts by final status, cleared before the launch.
+    uint8_t* orig_w;
+    uint8_t* rec_w;
+    uint32_t* counts;
+    uint64_t bs_orig, bs_counts;  // bytes / entries
 };
 // The shape of the scan launch: cw column lanes (a lane = one low dword and the
 // matching high dword, 4 elements; S / 8 per row) by rsub rows per workgroup
-// pass, gx workgroups over the columns, gy over the rows, rows_per_wg rows each.
+// pass, gx workgroups over the columns, gy over the rows, rows_per_wg rows each;
+// grid z takes the stripes, and the launch aims at about the same number of
+// workgroups in all, so gy shrinks towards 1 as the stripes get more.
 // Host arithmetic only.
 struct LocateScanShape {
     uint32_t cw, rsub, gx, gy, rows_per_wg;
 };
-LocateScanShape locate_scan_shape(uint64_t S, uint32_t m);
+LocateScanShape locate_scan_shape(uint64_t S, uint32_t m, uint32_t nstripes);
 hipError_t launch_locate_scan(const LocateArgs& a, hipStream_t s);
 hipError_t launch_locate_decide(const LocateArgs& a, hipStream_t s);
 hipError_t launch_locate_confirm(const LocateArgs& a, hipStream_t s);
+// The heal's last kernel: status / shard / fix as the confirm kernel left them.
+hipError_t launch_locate_apply(const LocateArgs& a, hipStream_t s);
 // The plan's unit stripe: byte `value` at element position q of row i0 + q for
 // q < n -- byte 64 (q >> 5) + (q & 31) of a row of Sc bytes.
 hipError_t launch_locate_unit(uint8_t* buf, uint64_t Sc, uint32_t i0, uint32_t n, uint32_t value, hipStream_t s);

@@ -1,7 +1,8 @@
-// rs16_locate.hip -- the kernels of rs16_locate_device (include/rs16.h): which
-// one shard of each 64-byte column block is corrupt.  The engine encodes the
-// stored originals into a buffer of its own (enc); the syndrome of recovery row
-// j is enc[j] ^ rec[j] and is never stored.
+// rs16_locate.hip -- the kernels of rs16_locate_device / _batch and
+// rs16_heal_device / _batch (include/rs16.h): which one shard of each 64-byte
+// column block is corrupt, for one stripe or many of one geometry.  The engine
+// encodes the stored originals into a buffer of its own (enc); the syndrome of
+// recovery row j is enc[j] ^ rec[j] and is never stored.
 //   scan     per element position, over all m rows: how many rows have a
 //            nonzero syndrome element there, and the sum of those rows (the
 //            row itself when there is one)
@@ -9,6 +10,8 @@
 //            scatter an ORIGINAL candidate's error into the error array E
 //   confirm  after the engine's encode of E: every ORIGINAL block must have
 //            encode(E) equal to the syndrome in all m rows, else UNLOCATABLE
+//   apply    the heal only: XOR each located block's fix into the named shard
+//            and count the stripe's blocks by final status
 // A unit of its own, so the kernels of the other units compile as before.
 #include "rs16_internal.hpp"
 
@@ -50,11 +53,18 @@ __device__ __forceinline__ void count_row(uint32_t d, uint32_t r, uint32_t (&cnt
 // rows) to the element's pair with one 64-bit atomic.  When an original is
 // corrupt every thread of a column does, so the pairs exist nslots times and
 // the row walkers spread over them (one address took 5 ns per atomic:
-// profiles/r19_locate.txt); the decide kernel adds the copies up.
+// profiles/r19_locate.txt); the decide kernel adds the copies up.  Grid z is
+// the stripe: the three arrays move on by their stripe strides (bytes, bytes,
+// pairs).  MANY = false is the form of one stripe, which does none of that: the
+// single call keeps the code it had before the stripe dimension (it measured
+// 0.3-0.6 us slower through the batch form; profiles/r20_heal.txt).
+template <bool MANY>
 __global__ void __launch_bounds__(SCAN_THREADS) locate_scan_kernel(const uint8_t* enc, const uint8_t* rec,
                                                                    unsigned long long* acc, uint32_t nslots,
                                                                    uint64_t S, uint32_t m, uint32_t cols, uint32_t cw,
-                                                                   uint32_t rsub, uint32_t rows_per_wg) {
+                                                                   uint32_t rsub, uint32_t rows_per_wg,
+                                                                   uint64_t bs_enc, uint64_t bs_rec, uint64_t bs_acc) {
+    if (MANY) enc += blockIdx.z * bs_enc, rec += blockIdx.z * bs_rec, acc += blockIdx.z * bs_acc;
     const uint32_t slot = threadIdx.x / cw;
     const uint32_t col = blockIdx.x * SCAN_THREADS + (threadIdx.x - slot * cw);
     if (slot >= rsub || col >= cols) return;
@@ -95,12 +105,25 @@ __global__ void __launch_bounds__(SCAN_THREADS) locate_scan_kernel(const uint8_t
 //   2 .. m - 1                        bad
 // The block is CLEAN without a dirty element, RECOVERY / ORIGINAL when every
 // dirty element names the same shard, else UNLOCATABLE.  Every entry of status,
-// shard and fix is written; the element's pairs go back to zero.
+// shard and fix is written; the element's pairs go back to zero.  The blocks
+// of all stripes are numbered through, stripe by stripe: the two halves of a
+// workgroup may belong to two stripes (an odd block count), so each half moves
+// the arrays on to its own stripe.  MANY = false: one stripe, as in the scan.
+template <bool MANY>
 __global__ void __launch_bounds__(64) locate_decide_kernel(LocateArgs a) {
     __shared__ uint32_t s_kind[2][32], s_shard[2][32];
     const uint32_t e = threadIdx.x & 31, h = threadIdx.x >> 5;
-    const uint32_t c = blockIdx.x * 2 + h;
-    const bool active = c < a.blocks;
+    const uint32_t g = blockIdx.x * 2 + h;
+    uint32_t c = g;
+    bool active = c < a.blocks;
+    if (MANY) {
+        const uint32_t st = g / a.blocks;
+        c = g - st * a.blocks;
+        active = g < a.blocks * a.nstripes;  // (below 2^31: launch_locate_decide)
+        a.enc += st * a.bs_enc, a.rec += st * a.bs_rec, a.E += st * a.bs_E, a.acc += st * a.bs_acc;
+        a.cand += st * a.bs_cand, a.status += st * a.bs_status, a.shard += st * a.bs_shard;
+        if (a.fix) a.fix += st * a.bs_fix;
+    }
     const uint64_t at = (uint64_t)c * 64 + e;  // the element's low byte within a row
     uint32_t kind = EL_CLEAN, shard = NONE, err = 0;
     if (active) {
@@ -169,11 +192,17 @@ __global__ void __launch_bounds__(64) locate_decide_kernel(LocateArgs a) {
 // lane that finds encode(E) ^ syndrome nonzero downgrades the block (the stores
 // of several such lanes carry the same values).  The first row chunk's
 // workgroup puts the candidate's block of E back to zero: E was consumed by the
-// encode before this launch.
+// encode before this launch.  Grid z is the stripe (MANY = false: one stripe).
+template <bool MANY>
 __global__ void __launch_bounds__(SCAN_THREADS) locate_confirm_kernel(LocateArgs a, uint32_t rows_per_wg) {
-    const uint32_t c = blockIdx.x;
-    const uint32_t i = a.cand[c];
+    const uint32_t c = blockIdx.x, st = MANY ? blockIdx.z : 0;
+    const uint32_t i = a.cand[st * a.bs_cand + c];
     if (i == NONE) return;
+    if (MANY) {
+        a.enc += st * a.bs_enc, a.rec += st * a.bs_rec, a.enc2 += st * a.bs_enc2, a.E += st * a.bs_E;
+        a.status += st * a.bs_status, a.shard += st * a.bs_shard;
+        if (a.fix) a.fix += st * a.bs_fix;
+    }
     if (blockIdx.y == 0 && threadIdx.x < 16) ((uint32_t*)(a.E + (uint64_t)i * a.S + (uint64_t)c * 64))[threadIdx.x] = 0;
     const uint32_t r0 = blockIdx.y * rows_per_wg;
     const uint32_t r1 = r0 + rows_per_wg < a.m ? r0 + rows_per_wg : a.m;
@@ -192,23 +221,58 @@ __global__ void __launch_bounds__(SCAN_THREADS) locate_confirm_kernel(LocateArgs
     }
 }
 
+// The heal: 16 lanes per block, one dword each, 16 blocks of one stripe per
+// workgroup (grid x), stripes over grid y (strided when there are more stripes
+// than grid rows).  A block whose final status is ORIGINAL or RECOVERY and
+// whose array is given (orig_w / rec_w, by the heal's mask) gets its fix XORed
+// into the named shard; every block is counted in the workgroup's histogram,
+// which goes to the stripe's four counters with one atomic per nonzero entry.
+__global__ void __launch_bounds__(256) locate_apply_kernel(LocateArgs a) {
+    __shared__ uint32_t s_cnt[4];
+    const uint32_t lane = threadIdx.x & 15;
+    const uint32_t c = blockIdx.x * 16 + (threadIdx.x >> 4);
+    for (uint32_t st = blockIdx.y; st < a.nstripes; st += gridDim.y) {
+        if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;
+        __syncthreads();
+        if (c < a.blocks) {
+            const uint32_t status = a.status[st * a.bs_status + c] & 3u;
+            const uint32_t i = a.shard[st * a.bs_shard + c];
+            uint8_t* dst = nullptr;
+            // (an index outside the shard counts is never followed)
+            if (status == RS16_LOCATE_ORIGINAL && a.orig_w && i < a.k)
+                dst = a.orig_w + st * a.bs_orig + (uint64_t)i * a.S;
+            else if (status == RS16_LOCATE_RECOVERY && a.rec_w && i < a.m)
+                dst = a.rec_w + st * a.bs_rec + (uint64_t)i * a.S;
+            if (dst) {
+                uint32_t* d = (uint32_t*)(dst + (uint64_t)c * 64) + lane;
+                *d ^= ((const uint32_t*)(a.fix + st * a.bs_fix + (uint64_t)c * 64))[lane];
+            }
+            if (lane == 0) atomicAdd(&s_cnt[status], 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x < 4 && s_cnt[threadIdx.x])
+            atomicAdd(&a.counts[st * a.bs_counts + threadIdx.x], s_cnt[threadIdx.x]);
+    }
+}
+
 __global__ void __launch_bounds__(256) locate_unit_kernel(uint8_t* buf, uint64_t Sc, uint32_t i0, uint32_t n,
                                                           uint32_t value) {
     const uint32_t q = blockIdx.x * 256 + threadIdx.x;
     if (q < n) buf[(uint64_t)(i0 + q) * Sc + 64 * (q >> 5) + (q & 31)] = (uint8_t)value;
 }
 
-// rows_per_wg of a launch of about SCAN_WGS workgroups, gx of them side by side,
-// each pass of a workgroup taking `step` rows and every thread at least four.
-static uint32_t chunk_rows(uint32_t m, uint32_t gx, uint32_t step) {
-    uint32_t gy = SCAN_WGS / gx ? SCAN_WGS / gx : 1;
+// rows_per_wg of a launch of about SCAN_WGS workgroups, gx of them side by side
+// (over the columns and the stripes), each pass of a workgroup taking `step`
+// rows and every thread at least four.
+static uint32_t chunk_rows(uint32_t m, uint64_t gx, uint32_t step) {
+    uint32_t gy = SCAN_WGS / gx ? (uint32_t)(SCAN_WGS / gx) : 1;
     const uint32_t most = (m + 4 * step - 1) / (4 * step);
     if (gy > most) gy = most;
     const uint32_t rows = (m + gy - 1) / gy;
     return (rows + step - 1) / step * step;
 }
 
-LocateScanShape locate_scan_shape(uint64_t S, uint32_t m) {
+LocateScanShape locate_scan_shape(uint64_t S, uint32_t m, uint32_t nstripes) {
     LocateScanShape sh{};
     const uint64_t cols = S / 8;
     if (cols >= SCAN_THREADS) {
@@ -216,38 +280,61 @@ LocateScanShape locate_scan_shape(uint64_t S, uint32_t m) {
     } else {
         sh.cw = (uint32_t)cols, sh.rsub = SCAN_THREADS / (uint32_t)cols, sh.gx = 1;
     }
-    sh.rows_per_wg = chunk_rows(m, sh.gx, sh.rsub);
+    sh.rows_per_wg = chunk_rows(m, (uint64_t)sh.gx * nstripes, sh.rsub);
     sh.gy = (m + sh.rows_per_wg - 1) / sh.rows_per_wg;
     return sh;
 }
 
+// what every launch asks of the stripe dimension: grid y and z stop at 65535,
+// and a stripe's rows of enc and rec lie inside its stride
+static bool stripes_ok(const LocateArgs& a) {
+    return a.nstripes >= 1 && a.nstripes <= 65535 && a.bs_enc >= a.m * a.S && a.bs_rec >= a.m * a.S;
+}
+
 hipError_t launch_locate_scan(const LocateArgs& a, hipStream_t s) {
     if (!a.enc || !a.rec || !a.acc || a.nslots == 0 || (a.nslots & (a.nslots - 1)) || a.S == 0 || a.S % 64 ||
-        a.m == 0 || a.m >= 65536)
+        a.m == 0 || a.m >= 65536 || !stripes_ok(a) || a.bs_acc < a.nslots * (a.S / 2))
         return hipErrorInvalidValue;
-    const LocateScanShape sh = locate_scan_shape(a.S, a.m);
-    hipLaunchKernelGGL(locate_scan_kernel, dim3(sh.gx, sh.gy), dim3(SCAN_THREADS), 0, s, a.enc, a.rec, a.acc, a.nslots,
-                       a.S, a.m, (uint32_t)(a.S / 8), sh.cw, sh.rsub, sh.rows_per_wg);
+    const LocateScanShape sh = locate_scan_shape(a.S, a.m, a.nstripes);
+    hipLaunchKernelGGL(a.nstripes > 1 ? locate_scan_kernel<true> : locate_scan_kernel<false>,
+                       dim3(sh.gx, sh.gy, a.nstripes), dim3(SCAN_THREADS), 0, s, a.enc, a.rec, a.acc, a.nslots, a.S, a.m,
+                       (uint32_t)(a.S / 8), sh.cw, sh.rsub, sh.rows_per_wg, a.bs_enc, a.bs_rec, a.bs_acc);
     return hipGetLastError();
 }
 
 hipError_t launch_locate_decide(const LocateArgs& a, hipStream_t s) {
     if (!a.enc || !a.rec || !a.E || !a.acc || a.nslots == 0 || a.nslots > LOCATE_MAX_SLOTS || !a.cand || !a.log || !a.exp || !a.log_m0 || !a.ratio ||
-        !a.status || !a.shard || a.m < 2 || a.blocks == 0 || a.blocks != a.S / 64)
+        !a.status || !a.shard || a.m < 2 || a.blocks == 0 || a.blocks != a.S / 64 || !stripes_ok(a) ||
+        a.bs_acc < a.nslots * (a.S / 2) || a.bs_E < a.k * a.S || a.bs_cand < a.blocks || a.bs_status < a.blocks ||
+        a.bs_shard < a.blocks || (a.fix && a.bs_fix < a.S))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(locate_decide_kernel, dim3((a.blocks + 1) / 2), dim3(64), 0, s, a);
+    const uint64_t all = (uint64_t)a.blocks * a.nstripes;  // (numbered in 32 bits by the kernel)
+    if (all > 0x7FFFFFFFu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(a.nstripes > 1 ? locate_decide_kernel<true> : locate_decide_kernel<false>,
+                       dim3((uint32_t)((all + 1) / 2)), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_locate_confirm(const LocateArgs& a, hipStream_t s) {
     if (!a.enc || !a.rec || !a.enc2 || !a.E || !a.cand || !a.status || !a.shard || a.blocks == 0 ||
-        a.blocks != a.S / 64)
+        a.blocks != a.S / 64 || !stripes_ok(a) || a.bs_enc2 < a.m * a.S)
         return hipErrorInvalidValue;
     const uint32_t step = SCAN_THREADS / 8;
     const uint32_t gx = a.blocks;
-    const uint32_t rows_per_wg = chunk_rows(a.m, gx < SCAN_WGS ? gx : SCAN_WGS, step);
-    hipLaunchKernelGGL(locate_confirm_kernel, dim3(gx, (a.m + rows_per_wg - 1) / rows_per_wg), dim3(SCAN_THREADS), 0, s,
-                       a, rows_per_wg);
+    const uint64_t wide = (uint64_t)gx * a.nstripes;
+    const uint32_t rows_per_wg = chunk_rows(a.m, wide < SCAN_WGS ? wide : SCAN_WGS, step);
+    hipLaunchKernelGGL(a.nstripes > 1 ? locate_confirm_kernel<true> : locate_confirm_kernel<false>,
+                       dim3(gx, (a.m + rows_per_wg - 1) / rows_per_wg, a.nstripes), dim3(SCAN_THREADS), 0, s, a,
+                       rows_per_wg);
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_apply(const LocateArgs& a, hipStream_t s) {
+    if (!a.status || !a.shard || !a.fix || !a.counts || (!a.orig_w && !a.rec_w) || a.blocks == 0 ||
+        a.blocks != a.S / 64 || !stripes_ok(a) || a.bs_status < a.blocks || a.bs_shard < a.blocks || a.bs_fix < a.S ||
+        a.bs_counts < 4 || (a.orig_w && a.bs_orig < a.k * a.S))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(locate_apply_kernel, dim3((a.blocks + 15) / 16, a.nstripes), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -37,6 +37,8 @@ __all__ = [
     "verify_device", "verify_device_batch", "verify", "verify_path",
     "LocatePlan", "locate_device", "locate", "LOCATE_CLEAN", "LOCATE_ORIGINAL", "LOCATE_RECOVERY",
     "LOCATE_UNLOCATABLE", "LOCATE_NO_SHARD",
+    "locate_device_batch", "heal_device", "heal_device_batch", "heal", "HEAL_ORIGINAL", "HEAL_RECOVERY",
+    "locate_scan_shape",
     "UpdatePlan", "update_recovery_device", "UPDATE_MAX_SHARDS",
     "encode_host_multi", "decode_host_multi", "Comm", "column_slice", "scatter_columns", "gather_columns",
 ]
@@ -877,6 +879,7 @@ def verify(original_count: int, recovery_count: int, original, recovery, checked
 
 LOCATE_CLEAN, LOCATE_ORIGINAL, LOCATE_RECOVERY, LOCATE_UNLOCATABLE = 0, 1, 2, 3  # RS16_LOCATE_*
 LOCATE_NO_SHARD = 0xFFFFFFFF
+HEAL_ORIGINAL, HEAL_RECOVERY = 1, 2  # RS16_HEAL_*: which arrays a heal may write
 
 
 class LocatePlan:
@@ -912,6 +915,42 @@ class LocatePlan:
                                         _dev_ptr(d_block_status), _dev_ptr(d_block_shard), _dev_ptr(d_block_fix),
                                         stream, C.byref(self._err)), self._err)
 
+    def locate_batch(self, shard_bytes, nstripes, d_original, original_stride, d_recovery, recovery_stride,
+                     d_block_status, status_stride, d_block_shard, shard_stride, d_block_fix=None, fix_stride=0,
+                     stream=None):
+        """rs16_locate_device_batch: locate() for nstripes stripes; stripe i's
+        arrays at + i * original_stride / recovery_stride (bytes), its outputs at
+        + i * status_stride (bytes, >= B), shard_stride (uint32 ENTRIES, >= B) and
+        fix_stride (bytes, >= 64 B)."""
+        _check(lib().rs16_locate_device_batch(self.h, shard_bytes, nstripes, _dev_ptr(d_original), original_stride,
+                                              _dev_ptr(d_recovery), recovery_stride, _dev_ptr(d_block_status),
+                                              status_stride, _dev_ptr(d_block_shard), shard_stride,
+                                              _dev_ptr(d_block_fix), fix_stride, stream, C.byref(self._err)),
+               self._err)
+
+    def heal(self, shard_bytes, d_original, d_recovery, d_counts, heal_mask=HEAL_ORIGINAL | HEAL_RECOVERY,
+             d_block_status=None, d_block_shard=None, stream=None):
+        """rs16_heal_device: locate, then XOR each located block's fix into the
+        named shard in place -- originals with HEAL_ORIGINAL in heal_mask,
+        recovery shards with HEAL_RECOVERY.  d_counts (4 uint32) gets the number
+        of blocks per final LOCATE_* status; d_block_status / d_block_shard, if
+        given, report what was found before the fix."""
+        _check(lib().rs16_heal_device(self.h, shard_bytes, _dev_ptr(d_original), _dev_ptr(d_recovery), heal_mask,
+                                      _dev_ptr(d_block_status), _dev_ptr(d_block_shard), _dev_ptr(d_counts), stream,
+                                      C.byref(self._err)), self._err)
+
+    def heal_batch(self, shard_bytes, nstripes, d_original, original_stride, d_recovery, recovery_stride, d_counts,
+                   counts_stride=4, heal_mask=HEAL_ORIGINAL | HEAL_RECOVERY, d_block_status=None, status_stride=0,
+                   d_block_shard=None, shard_stride=0, stream=None):
+        """rs16_heal_device_batch: heal() for nstripes stripes; stripe i's counts
+        at + i * counts_stride (uint32 ENTRIES, >= 4), the other strides as
+        locate_batch takes them."""
+        _check(lib().rs16_heal_device_batch(self.h, shard_bytes, nstripes, _dev_ptr(d_original), original_stride,
+                                            _dev_ptr(d_recovery), recovery_stride, heal_mask,
+                                            _dev_ptr(d_block_status), status_stride, _dev_ptr(d_block_shard),
+                                            shard_stride, _dev_ptr(d_counts), counts_stride, stream,
+                                            C.byref(self._err)), self._err)
+
     def close(self):
         # Safe after the engine is gone: rs16_engine_free detaches its plans,
         # and freeing a detached one only frees host memory.
@@ -937,6 +976,77 @@ def locate_device(original_count, recovery_count, shard_bytes, d_original, d_rec
         plan.engine.synchronize(stream)
     finally:
         plan.close()
+
+
+def _with_plan(original_count, recovery_count, rate, engine, stream, call):
+    """One call through a plan built for it (and waited for: the plan's tables
+    must outlive the launches)."""
+    plan = LocatePlan(original_count, recovery_count, rate, engine)
+    try:
+        call(plan)
+        plan.engine.synchronize(stream)
+    finally:
+        plan.close()
+
+
+def locate_device_batch(original_count, recovery_count, shard_bytes, nstripes, d_original, original_stride,
+                        d_recovery, recovery_stride, d_block_status, status_stride, d_block_shard, shard_stride,
+                        d_block_fix=None, fix_stride=0, rate="default", stream=None,
+                        engine: Optional[Engine] = None):
+    """One rs16_locate_device_batch call through a plan built for it (see locate_device)."""
+    _with_plan(original_count, recovery_count, rate, engine, stream, lambda plan: plan.locate_batch(
+        shard_bytes, nstripes, d_original, original_stride, d_recovery, recovery_stride, d_block_status,
+        status_stride, d_block_shard, shard_stride, d_block_fix, fix_stride, stream))
+
+
+def heal_device(original_count, recovery_count, shard_bytes, d_original, d_recovery, d_counts,
+                heal_mask=HEAL_ORIGINAL | HEAL_RECOVERY, d_block_status=None, d_block_shard=None, rate="default",
+                stream=None, engine: Optional[Engine] = None):
+    """One rs16_heal_device call through a plan built for it (see locate_device)."""
+    _with_plan(original_count, recovery_count, rate, engine, stream, lambda plan: plan.heal(
+        shard_bytes, d_original, d_recovery, d_counts, heal_mask, d_block_status, d_block_shard, stream))
+
+
+def heal_device_batch(original_count, recovery_count, shard_bytes, nstripes, d_original, original_stride,
+                      d_recovery, recovery_stride, d_counts, counts_stride=4,
+                      heal_mask=HEAL_ORIGINAL | HEAL_RECOVERY, d_block_status=None, status_stride=0,
+                      d_block_shard=None, shard_stride=0, rate="default", stream=None,
+                      engine: Optional[Engine] = None):
+    """One rs16_heal_device_batch call through a plan built for it (see locate_device)."""
+    _with_plan(original_count, recovery_count, rate, engine, stream, lambda plan: plan.heal_batch(
+        shard_bytes, nstripes, d_original, original_stride, d_recovery, recovery_stride, d_counts, counts_stride,
+        heal_mask, d_block_status, status_stride, d_block_shard, shard_stride, stream))
+
+
+def heal(original_count: int, recovery_count: int, original, recovery, heal_mask=HEAL_ORIGINAL | HEAL_RECOVERY,
+         rate="default", engine: Optional[Engine] = None):
+    """Heal one stripe held on the host: `original` and `recovery` are sequences
+    of equal-length shards (bytes or uint8 arrays).  Uploads, runs
+    rs16_heal_device and returns (healed originals, healed recovery, status,
+    shard, counts): two (count, shard_bytes) uint8 arrays, then per column block
+    the uint8 LOCATE_* status and uint32 shard found before the fix, and the four
+    uint32 block counts by final status (counts[LOCATE_UNLOCATABLE] == 0: the
+    healed stripe is consistent)."""
+    from .device import DeviceArray
+
+    eng = engine or default_engine()
+    shard_bytes, d_o, d_r = _upload_stripe(eng, original_count, recovery_count, original, recovery)
+    blocks = shard_bytes // 64
+    d_status, d_shard, d_counts = DeviceArray(eng, blocks), DeviceArray(eng, blocks * 4), DeviceArray(eng, 16)
+    heal_device(original_count, recovery_count, shard_bytes, d_o, d_r, d_counts, heal_mask, d_status, d_shard, rate,
+                engine=eng)
+    return (d_o.download(shape=(original_count, shard_bytes)), d_r.download(shape=(recovery_count, shard_bytes)),
+            d_status.download()[:blocks], d_shard.download(np.uint32)[:blocks], d_counts.download(np.uint32)[:4])
+
+
+def locate_scan_shape(shard_bytes, recovery_count, nstripes=1):
+    """rs16_host_locate_scan_shape: (cw, rsub, gx, gy, rows_per_wg) of the
+    locate's scan launch, None for sizes no locate takes; host arithmetic, no
+    device."""
+    out = (C.c_uint32 * 5)()
+    if lib().rs16_host_locate_scan_shape(shard_bytes, recovery_count, nstripes, out):
+        return None
+    return tuple(out)
 
 
 def locate(original_count: int, recovery_count: int, original, recovery, rate="default",

@@ -126,6 +126,10 @@ SIGNATURES = {
     "rs16_locate_plan_free": (None, [_p]),
     "rs16_locate_plan_rows": (_i, [_p, C.POINTER(C.c_uint16), _e]),
     "rs16_locate_device": (_i, [_p, _sz, _p, _p, _p, _p, _p, _p, _e]),
+    "rs16_locate_device_batch": (_i, [_p, _sz, _sz, _p, _sz, _p, _sz, _p, _sz, _p, _sz, _p, _sz, _p, _e]),
+    "rs16_heal_device": (_i, [_p, _sz, _p, _p, _i, _p, _p, _p, _p, _e]),
+    "rs16_heal_device_batch": (_i, [_p, _sz, _sz, _p, _sz, _p, _sz, _i, _p, _sz, _p, _sz, _p, _sz, _p, _e]),
+    "rs16_host_locate_scan_shape": (_i, [_sz, _sz, _sz, C.POINTER(_u32)]),
     "rs16_decode_check": (_i, [_p, _p, _e]),
     "rs16_device_alloc": (_p, [_p, _sz, _e]),
     "rs16_device_free": (None, [_p, _p]),
