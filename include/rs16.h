@@ -39,11 +39,17 @@
  *    share the scratch concurrently (calls on one engine serialise; use one
  *    engine per stream for concurrent codecs).
  *  - rs16_engine_free waits for the engine's work (its own streams and the
- *    last caller stream it ran on, through an event), releases the work space of
- *    every encoder/decoder created on the engine and detaches them: a
- *    detached encoder/decoder fails every call with RS16_INVALID_ARGUMENT,
- *    and rs16_{en,de}coder_free of it only frees its host memory (safe in
- *    any order at process exit).
+ *    last caller stream it ran on, through an event), releases what every
+ *    object created on the engine holds on the device and in page-locked
+ *    memory -- rs16_encoder, rs16_decoder, rs16_update_plan,
+ *    rs16_locate_plan, rs16_comm (whose RCCL communicator it destroys) -- and
+ *    detaches them.  These objects may outlive their engine: a detached one
+ *    fails every call with RS16_INVALID_ARGUMENT (rs16_comm_rank / _size,
+ *    which return no status: -RS16_INVALID_ARGUMENT), and its free() only
+ *    frees its host memory (safe in any order at process exit).  Device
+ *    memory, page-locked memory and streams from rs16_device_alloc /
+ *    rs16_host_alloc / rs16_stream_create are the caller's: free them
+ *    while the engine is alive.
  */
 #ifndef RS16_H
 #define RS16_H
@@ -917,7 +923,8 @@ int rs16_decode_host_multi(rs16_engine* const* engines, int n, size_t original_c
  * calls take this process's communicators (n of them, ranks in any order)
  * with one buffer per communicator: d_full is used on the root only,
  * d_slice on every rank.  Asynchronous on `stream` (n == 1) or on each
- * engine's stream. */
+ * engine's stream.  Like an encoder, a communicator is detached by
+ * rs16_engine_free ("Conventions"). */
 typedef struct rs16_comm rs16_comm;
 int rs16_comm_unique_id(void* id128, rs16_error* err);
 rs16_comm* rs16_comm_new(rs16_engine* eng, int nranks, int rank, const void* id128, rs16_error* err);

@@ -400,96 +400,70 @@ extern "C" rs16_engine* rs16_engine_new_ex(int device, int flags, rs16_error* er
     if (!e) return set_error(err, RS16_INVALID_ARGUMENT), nullptr;
     e->device = device;
     e->diag = g_default_diag.load();
+    e->flags = flags;
+    if (e->upload_tables(err)) {
+        delete e;
+        return nullptr;
+    }
+    set_error(err, RS16_OK);
+    return e;
+}
+
+// The engine's stream and the tables every engine has.
+int rs16_engine::upload_tables(rs16_error* err) {
     const HostTables& t = host_tables();
-    auto fail = [&](hipError_t x) {
-        hip_fail(err, x);
-        rs16_engine_free(e);
-        return (rs16_engine*)nullptr;
-    };
-    if ((he = hipSetDevice(device)) != hipSuccess) return fail(he);
+    RS16_HIP(hipSetDevice(device));
     if (flags & RS16_ENGINE_OWN_QUEUE) {
         // A stream with a CU mask gets a hardware queue of its own (the HIP
         // runtime shares its GPU_MAX_HW_QUEUES queues only among unmasked
         // streams); the mask enables every CU.
         int cus = 0;
-        if ((he = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device)) != hipSuccess) return fail(he);
+        RS16_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
         std::vector<uint32_t> mask(((size_t)cus + 31) / 32, 0xFFFFFFFFu);
         if (cus % 32) mask.back() = (1u << (cus % 32)) - 1;
-        if ((he = hipExtStreamCreateWithCUMask(&e->stream, (uint32_t)mask.size(), mask.data())) != hipSuccess)
-            return fail(he);
-    } else if ((he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking)) != hipSuccess) {
-        return fail(he);
+        hipStream_t masked = nullptr;
+        RS16_HIP(hipExtStreamCreateWithCUMask(&masked, (uint32_t)mask.size(), mask.data()));
+        stream.adopt(masked);
+    } else {
+        RS16_HIP(stream.get());
     }
-    e->flags = flags;
-    if ((he = hipMalloc(&e->d_skew_tab, (size_t)GF_ORDER * TAB_DWORDS * 4)) != hipSuccess) return fail(he);
-    if ((he = hipMalloc(&e->d_skew_tab_tower, (size_t)GF_ORDER * TAB_DWORDS * 4)) != hipSuccess) return fail(he);
-    if ((he = hipMalloc(&e->d_mul_tab, t.mul_tab.size() * 4)) != hipSuccess) return fail(he);
-    if ((he = hipMalloc(&e->d_log_walsh, GF_ORDER * 2)) != hipSuccess) return fail(he);
-    if ((he = hipMalloc(&e->d_zero_sink, RS16_ZERO_BYTES)) != hipSuccess) return fail(he);
-    if ((he = hipMemset(e->d_zero_sink, 0, RS16_ZERO_BYTES)) != hipSuccess) return fail(he);
-    if ((he = hipMemcpy(e->d_skew_tab, t.skew_tab.data(), t.skew_tab.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(he);
-    if ((he = hipMemcpy(e->d_skew_tab_tower, t.skew_tab_tower.data(), t.skew_tab_tower.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(he);
-    if ((he = hipMemcpy(e->d_mul_tab, t.mul_tab.data(), t.mul_tab.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(he);
-    if ((he = hipMemcpy(e->d_log_walsh, t.log_walsh.data(), GF_ORDER * 2, hipMemcpyHostToDevice)) != hipSuccess) return fail(he);
-    set_error(err, RS16_OK);
-    return e;
+    RS16_HIP(d_skew_tab.reserve((size_t)GF_ORDER * TAB_DWORDS * 4));
+    RS16_HIP(d_skew_tab_tower.reserve((size_t)GF_ORDER * TAB_DWORDS * 4));
+    RS16_HIP(d_mul_tab.reserve(t.mul_tab.size() * 4));
+    RS16_HIP(d_log_walsh.reserve(GF_ORDER * 2));
+    RS16_HIP(d_zero_sink.reserve(RS16_ZERO_BYTES));
+    RS16_HIP(hipMemset(d_zero_sink.p, 0, RS16_ZERO_BYTES));
+    RS16_HIP(hipMemcpy(d_skew_tab.p, t.skew_tab.data(), t.skew_tab.size() * 4, hipMemcpyHostToDevice));
+    RS16_HIP(hipMemcpy(d_skew_tab_tower.p, t.skew_tab_tower.data(), t.skew_tab_tower.size() * 4, hipMemcpyHostToDevice));
+    RS16_HIP(hipMemcpy(d_mul_tab.p, t.mul_tab.data(), t.mul_tab.size() * 4, hipMemcpyHostToDevice));
+    RS16_HIP(hipMemcpy(d_log_walsh.p, t.log_walsh.data(), GF_ORDER * 2, hipMemcpyHostToDevice));
+    return RS16_OK;
 }
 
-extern "C" void rs16_engine_free(rs16_engine* e) {
-    if (!e) return;
-    (void)hipSetDevice(e->device);
+rs16_engine::~rs16_engine() {
+    (void)hipSetDevice(device);
     // The streams this engine's work can be on: its own, the slice and
     // host-pipeline streams, and the last caller stream that used its scratch
     // (through order_ev).  Other engines and unrelated work are not waited for.
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (int j = 0; j < rs16_engine::MAX_SLICES; j++)
-        if (e->sl_own[j]) (void)hipStreamSynchronize(e->sl_own[j]);
-    for (auto& sl : e->hslot)
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (auto& s : sl_own)
+        if (s) (void)hipStreamSynchronize(s);
+    for (auto& sl : hslot)
         if (sl.s) (void)hipStreamSynchronize(sl.s);
-    if (e->last == rs16_engine::LAST_CALLER && e->order_ev) (void)hipEventSynchronize(e->order_ev);
-    for (rs16_encoder* c : e->encoders) detach(c);
-    for (rs16_decoder* c : e->decoders) detach(c);
-    for (rs16_update_plan* c : e->update_plans) detach(c);
-    for (rs16_locate_plan* c : e->locate_plans) detach(c);
-    e->ws_z.release();
-    e->ws_u.release();
-    e->ws_fd.release();
-    for (auto& b : e->mid_tab) b.release();
-    e->ev_main.release();
-    for (auto& l : e->ev_lane) l.release();
-    e->ws_flags.release();
-    e->ws_rep.release();
-    e->ws_loc_e.release(), e->ws_loc_rep.release(), e->ws_loc_acc.release(), e->ws_loc_cand.release(), e->ws_loc_fix.release();
-    e->hp_flags.release();
-    for (auto& sl : e->hslot) {
-        if (sl.s) (void)hipStreamSynchronize(sl.s), (void)hipStreamDestroy(sl.s);
-        sl.orig.release(), sl.rec.release(), sl.z.release(), sl.u.release();
-    }
-    e->hflags.release();
-    if (e->hev) (void)hipEventDestroy(e->hev);
-    if (e->prep_ev) (void)hipEventDestroy(e->prep_ev);
-    for (auto& ev : e->hp_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (e->hp_off) (void)hipEventDestroy(e->hp_off);
-    if (e->order_ev) (void)hipEventDestroy(e->order_ev);
-    for (int j = 0; j < rs16_engine::MAX_SLICES; j++) {
-        if (e->sl_own[j]) (void)hipStreamDestroy(e->sl_own[j]);
-        if (e->sl_join[j]) (void)hipEventDestroy(e->sl_join[j]);
-    }
-    if (e->sl_fork) (void)hipEventDestroy(e->sl_fork);
-    if (e->d_skew_tab) (void)hipFree(e->d_skew_tab);
-    if (e->d_skew_tab_tower) (void)hipFree(e->d_skew_tab_tower);
-    if (e->d_mul_tab) (void)hipFree(e->d_mul_tab);
-    if (e->d_col_img) (void)hipFree(e->d_col_img);
-    if (e->d_col_v) (void)hipFree(e->d_col_v);
-    if (e->d_log_walsh) (void)hipFree(e->d_log_walsh);
-    if (e->d_zero_sink) (void)hipFree(e->d_zero_sink);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
+    if (last == LAST_CALLER && order_ev) (void)hipEventSynchronize(order_ev);
+    for (rs16_encoder* c : encoders) detach(c);
+    for (rs16_decoder* c : decoders) detach(c);
+    for (rs16_update_plan* c : update_plans) detach(c);
+    for (rs16_locate_plan* c : locate_plans) detach(c);
+    for (rs16_comm* c : comms) detach(c);
+}
+
+extern "C" void rs16_engine_free(rs16_engine* e) {
+    if (e) delete e;  // (~rs16_engine)
 }
 
 extern "C" int rs16_engine_device(const rs16_engine* e) { return e->device; }
-extern "C" void* rs16_engine_stream(const rs16_engine* e) { return (void*)e->stream; }
+extern "C" void* rs16_engine_stream(const rs16_engine* e) { return (void*)e->stream.s; }
 extern "C" int rs16_engine_synchronize(rs16_engine* e, void* stream, rs16_error* err) {
     if (int rc = e->activate(err)) return rc;
     RS16_HIP(hipStreamSynchronize(e->pick(stream)));
@@ -548,14 +522,14 @@ extern "C" int rs16_engine_eval_poly(rs16_engine* e, uint16_t* d, size_t trunc, 
     if (int rc = e->order(e->pick(stream), err)) return rc;
     if (int rc = e->guard_eval(e->pick(stream), false, err)) return rc;
     RS16_HIP(e->ev_main.work32.reserve(GF_ORDER * 4));
-    RS16_HIP(launch_eval_poly_u16(d, (uint32_t*)e->ev_main.work32.p, e->d_log_walsh, e->pick(stream)));
+    RS16_HIP(launch_eval_poly_u16(d, (uint32_t*)e->ev_main.work32.p, e->d_log_walsh.as<uint16_t>(), e->pick(stream)));
     if (int rc = e->scratch_done(e->pick(stream), err)) return rc;
     return set_error(err, RS16_OK);
 }
 extern "C" int rs16_engine_mul(rs16_engine* e, void* x, size_t bytes, uint16_t log_m, void* stream, rs16_error* err) {
     if ((bytes & 63) || !shard_aligned(x)) return set_error(err, RS16_INVALID_ARGUMENT);
     if (int rc = e->activate(err)) return rc;
-    RS16_HIP(launch_mul((uint8_t*)x, bytes, log_m, e->d_mul_tab, e->pick(stream)));
+    RS16_HIP(launch_mul((uint8_t*)x, bytes, log_m, e->d_mul_tab.as<uint32_t>(), e->pick(stream)));
     return set_error(err, RS16_OK);
 }
 extern "C" int rs16_engine_xor(rs16_engine* e, void* x, const void* y, size_t bytes, void* stream, rs16_error* err) {

@@ -31,12 +31,20 @@ inline int begin_ordered(rs16_engine* e, void* stream, hipStream_t* s, rs16_erro
 }
 
 // Objects created on an engine (rs16_engine::encoders / decoders /
-// update_plans / locate_plans): detach releases the object's device memory and clears its
-// engine; the object's free() forgets it in its engine's list.
-void detach(rs16_encoder* enc);
-void detach(rs16_decoder* dec);
-void detach(rs16_update_plan* plan);
-void detach(rs16_locate_plan* plan);
+// update_plans / locate_plans / comms) keep what they hold on the device and in
+// page-locked memory in one member, `dev`: detach empties it (the holders free
+// what they own; the engine's device is current, the object's work done) and
+// clears the object's engine; the object's free() forgets it in its engine's list.
+template <class T> void detach(T* x) {
+    x->dev = {};
+    x->eng = nullptr;
+}
+// (instantiated in the unit that defines the type: the engine's destructor sees none of them whole)
+extern template void detach(rs16_encoder*);
+extern template void detach(rs16_decoder*);
+extern template void detach(rs16_update_plan*);
+extern template void detach(rs16_locate_plan*);
+void detach(rs16_comm* comm);  // first destroys its RCCL communicator (rs16_comm.cpp)
 template <class V, class T> void forget(V& v, T* x) { v.erase(std::remove(v.begin(), v.end(), x), v.end()); }
 template <class T> void free_attached(T* x, std::vector<T*> rs16_engine::*list) {
     if (!x) return;

@@ -26,12 +26,12 @@ template <class C, class Fetch>
 static const void* result_host(C* c, const void* on_device, size_t index, Fetch fetch, rs16_error* err) {
     if (!on_device) return set_error(err, RS16_OK), nullptr;
     // (the common case -- rows already copied back -- makes no HIP call)
-    if (!c->out_on_host || c->out_done.busy) {
+    if (!c->out_on_host || c->dev.out_done.busy) {
         if (c->eng->activate(err) || fetch(c, err)) return nullptr;
-        if (hipError_t he = c->out_done.wait()) return hip_fail(err, he), nullptr;
+        if (hipError_t he = c->dev.out_done.wait()) return hip_fail(err, he), nullptr;
     }
     set_error(err, RS16_OK);
-    return (const uint8_t*)c->h_out.p + index * c->S;
+    return (const uint8_t*)c->dev.h_out.p + index * c->S;
 }
 template <class C, class Fetch>
 static int result_copy(C* c, const void* on_device, size_t index, void* dst, size_t len, Fetch fetch,
@@ -57,27 +57,21 @@ struct rs16_encoder {
     // that out at compile time (src/rate.rs:157-166), here it is an error.
     bool encoded = false;
     size_t k = 0, m = 0, S = 0, work_count = 0, received = 0;
-    DevBuf work;
     // Host staging: h_in holds the rows added from host memory (row = the
     // shard's position, as the reference's work buffer); rows [run0,
     // received) are there but not yet copied to `work`.  h_out receives the
     // recovery rows.  in_done: the last H2D out of h_in (h_in may be
     // rewritten once it completed); out_done: the D2H into h_out.
-    HostBuf h_in, h_out;
+    struct Dev {
+        DevBuf work;
+        HostBuf h_in, h_out;
+        Pending in_done, out_done;
+    } dev;
     size_t run0 = 0;
     bool host_round = false;  // a shard of this round came from host memory
     bool out_on_host = false;  // the D2H of this round's recovery rows is issued
-    Pending in_done, out_done;
 };
-
-void rs16::detach(rs16_encoder* enc) {
-    enc->work.release();
-    enc->h_in.release();
-    enc->h_out.release();
-    enc->in_done.release();
-    enc->out_done.release();
-    enc->eng = nullptr;
-}
+template void rs16::detach(rs16_encoder*);
 
 static void encoder_new_round(rs16_encoder* enc) {
     enc->received = 0;
@@ -93,7 +87,7 @@ extern "C" int rs16_encoder_reset(rs16_encoder* enc, size_t k, size_t m, size_t 
     if (int rc = resolve_rate(enc->rate_kind, k, m, S, &high, err)) return rc;
     const size_t wc = rs16_encoder_work_count(high, k, m);
     if (int rc = enc->eng->activate(err)) return rc;
-    RS16_HIP(enc->work.reserve(wc * S));
+    RS16_HIP(enc->dev.work.reserve(wc * S));
     enc->high = high;
     enc->k = k;
     enc->m = m;
@@ -121,7 +115,7 @@ extern "C" void rs16_encoder_free(rs16_encoder* enc) { free_attached(enc, &rs16_
 static int encoder_stream(rs16_encoder* enc, size_t upto, rs16_error* err) {
     if (upto <= enc->run0) return RS16_OK;
     const size_t S = enc->S;
-    RS16_HIP(hipMemcpyAsync((uint8_t*)enc->work.p + enc->run0 * S, (const uint8_t*)enc->h_in.p + enc->run0 * S,
+    RS16_HIP(hipMemcpyAsync((uint8_t*)enc->dev.work.p + enc->run0 * S, (const uint8_t*)enc->dev.h_in.p + enc->run0 * S,
                             (upto - enc->run0) * S, hipMemcpyHostToDevice, enc->eng->stream));
     enc->run0 = upto;
     return RS16_OK;
@@ -134,15 +128,15 @@ static int encoder_add(rs16_encoder* enc, const void* shard, size_t len, bool de
     if (device) {
         if (int rc = enc->eng->activate(err)) return rc;
         if (int rc = encoder_stream(enc, r, err)) return rc;  // (host rows before it)
-        RS16_HIP(hipMemcpyAsync((uint8_t*)enc->work.p + r * S, shard, len, hipMemcpyDeviceToDevice, enc->eng->stream));
+        RS16_HIP(hipMemcpyAsync((uint8_t*)enc->dev.work.p + r * S, shard, len, hipMemcpyDeviceToDevice, enc->eng->stream));
         enc->run0 = r + 1;
     } else {
         if (r == 0) {
             // the previous round's copies out of h_in must be done
-            RS16_HIP(enc->in_done.wait());
-            RS16_HIP(enc->h_in.reserve(enc->k * S));
+            RS16_HIP(enc->dev.in_done.wait());
+            RS16_HIP(enc->dev.h_in.reserve(enc->k * S));
         }
-        memcpy((uint8_t*)enc->h_in.p + r * S, shard, len);
+        memcpy((uint8_t*)enc->dev.h_in.p + r * S, shard, len);
         enc->host_round = true;
         if ((r + 1 - enc->run0) * S >= STREAM_BYTES) {
             if (int rc = enc->eng->activate(err)) return rc;
@@ -161,9 +155,9 @@ extern "C" int rs16_encoder_add_original_shard_device(rs16_encoder* enc, const v
 // D2H of every recovery row into h_out (once per round).
 static int encoder_fetch(rs16_encoder* enc, rs16_error* err) {
     if (enc->out_on_host) return RS16_OK;
-    RS16_HIP(enc->h_out.reserve(enc->m * enc->S));
-    RS16_HIP(hipMemcpyAsync(enc->h_out.p, enc->work.p, enc->m * enc->S, hipMemcpyDeviceToHost, enc->eng->stream));
-    RS16_HIP(enc->out_done.record(enc->eng->stream));
+    RS16_HIP(enc->dev.h_out.reserve(enc->m * enc->S));
+    RS16_HIP(hipMemcpyAsync(enc->dev.h_out.p, enc->dev.work.p, enc->m * enc->S, hipMemcpyDeviceToHost, enc->eng->stream));
+    RS16_HIP(enc->dev.out_done.record(enc->eng->stream));
     enc->out_on_host = true;
     return RS16_OK;
 }
@@ -175,9 +169,9 @@ extern "C" int rs16_encoder_encode(rs16_encoder* enc, rs16_error* err) {
     if (int rc = e->order(e->stream, err)) return rc;
     if (enc->host_round) {
         if (int rc = encoder_stream(enc, enc->received, err)) return rc;
-        RS16_HIP(enc->in_done.record(e->stream));
+        RS16_HIP(enc->dev.in_done.record(e->stream));
     }
-    uint8_t* w = (uint8_t*)enc->work.p;
+    uint8_t* w = (uint8_t*)enc->dev.work.p;
     uint8_t* U;
     if (int rc = engine_u(e, enc->high, enc->k, enc->S, &U, err)) return rc;
     if (int rc = encode_dev(e, enc->high, enc->k, enc->m, enc->S, w, w, w, U, e->stream, err)) return rc;
@@ -189,7 +183,7 @@ extern "C" int rs16_encoder_encode(rs16_encoder* enc, rs16_error* err) {
     return set_error(err, RS16_OK);
 }
 extern "C" const void* rs16_encoder_recovery_device(rs16_encoder* enc, size_t index) {
-    return enc->eng && enc->encoded && index < enc->m ? (const uint8_t*)enc->work.p + index * enc->S : nullptr;
+    return enc->eng && enc->encoded && index < enc->m ? (const uint8_t*)enc->dev.work.p + index * enc->S : nullptr;
 }
 extern "C" const void* rs16_encoder_recovery(rs16_encoder* enc, size_t index, rs16_error* err) {
     return result_host(enc, rs16_encoder_recovery_device(enc, index), index, encoder_fetch, err);
@@ -214,30 +208,21 @@ struct rs16_decoder {
     size_t k = 0, m = 0, S = 0, work_count = 0;
     size_t orig_base = 0, rec_base = 0, orig_recv = 0, rec_recv = 0;
     std::vector<uint8_t> received;  // by work position
-    DevBuf work, ubuf, flags;       // work = shards (z), ubuf = second work array (u)
     // Host staging: h_img is a page-locked image of the work layout.  hrow[pos]
     // = 1: row pos was added from host memory and is not yet on the device;
     // [run_lo, run_hi) is the latest stretch of consecutive host rows (it
     // streams to HBM once it reaches STREAM_BYTES).  h_flags: the received
     // flags of the two segments, for the device.
-    HostBuf h_img, h_flags, h_out;  // h_out: restored originals, row = original index
+    struct Dev {
+        DevBuf work, ubuf, flags;       // work = shards (z), ubuf = second work array (u)
+        HostBuf h_img, h_flags, h_out;  // h_out: restored originals, row = original index
+        Pending in_done, out_done;
+    } dev;
     std::vector<uint8_t> hrow;
     size_t run_lo = 0, run_hi = 0;
     bool host_round = false, dev_round = false, out_on_host = false;
-    Pending in_done, out_done;
 };
-
-void rs16::detach(rs16_decoder* d) {
-    d->work.release();
-    d->ubuf.release();
-    d->flags.release();
-    d->h_img.release();
-    d->h_flags.release();
-    d->h_out.release();
-    d->in_done.release();
-    d->out_done.release();
-    d->eng = nullptr;
-}
+template void rs16::detach(rs16_decoder*);
 
 static void decoder_new_round(rs16_decoder* d) {
     d->decoded = false;
@@ -254,9 +239,9 @@ extern "C" int rs16_decoder_reset(rs16_decoder* d, size_t k, size_t m, size_t S,
     if (int rc = resolve_rate(d->rate_kind, k, m, S, &high, err)) return rc;
     const size_t wc = rs16_decoder_work_count(high, k, m);
     if (int rc = d->eng->activate(err)) return rc;
-    RS16_HIP(d->work.reserve(wc * S));
-    RS16_HIP(d->ubuf.reserve(wc * S));
-    RS16_HIP(d->flags.reserve(GF_ORDER * 2));
+    RS16_HIP(d->dev.work.reserve(wc * S));
+    RS16_HIP(d->dev.ubuf.reserve(wc * S));
+    RS16_HIP(d->dev.flags.reserve(GF_ORDER * 2));
     d->high = high;
     d->k = k;
     d->m = m;
@@ -288,7 +273,7 @@ extern "C" void rs16_decoder_free(rs16_decoder* d) { free_attached(d, &rs16_engi
 // Copy host rows [lo, hi) of the image to the device work rows.
 static int decoder_stream(rs16_decoder* d, size_t lo, size_t hi, rs16_error* err) {
     const size_t S = d->S;
-    RS16_HIP(hipMemcpyAsync((uint8_t*)d->work.p + lo * S, (const uint8_t*)d->h_img.p + lo * S, (hi - lo) * S,
+    RS16_HIP(hipMemcpyAsync((uint8_t*)d->dev.work.p + lo * S, (const uint8_t*)d->dev.h_img.p + lo * S, (hi - lo) * S,
                             hipMemcpyHostToDevice, d->eng->stream));
     std::fill(d->hrow.begin() + lo, d->hrow.begin() + hi, 0);
     return RS16_OK;
@@ -331,16 +316,16 @@ static int decoder_add(rs16_decoder* d, bool original, size_t index, const void*
     const size_t S = d->S;
     if (device) {
         if (int rc = d->eng->activate(err)) return rc;
-        RS16_HIP(hipMemcpyAsync((uint8_t*)d->work.p + pos * S, shard, len, hipMemcpyDeviceToDevice, d->eng->stream));
+        RS16_HIP(hipMemcpyAsync((uint8_t*)d->dev.work.p + pos * S, shard, len, hipMemcpyDeviceToDevice, d->eng->stream));
         d->dev_round = true;
     } else {
         if (!d->host_round) {
             // the previous round's copies out of the image must be done
-            RS16_HIP(d->in_done.wait());
-            RS16_HIP(d->h_img.reserve(d->work_count * S));
+            RS16_HIP(d->dev.in_done.wait());
+            RS16_HIP(d->dev.h_img.reserve(d->work_count * S));
             d->host_round = true;
         }
-        memcpy((uint8_t*)d->h_img.p + pos * S, shard, len);
+        memcpy((uint8_t*)d->dev.h_img.p + pos * S, shard, len);
         d->hrow[pos] = 1;
         if (pos == d->run_hi && d->run_hi > d->run_lo) d->run_hi++;
         else d->run_lo = pos, d->run_hi = pos + 1;
@@ -377,10 +362,10 @@ static int decoder_fetch(rs16_decoder* d, rs16_error* err) {
         if (!d->received[d->orig_base + i]) lo = std::min(lo, i), hi = i + 1;
     if (hi > lo) {
         const size_t S = d->S;
-        RS16_HIP(d->h_out.reserve(d->k * S));
-        RS16_HIP(hipMemcpyAsync((uint8_t*)d->h_out.p + lo * S, (const uint8_t*)d->work.p + (d->orig_base + lo) * S,
+        RS16_HIP(d->dev.h_out.reserve(d->k * S));
+        RS16_HIP(hipMemcpyAsync((uint8_t*)d->dev.h_out.p + lo * S, (const uint8_t*)d->dev.work.p + (d->orig_base + lo) * S,
                                 (hi - lo) * S, hipMemcpyDeviceToHost, d->eng->stream));
-        RS16_HIP(d->out_done.record(d->eng->stream));
+        RS16_HIP(d->dev.out_done.record(d->eng->stream));
     }
     d->out_on_host = true;
     return RS16_OK;
@@ -404,22 +389,22 @@ extern "C" int rs16_decoder_decode(rs16_decoder* d, rs16_error* err) {
     // Received flags of the two segments -> device (bytes, one per row), out
     // of the page-locked staging (written once the previous round's copies
     // out of it are done).
-    if (!d->host_round) RS16_HIP(d->in_done.wait());
-    RS16_HIP(d->h_flags.reserve(GF_ORDER * 2));
-    uint8_t* hf = (uint8_t*)d->h_flags.p;
+    if (!d->host_round) RS16_HIP(d->dev.in_done.wait());
+    RS16_HIP(d->dev.h_flags.reserve(GF_ORDER * 2));
+    uint8_t* hf = (uint8_t*)d->dev.h_flags.p;
     memcpy(hf, d->received.data(), g.a_count);
     memcpy(hf + GF_ORDER, d->received.data() + g.chunk, g.b_count);
-    uint8_t* fl = (uint8_t*)d->flags.p;
+    uint8_t* fl = (uint8_t*)d->dev.flags.p;
     RS16_HIP(hipMemcpyAsync(fl, hf, g.a_count, hipMemcpyHostToDevice, e->stream));
     RS16_HIP(hipMemcpyAsync(fl + GF_ORDER, hf + GF_ORDER, g.b_count, hipMemcpyHostToDevice, e->stream));
-    RS16_HIP(d->in_done.record(e->stream));
-    uint8_t* w = (uint8_t*)d->work.p;
+    RS16_HIP(d->dev.in_done.record(e->stream));
+    uint8_t* w = (uint8_t*)d->dev.work.p;
     DecodeSegs v;
     v.seg_a = w, v.fl_a = fl;
     v.seg_b = w + (size_t)g.chunk * d->S, v.fl_b = fl + GF_ORDER;
     v.rest = w + d->orig_base * d->S;
     v.S_user = d->S;
-    if (int rc = e->decode_fused(g, d->S, v, w, (uint8_t*)d->ubuf.p, e->stream, err)) return rc;
+    if (int rc = e->decode_fused(g, d->S, v, w, (uint8_t*)d->dev.ubuf.p, e->stream, err)) return rc;
     e->forget_decode();
     if (int rc = e->scratch_done(e->stream, err)) return rc;
     if (d->host_round)
@@ -429,7 +414,7 @@ extern "C" int rs16_decoder_decode(rs16_decoder* d, rs16_error* err) {
 }
 extern "C" const void* rs16_decoder_restored_original_device(rs16_decoder* d, size_t index) {
     const size_t pos = d->orig_base + index;
-    if (d->eng && d->decoded && index < d->k && !d->received[pos]) return (const uint8_t*)d->work.p + pos * d->S;
+    if (d->eng && d->decoded && index < d->k && !d->received[pos]) return (const uint8_t*)d->dev.work.p + pos * d->S;
     return nullptr;
 }
 extern "C" const void* rs16_decoder_restored_original(rs16_decoder* d, size_t index, rs16_error* err) {

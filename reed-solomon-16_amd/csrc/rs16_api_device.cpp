@@ -202,7 +202,7 @@ extern "C" int rs16_decode_prepare(rs16_engine* e, size_t k, size_t m, size_t S,
         if (int rc = begin_ordered(e, stream, &s, err)) return rc;
         if (int rc = e->guard_eval(s, false, err)) return rc;  // (an earlier, unconsumed preparation)
         if (int rc = ds.eval(e, e->ev_main, &p.plan, s, err, p.nslices == 1 ? S : 0, 1, 0, true)) return rc;
-        if (!e->prep_ev) RS16_HIP(hipEventCreateWithFlags(&e->prep_ev, hipEventDisableTiming));
+        RS16_HIP(e->prep_ev.get());
         RS16_HIP(hipEventRecord(e->prep_ev, s));
         e->prep_pending = true;
     }

@@ -10,8 +10,8 @@ using namespace rs16;
 // ---------------------------------------------------------------------------
 int rs16_engine::host_slots(rs16_error* err) {
     for (auto& sl : hslot)
-        if (!sl.s) RS16_HIP(hipStreamCreateWithFlags(&sl.s, hipStreamNonBlocking));
-    if (!hev) RS16_HIP(hipEventCreateWithFlags(&hev, hipEventDisableTiming));
+        RS16_HIP(sl.s.get());
+    RS16_HIP(hev.get());
     if (int rc = order(stream, err)) return rc;
     // start after the caller's earlier work on the engine stream
     RS16_HIP(hipEventRecord(hev, stream));
@@ -194,9 +194,8 @@ constexpr size_t HP_MAX_RUNS = 64;
 }  // namespace
 
 int rs16_engine::host_pipe_events(rs16_error* err) {
-    for (auto& ev : hp_ev)
-        if (!ev) RS16_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    if (!hp_off) RS16_HIP(hipEventCreateWithFlags(&hp_off, hipEventDisableTiming));
+    for (auto& ev : hp_ev) RS16_HIP(ev.get());
+    RS16_HIP(hp_off.get());
     return RS16_OK;
 }
 

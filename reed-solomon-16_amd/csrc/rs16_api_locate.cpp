@@ -22,13 +22,11 @@ struct rs16_locate_plan {
     std::vector<uint16_t> rows;  // 2 k field elements: M[0][i], then M[1][i]
     // u16 tables on the device: log (GF_ORDER), exp (GF_ORDER), ratio -> i
     // (GF_ORDER, the last entry unused), log M[0][i] (k)
-    DevBuf tab;
+    struct Dev {
+        DevBuf tab;
+    } dev;
 };
-
-void rs16::detach(rs16_locate_plan* p) {
-    p->tab.release();
-    p->eng = nullptr;
-}
+template void rs16::detach(rs16_locate_plan*);
 
 // Rows 0 and 1 of M from the engine's own encode of unit vectors, so they are
 // exact on every rate path: original i carries the element 1 at element
@@ -44,34 +42,28 @@ static int locate_rows(rs16_engine* e, bool high, size_t k, size_t m, std::vecto
     std::vector<uint8_t> rec(2 * Smax);
     rows.assign(2 * k, 0);
     DevBuf d_unit, d_rec;
-    auto run = [&]() -> int {
-        RS16_HIP(d_unit.reserve(k * Smax));
-        RS16_HIP(d_rec.reserve(m * Smax));
-        hipStream_t s = e->stream;
-        if (int rc = e->order(s, err)) return rc;
-        // (on the stream the ones are set on: a non-blocking stream does not wait for the null stream)
-        RS16_HIP(hipMemsetAsync(d_unit.p, 0, k * Smax, s));
-        // (the first chunk is the widest: the engine's scratch grows there or not at all)
-        for (size_t i0 = 0; i0 < k; i0 += per) {
-            const size_t n = std::min(per, k - i0), S = 64 * ((n + 31) / 32);
-            RS16_HIP(launch_locate_unit((uint8_t*)d_unit.p, S, (uint32_t)i0, (uint32_t)n, 1, s));
-            if (int rc = encode_stripes(e, high, k, m, S, 1, (const uint8_t*)d_unit.p, 0, (uint8_t*)d_rec.p, 0, s, err))
-                return rc;
-            RS16_HIP(launch_locate_unit((uint8_t*)d_unit.p, S, (uint32_t)i0, (uint32_t)n, 0, s));
-            RS16_HIP(hipMemcpyAsync(rec.data(), d_rec.p, 2 * S, hipMemcpyDeviceToHost, s));
-            RS16_HIP(hipStreamSynchronize(s));
-            for (size_t j = 0; j < 2; j++)
-                for (size_t q = 0; q < n; q++) {
-                    const size_t at = j * S + 64 * (q / 32) + q % 32;
-                    rows[j * k + i0 + q] = (uint16_t)(rec[at] | (uint16_t)rec[at + 32] << 8);
-                }
-        }
-        return e->scratch_done(s, err);
-    };
-    const int rc = run();
-    d_unit.release();
-    d_rec.release();
-    return rc;
+    RS16_HIP(d_unit.reserve(k * Smax));
+    RS16_HIP(d_rec.reserve(m * Smax));
+    hipStream_t s = e->stream;
+    if (int rc = e->order(s, err)) return rc;
+    // (on the stream the ones are set on: a non-blocking stream does not wait for the null stream)
+    RS16_HIP(hipMemsetAsync(d_unit.p, 0, k * Smax, s));
+    // (the first chunk is the widest: the engine's scratch grows there or not at all)
+    for (size_t i0 = 0; i0 < k; i0 += per) {
+        const size_t n = std::min(per, k - i0), S = 64 * ((n + 31) / 32);
+        RS16_HIP(launch_locate_unit((uint8_t*)d_unit.p, S, (uint32_t)i0, (uint32_t)n, 1, s));
+        if (int rc = encode_stripes(e, high, k, m, S, 1, (const uint8_t*)d_unit.p, 0, (uint8_t*)d_rec.p, 0, s, err))
+            return rc;
+        RS16_HIP(launch_locate_unit((uint8_t*)d_unit.p, S, (uint32_t)i0, (uint32_t)n, 0, s));
+        RS16_HIP(hipMemcpyAsync(rec.data(), d_rec.p, 2 * S, hipMemcpyDeviceToHost, s));
+        RS16_HIP(hipStreamSynchronize(s));
+        for (size_t j = 0; j < 2; j++)
+            for (size_t q = 0; q < n; q++) {
+                const size_t at = j * S + 64 * (q / 32) + q % 32;
+                rows[j * k + i0 + q] = (uint16_t)(rec[at] | (uint16_t)rec[at + 32] << 8);
+            }
+    }
+    return e->scratch_done(s, err);
 }
 
 extern "C" rs16_locate_plan* rs16_locate_plan_new(rs16_engine* eng, int rate, size_t k, size_t m, rs16_error* err) {
@@ -105,8 +97,8 @@ extern "C" rs16_locate_plan* rs16_locate_plan_new(rs16_engine* eng, int rate, si
             ratio[d] = (uint16_t)i;
             log_m0[i] = (uint16_t)la;
         }
-        RS16_HIP(p->tab.reserve(tab.size() * 2));
-        RS16_HIP(hipMemcpy(p->tab.p, tab.data(), tab.size() * 2, hipMemcpyHostToDevice));
+        RS16_HIP(p->dev.tab.reserve(tab.size() * 2));
+        RS16_HIP(hipMemcpy(p->dev.tab.p, tab.data(), tab.size() * 2, hipMemcpyHostToDevice));
         return RS16_OK;
     };
     if (build()) {
@@ -195,7 +187,7 @@ static int locate(rs16_locate_plan* p, size_t S, bool batched, size_t nstripes, 
         RS16_HIP(hipMemsetAsync(e->ws_loc_acc.p, 0, e->ws_loc_acc.cap, s));
     }
     e->loc_clean = false;  // until the confirm kernel, which puts the last of it back, is enqueued
-    const uint16_t* tab = (const uint16_t*)p->tab.p;
+    const uint16_t* tab = (const uint16_t*)p->dev.tab.p;
     LocateArgs a{};
     a.enc = (const uint8_t*)e->ws_rep.p, a.bs_enc = m * S;
     a.rec = (const uint8_t*)d_recovery, a.bs_rec = r_stride;

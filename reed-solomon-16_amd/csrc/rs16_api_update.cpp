@@ -18,13 +18,11 @@ struct rs16_update_plan {
     rs16_engine* eng;  // nullptr once the engine was freed (detached)
     size_t k = 0, m = 0, n = 0;
     std::vector<uint16_t> coef;  // m x n field elements, coef[j n + e] = M[j][indices[e]]
-    DevBuf idx;                  // m x n d_mul_tab entries of them (ZERO_ENTRY for 0)
+    struct Dev {
+        DevBuf idx;  // m x n d_mul_tab entries of them (ZERO_ENTRY for 0)
+    } dev;
 };
-
-void rs16::detach(rs16_update_plan* p) {
-    p->idx.release();
-    p->eng = nullptr;
-}
+template void rs16::detach(rs16_update_plan*);
 
 // The unit-vector encode: coef[j n + e] = M[j][indices[e]].
 static int update_coefficients(rs16_engine* e, bool high, size_t k, size_t m, const size_t* indices, size_t n,
@@ -33,23 +31,16 @@ static int update_coefficients(rs16_engine* e, bool high, size_t k, size_t m, co
     std::vector<uint8_t> unit(k * S, 0), rec(m * S);
     for (size_t el = 0; el < n; el++) unit[indices[el] * S + el] = 1;  // low byte 1, high byte 0
     DevBuf d_unit, d_rec;
-    auto run = [&]() -> int {
-        RS16_HIP(d_unit.reserve(k * S));
-        RS16_HIP(d_rec.reserve(m * S));
-        RS16_HIP(hipMemcpy(d_unit.p, unit.data(), k * S, hipMemcpyHostToDevice));
-        hipStream_t s = e->stream;
-        if (int rc = e->order(s, err)) return rc;
-        if (int rc = encode_stripes(e, high, k, m, S, 1, (const uint8_t*)d_unit.p, 0, (uint8_t*)d_rec.p, 0, s, err))
-            return rc;
-        if (int rc = e->scratch_done(s, err)) return rc;
-        RS16_HIP(hipStreamSynchronize(s));
-        RS16_HIP(hipMemcpy(rec.data(), d_rec.p, m * S, hipMemcpyDeviceToHost));
-        return RS16_OK;
-    };
-    const int rc = run();
-    d_unit.release();
-    d_rec.release();
-    if (rc) return rc;
+    RS16_HIP(d_unit.reserve(k * S));
+    RS16_HIP(d_rec.reserve(m * S));
+    RS16_HIP(hipMemcpy(d_unit.p, unit.data(), k * S, hipMemcpyHostToDevice));
+    hipStream_t s = e->stream;
+    if (int rc = e->order(s, err)) return rc;
+    if (int rc = encode_stripes(e, high, k, m, S, 1, (const uint8_t*)d_unit.p, 0, (uint8_t*)d_rec.p, 0, s, err))
+        return rc;
+    if (int rc = e->scratch_done(s, err)) return rc;
+    RS16_HIP(hipStreamSynchronize(s));
+    RS16_HIP(hipMemcpy(rec.data(), d_rec.p, m * S, hipMemcpyDeviceToHost));
     coef.resize(m * n);
     for (size_t j = 0; j < m; j++)
         for (size_t el = 0; el < n; el++)
@@ -80,9 +71,9 @@ extern "C" rs16_update_plan* rs16_update_plan_new(rs16_engine* eng, int rate, si
         const HostTables& t = host_tables();
         std::vector<uint32_t> entry(m * n);
         for (size_t i = 0; i < m * n; i++) entry[i] = p->coef[i] ? (uint32_t)t.log[p->coef[i]] : ZERO_ENTRY;
-        RS16_HIP(p->idx.reserve(m * n * 4));
+        RS16_HIP(p->dev.idx.reserve(m * n * 4));
         // a host copy, complete before any launch reads the array on the scalar path
-        RS16_HIP(hipMemcpy(p->idx.p, entry.data(), m * n * 4, hipMemcpyHostToDevice));
+        RS16_HIP(hipMemcpy(p->dev.idx.p, entry.data(), m * n * 4, hipMemcpyHostToDevice));
         return RS16_OK;
     };
     if (build()) {
@@ -117,8 +108,8 @@ extern "C" int rs16_update_device(rs16_update_plan* p, size_t S, const void* d_d
     UpdateArgs a{};
     a.rec = (uint8_t*)d_recovery;
     a.delta = (const uint8_t*)d_delta;
-    a.idx = (const uint32_t*)p->idx.p;
-    a.mul_tab = e->d_mul_tab;
+    a.idx = (const uint32_t*)p->dev.idx.p;
+    a.mul_tab = e->d_mul_tab.as<uint32_t>();
     a.S = S;
     a.qrow = (uint32_t)(S / 8);
     a.row0 = (uint32_t)recovery_pos;

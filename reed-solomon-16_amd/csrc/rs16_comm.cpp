@@ -23,21 +23,31 @@
 #include <thread>
 #include <vector>
 
-#include "rs16_engine.hpp"
+#include "rs16_api.hpp"
 
 using namespace rs16;
 
 struct rs16_comm {
-    rs16_engine* eng = nullptr;
+    rs16_engine* eng = nullptr;  // nullptr once the engine was freed (detached)
     ncclComm_t nc = nullptr;
     int nranks = 0, rank = 0;
     bool blocking = false;  // ncclCommInitAll communicators are blocking
-    DevBuf stage;  // root: packed column slices
-    // the last collective's use of `stage` (recorded on its stream): the
-    // next collective, on whatever stream, waits for it before repacking
-    hipEvent_t stage_ev = nullptr;
-    bool stage_busy = false;
+    struct Dev {
+        DevBuf stage;  // root: packed column slices
+        // the last collective's use of `stage` (recorded on its stream): the
+        // next collective, on whatever stream, waits for it before repacking
+        Pending stage_used;
+    } dev;
 };
+
+// The engine's device is current and its stream idle (rs16_engine's destructor, free_attached).
+void rs16::detach(rs16_comm* c) {
+    // (a collective on a caller's stream: its last use of the staging buffer)
+    (void)c->dev.stage_used.wait();
+    if (c->nc) (void)ncclCommDestroy(c->nc);
+    c->nc = nullptr;
+    detach<rs16_comm>(c);
+}
 
 static int nccl_fail(rs16_error* err, ncclResult_t r) { return set_error(err, RS16_DEVICE_ERROR, 1000 + (uint64_t)r); }
 #define RS16_NCCL(call)                                     \
@@ -111,6 +121,7 @@ extern "C" rs16_comm* rs16_comm_new(rs16_engine* eng, int nranks, int rank, cons
     c->eng = eng;
     c->nranks = nranks;
     c->rank = rank;
+    eng->comms.push_back(c);
     set_error(err, RS16_OK);
     return c;
 }
@@ -135,6 +146,7 @@ extern "C" int rs16_comm_init_all(rs16_engine* const* engines, int n, rs16_comm*
     }
     for (int i = 0; i < n; i++) {
         comms[i]->eng = engines[i];
+        engines[i]->comms.push_back(comms[i]);
         comms[i]->nc = nc[i];
         comms[i]->nranks = n;
         comms[i]->rank = i;
@@ -143,22 +155,11 @@ extern "C" int rs16_comm_init_all(rs16_engine* const* engines, int n, rs16_comm*
     return set_error(err, RS16_OK);
 }
 
-extern "C" void rs16_comm_free(rs16_comm* c) {
-    if (!c) return;
-    if (c->eng) {
-        (void)hipSetDevice(c->eng->device);
-        (void)hipStreamSynchronize(c->eng->stream);
-        // (a collective on a caller's stream: its last use of the staging buffer)
-        if (c->stage_busy) (void)hipEventSynchronize(c->stage_ev);
-    }
-    if (c->nc) (void)ncclCommDestroy(c->nc);
-    if (c->stage_ev) (void)hipEventDestroy(c->stage_ev);
-    c->stage.release();
-    delete c;
-}
+extern "C" void rs16_comm_free(rs16_comm* c) { free_attached(c, &rs16_engine::comms); }
 
-extern "C" int rs16_comm_rank(const rs16_comm* c) { return c->rank; }
-extern "C" int rs16_comm_size(const rs16_comm* c) { return c->nranks; }
+// (a detached communicator: the code, negative so that it is no rank and no size)
+extern "C" int rs16_comm_rank(const rs16_comm* c) { return c->eng ? c->rank : -RS16_INVALID_ARGUMENT; }
+extern "C" int rs16_comm_size(const rs16_comm* c) { return c->eng ? c->nranks : -RS16_INVALID_ARGUMENT; }
 extern "C" int rs16_column_slice(size_t shard_bytes, int nranks, int rank, size_t* offset, size_t* width) {
     if (nranks < 1 || rank < 0 || rank >= nranks || shard_bytes % 64) return RS16_INVALID_ARGUMENT;
     col_slice(shard_bytes, nranks, rank, offset, width);
@@ -180,7 +181,8 @@ static int columns(rs16_comm* const* comms, int n, int root, size_t rows, size_t
     const int nranks = comms[0]->nranks;
     if (root < 0 || root >= nranks) return set_error(err, RS16_INVALID_ARGUMENT);
     for (int i = 0; i < n; i++)
-        if (!comms[i] || !comms[i]->nc || comms[i]->nranks != nranks) return set_error(err, RS16_INVALID_ARGUMENT);
+        if (!comms[i] || !comms[i]->eng || !comms[i]->nc || comms[i]->nranks != nranks)
+            return set_error(err, RS16_INVALID_ARGUMENT);
     const bool virt = vslices > 0;
     if (virt && (nranks != 1 || n != 1 || vslices > 4096)) return set_error(err, RS16_INVALID_ARGUMENT);
     const int P = virt ? vslices : nranks;
@@ -206,16 +208,16 @@ static int columns(rs16_comm* const* comms, int n, int root, size_t rows, size_t
                                       hipMemcpyDeviceToDevice, strm(c)));
         if (P == 1) continue;
         // the previous collective's use of the staging buffer (maybe on another stream)
-        if (c->stage_busy) RS16_HIP(hipStreamWaitEvent(strm(c), c->stage_ev, 0));
-        if (c->stage.cap < rows * S) {
+        if (c->dev.stage_used.busy) RS16_HIP(hipStreamWaitEvent(strm(c), c->dev.stage_used.ev, 0));
+        if (c->dev.stage.cap < rows * S) {
             RS16_HIP(hipStreamSynchronize(strm(c)));  // (reserve frees the old buffer)
-            RS16_HIP(c->stage.reserve(rows * S));
+            RS16_HIP(c->dev.stage.reserve(rows * S));
         }
         if (scatter)
             for (int j = 0; j < P; j++) {
                 col_slice(S, P, j, &off, &w);
                 if (!w || j == own) continue;
-                RS16_HIP(hipMemcpy2DAsync((uint8_t*)c->stage.p + rows * off, w, (const uint8_t*)d_full[i] + off, S, w,
+                RS16_HIP(hipMemcpy2DAsync((uint8_t*)c->dev.stage.p + rows * off, w, (const uint8_t*)d_full[i] + off, S, w,
                                           rows, hipMemcpyDeviceToDevice, strm(c)));
             }
     }
@@ -242,7 +244,7 @@ static int columns(rs16_comm* const* comms, int n, int root, size_t rows, size_t
                 size_t o2, w2;
                 col_slice(S, P, j, &o2, &w2);
                 if (!w2 || j == own) continue;
-                if (int rc = p2p(scatter, (uint8_t*)c->stage.p + rows * o2, rows * w2, owner(j), c)) return rc;
+                if (int rc = p2p(scatter, (uint8_t*)c->dev.stage.p + rows * o2, rows * w2, owner(j), c)) return rc;
             }
         // the owners' side: every slice of this rank that the root does not keep
         for (int j = 0; j < P; j++) {
@@ -274,12 +276,10 @@ static int columns(rs16_comm* const* comms, int n, int root, size_t rows, size_t
                 size_t off, w;
                 col_slice(S, P, j, &off, &w);
                 if (!w || j == own) continue;
-                RS16_HIP(hipMemcpy2DAsync((uint8_t*)d_full[i] + off, S, (const uint8_t*)c->stage.p + rows * off, w, w,
+                RS16_HIP(hipMemcpy2DAsync((uint8_t*)d_full[i] + off, S, (const uint8_t*)c->dev.stage.p + rows * off, w, w,
                                           rows, hipMemcpyDeviceToDevice, strm(c)));
             }
-        if (!c->stage_ev) RS16_HIP(hipEventCreateWithFlags(&c->stage_ev, hipEventDisableTiming));
-        RS16_HIP(hipEventRecord(c->stage_ev, strm(c)));
-        c->stage_busy = true;
+        RS16_HIP(c->dev.stage_used.record(strm(c)));
     }
     return set_error(err, RS16_OK);
 }

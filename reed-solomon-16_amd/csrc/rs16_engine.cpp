@@ -10,9 +10,7 @@ namespace rs16 {
 
 hipError_t DevBuf::reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
     hipError_t e = hipMalloc(&p, bytes);
     if (e == hipSuccess) cap = bytes;
     return e;
@@ -25,9 +23,7 @@ void DevBuf::release() {
 
 hipError_t HostBuf::reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
     hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocPortable);
     if (e == hipSuccess) cap = bytes;
     return e;
@@ -38,11 +34,17 @@ void HostBuf::release() {
     cap = 0;
 }
 
+void Event::release() {
+    if (ev) (void)hipEventDestroy(ev);
+    ev = nullptr;
+}
+void Stream::release() {
+    if (s) (void)hipStreamDestroy(s);
+    s = nullptr;
+}
+
 hipError_t Pending::record(hipStream_t s) {
-    if (!ev) {
-        hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = ev.get()) return e;
     hipError_t e = hipEventRecord(ev, s);
     busy = e == hipSuccess;
     return e;
@@ -51,11 +53,6 @@ hipError_t Pending::wait() {
     if (!busy) return hipSuccess;
     busy = false;
     return hipEventSynchronize(ev);
-}
-void Pending::release() {
-    if (ev) (void)hipEventDestroy(ev);
-    ev = nullptr;
-    busy = false;
 }
 
 int set_error(rs16_error* err, int code, uint64_t v0, uint64_t v1, uint64_t v2) {
@@ -102,9 +99,9 @@ RepairTiles repair_tiles(const DecodeGeom& g) {
 static PassArgs base_args(const rs16_engine* e, size_t S) {
     PassArgs a;
     std::memset(&a, 0, sizeof a);
-    a.skew_tab = e->d_skew_tab;
-    a.mul_tab = e->d_mul_tab;
-    a.zero = e->d_zero_sink;
+    a.skew_tab = e->d_skew_tab.as<uint32_t>();
+    a.mul_tab = e->d_mul_tab.as<uint32_t>();
+    a.zero = e->d_zero_sink.as<uint8_t>();
     a.S_in = a.S_out = a.S_seg = a.S_rest = S;
     a.qrow = (uint32_t)(S / 8);
     a.diag = (uint32_t)e->diag;
@@ -129,10 +126,10 @@ int rs16_engine::slice_count(size_t S) const {
 // Slice 0 runs on the caller's stream s itself; slices 1.. on sl_stream[1..]
 // (sl_stream[0] = s while a sliced call is being issued).
 int rs16_engine::fork(hipStream_t s, int n, rs16_error* err) {
-    if (!sl_fork) RS16_HIP(hipEventCreateWithFlags(&sl_fork, hipEventDisableTiming));
+    RS16_HIP(sl_fork.get());
     if (n > 1) RS16_HIP(hipEventRecord(sl_fork, s));
     for (int j = 1; j < n; j++) {
-        if (!sl_own[j]) RS16_HIP(hipStreamCreateWithFlags(&sl_own[j], hipStreamNonBlocking));
+        RS16_HIP(sl_own[j].get());
         RS16_HIP(hipStreamWaitEvent(sl_own[j], sl_fork, 0));
     }
     sl_stream[0] = s;
@@ -142,7 +139,7 @@ int rs16_engine::fork(hipStream_t s, int n, rs16_error* err) {
 
 int rs16_engine::join(hipStream_t s, int n, rs16_error* err) {
     for (int j = 1; j < n; j++) {
-        if (!sl_join[j]) RS16_HIP(hipEventCreateWithFlags(&sl_join[j], hipEventDisableTiming));
+        RS16_HIP(sl_join[j].get());
         RS16_HIP(hipEventRecord(sl_join[j], sl_own[j]));
         RS16_HIP(hipStreamWaitEvent(s, sl_join[j], 0));
     }
@@ -151,7 +148,7 @@ int rs16_engine::join(hipStream_t s, int n, rs16_error* err) {
 
 int rs16_engine::order(hipStream_t s, rs16_error* err) {
     if (last == LAST_ENGINE && s != stream) {
-        if (!order_ev) RS16_HIP(hipEventCreateWithFlags(&order_ev, hipEventDisableTiming));
+        RS16_HIP(order_ev.get());
         RS16_HIP(hipEventRecord(order_ev, stream));
         RS16_HIP(hipStreamWaitEvent(s, order_ev, 0));
     } else if (last == LAST_CALLER) {
@@ -165,50 +162,42 @@ int rs16_engine::scratch_done(hipStream_t s, rs16_error* err) {
         last = LAST_ENGINE;
         return RS16_OK;
     }
-    if (!order_ev) RS16_HIP(hipEventCreateWithFlags(&order_ev, hipEventDisableTiming));
+    RS16_HIP(order_ev.get());
     RS16_HIP(hipEventRecord(order_ev, s));
     last = LAST_CALLER;
     return RS16_OK;
 }
 
-int rs16_engine::prof_begin(hipStream_t s, hipEvent_t* ev, rs16_error* err) {
-    *ev = nullptr;
-    if (!profiling) return RS16_OK;
-    if (ev_pool.empty()) {
-        hipEvent_t e;
-        RS16_HIP(hipEventCreate(&e));
-        ev_pool.push_back(e);
-    }
-    *ev = ev_pool.back();
-    ev_pool.pop_back();
-    RS16_HIP(hipEventRecord(*ev, s));
+// A timing event out of the pool (a new one when the pool is empty), recorded on s.
+static hipError_t pooled_record(std::vector<Event>& pool, Event* ev, hipStream_t s) {
+    if (!pool.empty()) *ev = std::move(pool.back()), pool.pop_back();
+    if (hipError_t e = ev->get(hipEventDefault)) return e;
+    return hipEventRecord(*ev, s);
+}
+
+int rs16_engine::prof_begin(hipStream_t s, Event* ev, rs16_error* err) {
+    if (profiling) RS16_HIP(pooled_record(ev_pool, ev, s));
     return RS16_OK;
 }
 
-int rs16_engine::prof_end(int id, hipStream_t s, hipEvent_t ev, rs16_error* err) {
+int rs16_engine::prof_end(int id, hipStream_t s, Event ev, rs16_error* err) {
     if (!ev) return RS16_OK;
-    if (ev_pool.empty()) {
-        hipEvent_t e;
-        RS16_HIP(hipEventCreate(&e));
-        ev_pool.push_back(e);
-    }
-    hipEvent_t b = ev_pool.back();
-    ev_pool.pop_back();
-    RS16_HIP(hipEventRecord(b, s));
-    prof_pending.push_back({id, ev, b});
+    Event b;
+    RS16_HIP(pooled_record(ev_pool, &b, s));
+    prof_pending.push_back({id, std::move(ev), std::move(b)});
     if (prof_pending.size() > 4096) return prof_collect(err);  // bound the event pool
     return RS16_OK;
 }
 
 int rs16_engine::prof_collect(rs16_error* err) {
-    for (const ProfRec& r : prof_pending) {
+    for (ProfRec& r : prof_pending) {
         RS16_HIP(hipEventSynchronize(r.b));
         float ms = 0.f;
         RS16_HIP(hipEventElapsedTime(&ms, r.a, r.b));
         prof_ms[r.id] += ms;
         prof_n[r.id] += 1;
-        ev_pool.push_back(r.a);
-        ev_pool.push_back(r.b);
+        ev_pool.push_back(std::move(r.a));
+        ev_pool.push_back(std::move(r.b));
     }
     prof_pending.clear();
     return RS16_OK;
@@ -245,9 +234,9 @@ ColArgs rs16_engine::col_args(const uint8_t* in, size_t S_in, uint8_t* out, size
                               size_t out_rows, size_t skew_ifft, size_t skew_fft) const {
     ColArgs a;
     std::memset(&a, 0, sizeof a);
-    a.skew_tab = d_skew_tab;
-    a.mul_tab = d_mul_tab;
-    a.zero = d_zero_sink;
+    a.skew_tab = d_skew_tab.as<uint32_t>();
+    a.mul_tab = d_mul_tab.as<uint32_t>();
+    a.zero = d_zero_sink.as<uint8_t>();
     a.nstripes = 1;
     a.diag = (uint32_t)diag;
     a.in = in;
@@ -283,24 +272,16 @@ EncodeForm rs16_engine::encode_form(bool high, size_t k, size_t m, size_t S, siz
 // The column codec's tables (HostTables::col_img / col_v), uploaded on the
 // engine's first column launch: engines that never run it allocate nothing.
 int rs16_engine::col_tables(hipStream_t s, rs16_error* err) {
-    if (d_col_img) return RS16_OK;
+    if (d_col_img.p) return RS16_OK;
     const HostTables& t = host_tables();
-    uint32_t *img = nullptr, *v = nullptr;
-    RS16_HIP(hipMalloc(&img, COL_IMG_DWORDS * 4));
-    if (hipError_t e = hipMalloc(&v, t.col_v.size() * 4)) {
-        (void)hipFree(img);
-        return hip_fail(err, e);
-    }
-    hipError_t e = hipMemcpyAsync(img, t.col_img.data(), COL_IMG_DWORDS * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(v, t.col_v.data(), t.col_v.size() * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);  // (pageable sources: keep no pending copy)
-    if (e != hipSuccess) {
-        (void)hipFree(img);
-        (void)hipFree(v);
-        return hip_fail(err, e);
-    }
-    d_col_img = img;
-    d_col_v = v;
+    DevBuf img, v;  // (the members only once both are whole)
+    RS16_HIP(img.reserve(COL_IMG_DWORDS * 4));
+    RS16_HIP(v.reserve(t.col_v.size() * 4));
+    RS16_HIP(hipMemcpyAsync(img.p, t.col_img.data(), COL_IMG_DWORDS * 4, hipMemcpyHostToDevice, s));
+    RS16_HIP(hipMemcpyAsync(v.p, t.col_v.data(), t.col_v.size() * 4, hipMemcpyHostToDevice, s));
+    RS16_HIP(hipStreamSynchronize(s));  // (pageable sources: keep no pending copy)
+    d_col_img = std::move(img);
+    d_col_v = std::move(v);
     return RS16_OK;
 }
 
@@ -315,10 +296,11 @@ int rs16_engine::col(const ColArgs& args, int L, int mode, hipStream_t s, rs16_e
     if ((a.skew_ifft != 0 && a.skew_ifft != N) || (a.skew_fft != 0 && a.skew_fft != N) ||
         (a.nch > 1 && a.nch >= col_img_count((uint32_t)L)))
         return hip_fail(err, hipErrorInvalidValue);  // (unreachable: every caller passes 0 or 2^L)
-    a.img_ifft = (const uint8_t*)(d_col_img + col_img_offset((uint32_t)L, a.skew_ifft ? 1 : 0));
-    a.img_fft = (const uint8_t*)(d_col_img + col_img_offset((uint32_t)L, a.skew_fft ? 1 : 0));
-    if (mode == COL_DEC_EVAL) a.vtab = d_col_v + col_v_offset(2u << L);  // (2^(L+1) work rows)
-    if (mode == COL_DEC_GEN || sel) a.vtab = d_col_v + col_v_offset(1u << L);  // (2^L work rows)
+    const uint32_t *img = d_col_img.as<uint32_t>(), *vt = d_col_v.as<uint32_t>();
+    a.img_ifft = (const uint8_t*)(img + col_img_offset((uint32_t)L, a.skew_ifft ? 1 : 0));
+    a.img_fft = (const uint8_t*)(img + col_img_offset((uint32_t)L, a.skew_fft ? 1 : 0));
+    if (mode == COL_DEC_EVAL) a.vtab = vt + col_v_offset(2u << L);  // (2^(L+1) work rows)
+    if (mode == COL_DEC_GEN || sel) a.vtab = vt + col_v_offset(1u << L);  // (2^L work rows)
     return profiled(sel ? PROF_COL_DEC_SEL : (dec ? PROF_COL_DEC : PROF_COL_ENC), s, err, [&](uint64_t* stamps) {
         if (stamps) a.stamps = stamps;
         return launch_col(a, (uint32_t)L, mode, s);
@@ -339,7 +321,7 @@ int rs16_engine::col_multi(size_t k, size_t m, size_t S, size_t S_user, const ui
 // form, and their twiddle table (a tower sequence: in tower coordinates).
 void rs16_engine::z_form_args(PassArgs& a, ZForm f) const {
     a.z_form = f;
-    a.skew_tab = f == Z_TOWER ? d_skew_tab_tower : d_skew_tab;
+    a.skew_tab = (f == Z_TOWER ? d_skew_tab_tower : d_skew_tab).as<uint32_t>();
 }
 
 // Engine::fft over 2^L rows: L <= 8 in one pass; otherwise the high
@@ -575,7 +557,7 @@ int rs16_engine::decode_eval(const DecodeGeom& g, const uint8_t* flags_a, const 
     return profiled(PROF_EVAL_POLY, s, err, [&](uint64_t* stamps) {
         es.stamps = stamps;
         // (the form -- small, fused, two-kernel -- is the launcher's choice, rs16_eval.hip)
-        return launch_eval_poly_from_flags(es, work, elog, d_log_walsh, s, !p.elog_fused);
+        return launch_eval_poly_from_flags(es, work, elog, d_log_walsh.as<uint16_t>(), s, !p.elog_fused);
     });
 }
 
@@ -625,12 +607,10 @@ int rs16_engine::mid_tables(int L, const uint32_t** out, rs16_error* err) {
         std::vector<uint32_t> tabs(ent.size() * 20);
         for (size_t i = 0; i < ent.size(); i++)
             std::copy_n(&t.mul_tab[(size_t)ent[i] * TAB_DWORDS], 20, &tabs[i * 20]);
-        hipError_t he = b.reserve(tabs.size() * 4);
-        if (he == hipSuccess) he = hipMemcpy(b.p, tabs.data(), tabs.size() * 4, hipMemcpyHostToDevice);
-        if (he != hipSuccess) {
-            b.release();
-            return hip_fail(err, he);
-        }
+        DevBuf up;  // (the member only once the table is whole)
+        RS16_HIP(up.reserve(tabs.size() * 4));
+        RS16_HIP(hipMemcpy(up.p, tabs.data(), tabs.size() * 4, hipMemcpyHostToDevice));
+        b = std::move(up);
     }
     *out = (const uint32_t*)b.p;
     return RS16_OK;

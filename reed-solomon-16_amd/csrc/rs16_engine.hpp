@@ -2,6 +2,8 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/rs16.h"
@@ -9,28 +11,75 @@
 
 namespace rs16 {
 
+// The five holders of what the host side owns on the GPU.  Each frees its
+// resource in its destructor (on the device it was made on, current then),
+// cannot be copied and is empty after a move: a member or a local of these
+// types needs no release list.  release() is for freeing early on purpose.
+//
 // Grow-only device buffer.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept { return release(), std::swap(p, o.p), std::swap(cap, o.cap), *this; }
+    ~DevBuf() { if (p) release(); }
     hipError_t reserve(size_t bytes);
     void release();
+    template <class T> T* as() const { return (T*)p; }  // a table that kernels read as T
 };
 // Grow-only page-locked host buffer (hipHostMalloc): DMA-rate H2D / D2H.
 struct HostBuf {
     void* p = nullptr;
     size_t cap = 0;
+    HostBuf() = default;
+    HostBuf(HostBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    HostBuf& operator=(HostBuf&& o) noexcept { return release(), std::swap(p, o.p), std::swap(cap, o.cap), *this; }
+    ~HostBuf() { if (p) release(); }
     hipError_t reserve(size_t bytes);
     void release();
 };
+// An event, made by the first get() (hipEventDefault: the profiling pool's timing flavour).
+struct Event {
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : ev(std::exchange(o.ev, nullptr)) {}
+    Event& operator=(Event&& o) noexcept { return release(), std::swap(ev, o.ev), *this; }
+    ~Event() { if (ev) release(); }  // (inline: an empty one costs a test)
+    hipError_t get(unsigned flags = hipEventDisableTiming) {
+        return ev ? hipSuccess : hipEventCreateWithFlags(&ev, flags);
+    }
+    void release();
+    operator hipEvent_t() const { return ev; }
+};
+// A stream, made by the first get() (non-blocking) or made elsewhere and handed over (adopt).
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream&& o) noexcept : s(std::exchange(o.s, nullptr)) {}
+    Stream& operator=(Stream&& o) noexcept { return release(), std::swap(s, o.s), *this; }
+    ~Stream() { if (s) release(); }
+    hipError_t get() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    void adopt(hipStream_t made) { release(), s = made; }
+    void release();
+    operator hipStream_t() const { return s; }
+};
 // An event recorded on a stream and not yet waited for on the host.
 struct Pending {
-    hipEvent_t ev = nullptr;
+    Event ev;
     bool busy = false;
+    Pending() = default;
+    Pending(Pending&& o) noexcept : ev(std::move(o.ev)), busy(std::exchange(o.busy, false)) {}
+    Pending& operator=(Pending&& o) noexcept {
+        return ev = std::move(o.ev), busy = std::exchange(o.busy, false), *this;
+    }
     hipError_t record(hipStream_t s);
     hipError_t wait();  // host-side: returns once the recorded work is done
-    void release();
 };
+template <class T>
+constexpr bool owns = !std::is_copy_constructible<T>::value && !std::is_copy_assignable<T>::value &&
+                      std::is_nothrow_move_constructible<T>::value;
+static_assert(owns<DevBuf> && owns<HostBuf> && owns<Event> && owns<Stream> && owns<Pending>, "holders: move only");
 
 // Status helper: every internal call returns an rs16 code and fills err.
 int set_error(rs16_error* err, int code, uint64_t v0 = 0, uint64_t v1 = 0, uint64_t v2 = 0);
@@ -153,20 +202,22 @@ struct rs16_encoder;
 struct rs16_decoder;
 struct rs16_update_plan;
 struct rs16_locate_plan;
+struct rs16_comm;
 
 struct rs16_engine {
     int device = 0;
     int flags = 0;  // rs16_engine_new_ex flags (RS16_ENGINE_OWN_QUEUE)
-    hipStream_t stream = nullptr;
+    rs16::Stream stream;
     // diagnostic switches of this engine (rs16::DiagFlags, rs16_engine_set_diagnostics)
     int diag = 0;
-    uint32_t* d_skew_tab = nullptr;  // v_perm table per twiddle index (8 MiB)
-    uint32_t* d_skew_tab_tower = nullptr;  // the same in tower coordinates: the passes of a tower sequence
-    uint32_t* d_mul_tab = nullptr;
-    uint32_t* d_col_img = nullptr;   // column codec table images (HostTables::col_img)
-    uint32_t* d_col_v = nullptr;     // column codec eval_poly tables (HostTables::col_v)
-    uint16_t* d_log_walsh = nullptr;
-    uint8_t* d_zero_sink = nullptr;  // zero page (PassArgs::zero, ColArgs::zero)
+    rs16::DevBuf d_skew_tab;        // v_perm table per twiddle index (8 MiB)
+    rs16::DevBuf d_skew_tab_tower;  // the same in tower coordinates: the passes of a tower sequence
+    rs16::DevBuf d_mul_tab;
+    rs16::DevBuf d_col_img;    // column codec table images (HostTables::col_img)
+    rs16::DevBuf d_col_v;      // column codec eval_poly tables (HostTables::col_v)
+    rs16::DevBuf d_log_walsh;  // (uint16_t)
+    rs16::DevBuf d_zero_sink;  // zero page (PassArgs::zero, ColArgs::zero)
+    int upload_tables(rs16_error* err);  // the five of them every engine has (rs16_engine_new_ex)
     // scratch
     rs16::DevBuf ws_z, ws_u, ws_fd, ws_flags;
     // the repair's recovery-only path: the re-encoded recovery shards of the
@@ -194,7 +245,6 @@ struct rs16_engine {
         rs16::DevBuf rbits;   // received-row bitmap (65536 bits)
         rs16::DevBuf lost;    // lost-original row range per 256-row block (2 KiB) + overall (8 B)
         rs16::DevBuf rcount;  // received rows per 64-row chunk and segment (ErasureSpec::rcount)
-        void release() { work32.release(), elog.release(), zflag.release(), rbits.release(), lost.release(), rcount.release(); }
     };
     EvalBufs ev_main, ev_lane[2];
     // What one decode_eval left behind, the value decode_passes works from: the
@@ -220,7 +270,7 @@ struct rs16_engine {
         int nslices = 1;
         DecodePlan plan;  // of its evaluation, which the prepared decode's passes get
     } prep;
-    hipEvent_t prep_ev = nullptr;
+    rs16::Event prep_ev;
     bool prep_pending = false;
     // order stream s after a pending preparation's eval_poly (whose outputs
     // the caller is about to overwrite or read) and drop the preparation
@@ -240,7 +290,7 @@ struct rs16_engine {
     // overlap.  hflags: the received flags of a host decode; hev orders the
     // slots after the engine stream.
     struct HostSlot {
-        hipStream_t s = nullptr;
+        rs16::Stream s;
         rs16::DevBuf orig, rec, z, u;
         rs16::DevBuf rcount;  // the slot's column decodes' received counts (never ws_rcount)
     };
@@ -255,23 +305,23 @@ struct rs16_engine {
     // only fully independent streams (two stripes) gain (+10 %).
     static constexpr int MAX_SLICES = 4;
     int slices = 1;
-    hipStream_t sl_stream[MAX_SLICES] = {};  // per call: [0] = caller's stream, [j] = sl_own[j]
-    hipStream_t sl_own[MAX_SLICES] = {};
-    hipEvent_t sl_fork = nullptr, sl_join[MAX_SLICES] = {};
+    hipStream_t sl_stream[MAX_SLICES] = {};  // per call: [0] = caller's stream, [j] = sl_own[j] (borrowed)
+    rs16::Stream sl_own[MAX_SLICES];
+    rs16::Event sl_fork, sl_join[MAX_SLICES];
     int slice_count(size_t S) const;
     int fork(hipStream_t s, int n, rs16_error* err);
     int join(hipStream_t s, int n, rs16_error* err);
     rs16::DevBuf hflags;
-    hipEvent_t hev = nullptr;
+    rs16::Event hev;
     // pipelined host stripes (rs16_{en,de}code_host_batch): per lane, the
     // flag bytes' copy out of hp_flags is done
-    hipEvent_t hp_ev[2] = {};
-    hipEvent_t hp_off = nullptr;  // the first stripe's H2D is done: the other lane's first H2D starts then
+    rs16::Event hp_ev[2];
+    rs16::Event hp_off;  // the first stripe's H2D is done: the other lane's first H2D starts then
     rs16::HostBuf hp_flags;  // page-locked staging of the decode's flag bytes (2 x (k + m))
     int host_pipe_events(rs16_error* err);
     int host_slots(rs16_error* err);
 
-    hipStream_t pick(void* s) const { return s ? (hipStream_t)s : stream; }
+    hipStream_t pick(void* s) const { return s ? (hipStream_t)s : stream.s; }
     int activate(rs16_error* err);
 
     // The scratch buffers (ws_*) belong to the engine, not to a stream: a
@@ -285,33 +335,38 @@ struct rs16_engine {
     // (then it is recorded on the engine stream, which the engine owns), so
     // the one-stream case costs no event.
     enum { LAST_NONE, LAST_ENGINE, LAST_CALLER } last = LAST_NONE;
-    hipEvent_t order_ev = nullptr;
+    rs16::Event order_ev;
     int order(hipStream_t s, rs16_error* err);
     int scratch_done(hipStream_t s, rs16_error* err);
 
-    // Encoders / decoders created on this engine.  rs16_engine_free releases
-    // their device work space and detaches them (eng = nullptr): a detached
-    // object answers every call with RS16_INVALID_ARGUMENT and
-    // rs16_{en,de}coder_free only frees its host memory.
+    // The five kinds of object created on this engine.  Its destructor detaches
+    // them (rs16::detach, rs16_api.hpp: the object's device and page-locked
+    // memory freed, its eng cleared): a detached object answers every call with
+    // RS16_INVALID_ARGUMENT and its free() only frees host memory.
     std::vector<rs16_encoder*> encoders;
     std::vector<rs16_decoder*> decoders;
-    std::vector<rs16_update_plan*> update_plans;  // detached the same way (rs16_update_plan_free)
-    std::vector<rs16_locate_plan*> locate_plans;  // ... (rs16_locate_plan_free)
+    std::vector<rs16_update_plan*> update_plans;
+    std::vector<rs16_locate_plan*> locate_plans;
+    std::vector<rs16_comm*> comms;
+    // Waits for the engine's work and detaches those objects; the members free
+    // themselves.  The one ordering rule: all waiting happens in the destructor's
+    // body, before any member is destroyed, so the order of the members is free.
+    ~rs16_engine();
 
     // Pass launch (with optional hipEvent timing on the launch stream under
     // profiling id `prof` (rs16::ProfId; -1 = the program's own id).
     int pass(int prog, int T, const rs16::PassArgs& a, uint32_t tiles, hipStream_t s, rs16_error* err,
              int prof = -1);
-    int prof_begin(hipStream_t s, hipEvent_t* ev, rs16_error* err);
-    int prof_end(int id, hipStream_t s, hipEvent_t ev, rs16_error* err);
+    int prof_begin(hipStream_t s, rs16::Event* ev, rs16_error* err);
+    int prof_end(int id, hipStream_t s, rs16::Event ev, rs16_error* err);
     // One kernel launch under profiling id `prof`: launch(stamps) returns the
     // launch's hipError_t; stamps = stamp_buf when `prof` is the stamped id,
     // else nullptr.  The only caller of prof_begin / prof_end.
     template <class F> int profiled(int prof, hipStream_t s, rs16_error* err, F launch) {
-        hipEvent_t ev;
+        rs16::Event ev;  // (stays empty unless profiling is on)
         if (int rc = prof_begin(s, &ev, err)) return rc;
         const hipError_t he = launch(stamp_buf && prof == stamp_prof ? (uint64_t*)stamp_buf : nullptr);
-        return he == hipSuccess ? prof_end(prof, s, ev, err) : rs16::hip_fail(err, he);
+        return he == hipSuccess ? prof_end(prof, s, std::move(ev), err) : rs16::hip_fail(err, he);
     }
     bool profiling = false;
     // diagnostic timelines (rs16_engine_set_stamps): passes under profiling
@@ -320,10 +375,10 @@ struct rs16_engine {
     int stamp_prof = -1;
     struct ProfRec {
         int id;
-        hipEvent_t a, b;
+        rs16::Event a, b;
     };
     std::vector<ProfRec> prof_pending;
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<rs16::Event> ev_pool;  // timing events not in use
     double prof_ms[rs16::NUM_PROF] = {};
     uint64_t prof_n[rs16::NUM_PROF] = {};
     int prof_collect(rs16_error* err);

@@ -1297,15 +1297,23 @@ class Comm:
         _check(lib().rs16_comm_init_all(_engine_array(engines), len(engines), arr, C.byref(err)), err)
         return [cls(e, _h=arr[i]) for i, e in enumerate(engines)]
 
+    @staticmethod
+    def _count(n: int) -> int:
+        if n < 0:  # (a communicator whose engine was freed answers -RS16_INVALID_ARGUMENT)
+            raise Error("InvalidArgument")
+        return n
+
     @property
     def rank(self) -> int:
-        return lib().rs16_comm_rank(self.h)
+        return self._count(lib().rs16_comm_rank(self.h))
 
     @property
     def size(self) -> int:
-        return lib().rs16_comm_size(self.h)
+        return self._count(lib().rs16_comm_size(self.h))
 
     def close(self):
+        # Safe after the engine is gone: rs16_engine_free detaches its
+        # communicators, and freeing a detached one only frees host memory.
         if getattr(self, "h", None):
             lib().rs16_comm_free(self.h)
             self.h = None
