@@ -864,6 +864,72 @@ size_t rs16_update_plan_count(const rs16_update_plan* plan);
 int rs16_update_plan_coefficients(rs16_update_plan* plan, uint16_t* out, rs16_error* err);
 int rs16_update_device(rs16_update_plan* plan, size_t shard_bytes, const void* d_delta, void* d_recovery,
                        size_t recovery_pos, size_t recovery_n, void* stream, rs16_error* err);
+/* rs16_update_device on a column window of the shards, for a batch of stripes
+ * of one geometry in one launch.  Every 64-byte column block
+ * is a codeword of its own (src/algorithm.md:18-32), so a write that changes
+ * bytes [off, off + width) of some originals changes the same bytes of the
+ * recovery shards and no others; and the plan's table of (recovery row, delta
+ * shard) is the same for every stripe of a geometry.
+ *
+ * Layout.  `width` = the bytes of every row that are updated, a multiple of
+ * 64.  d_delta and d_recovery point at the window's FIRST byte: the caller
+ * has added the column offset, a multiple of 64, so they are 64-byte aligned
+ * like every shard array.  Delta e (old ^ new of original indices[e], its
+ * window) of stripe i lies at d_delta + i delta_stride + e delta_pitch;
+ * recovery shard recovery_pos + r of stripe i at d_recovery + i
+ * recovery_stride + r recovery_pitch, r < recovery_n.  Bytes of a row outside
+ * [0, width), rows outside the range and bytes between strides are neither
+ * read as data nor written; the deltas are read only.  Each stripe's result
+ * is that of rs16_update_device on the stripe's whole shards with deltas that
+ * are zero outside the window -- and so that of a re-encode.  Asynchronous on
+ * `stream`, in place.  The strides of a single stripe (nstripes == 1) are not
+ * used.
+ *
+ * Errors, checked in this order: a NULL or detached plan: InvalidArgument;
+ * width 0 or no multiple of 64: InvalidShardSize (v0 = width); a range beyond
+ * recovery_count: InvalidArgument; recovery_n == 0 or nstripes == 0: RS16_OK,
+ * nothing launched; then InvalidArgument for a NULL or misaligned array; a
+ * pitch that is no multiple of 64 or below width; for nstripes > 1 a stride
+ * that is no multiple of 64, a recovery_stride below (recovery_n - 1)
+ * recovery_pitch + width or a delta_stride below (n - 1) delta_pitch + width
+ * (stripes would overlap); nstripes > 65535 (the heal's cap); a width or pitch
+ * of 4 GiB or more.  Like rs16_update_device it uses no engine scratch and no
+ * decode state: any stream, beside the engine's other work; it neither
+ * disturbs rs16_decode_check nor a pending rs16_decode_prepare.
+ *
+ * When to prefer it (MI355X, DESIGN.md 3.22, profiles/r22_update_batch.txt;
+ * hipEvent time per call through the Python binding, against the library of
+ * the commit before in a process of its own, five alternating pairs):
+ * - Stripes: at 1000:1000 x 1 KiB the batch beats a loop of
+ *   rs16_update_device calls from 4 stripes on, the fewest measured above
+ *   one, in every pair: 4 stripes 4.4 / 4.9 / 11.5 us at n = 1 / 4 / 16
+ *   against 14.1 / 15.5 / 19.1 for the loop, 8 stripes 5.2 / 7.9 / 20.0
+ *   against 29.3 / 30.8 / 37.7, 32 stripes 11.4 / 19.5 / 53.9 against 121.8 /
+ *   125.2 / 148.8.  At 32768:32768 x 1 KiB the sweep dominates: 4 stripes 41.7
+ *   / 53.7 / 203.9 against 53.0 / 76.8 / 223.9 (1.27 / 1.43 / 1.10 x).  It
+ *   lost to the loop nowhere.
+ * - Windows: a 4 KiB window of 64 KiB shards takes 4.3 / 4.9 / 11.3 us at
+ *   1000:1000 and 10.6 / 18.5 / 56.7 at 8000:8000, against 21.2 / 31.2 / 106.2
+ *   and 227.7 / 229.7 / 730.4 for rs16_update_device on the whole shards with
+ *   zero-padded deltas: 4.9 .. 9.4 x and 12.4 .. 21.4 x.
+ * - Windows of at most 128 bytes of two stripes or more take a packed form
+ *   (8 or 4 stripes a wave): 32 stripes of 64 bytes 4.0 / 4.4 / 7.9 us, of
+ *   128 bytes 4.3 / 6.0 / 12.5, against 5.7 / 11.0 / 33.0 and 5.8 / 10.4 /
+ *   29.9 with one stripe a wave.
+ * - One stripe at full width is the single call's work through a longer
+ *   argument list: at 1000:1000 x 1 KiB 4.2 / 4.4 / 5.1 us against 3.5 / 3.9 /
+ *   5.0, outside the single call's run-to-run spread at n = 1 and 4 (both are
+ *   bound by the launch), inside it at 16; at 32768:32768 12.8 / 19.2 / 56.5
+ *   against 12.6 / 19.4 / 58.5, inside it at n = 1 and 4.  For one stripe of
+ *   whole shards rs16_update_device stays the call to make.
+ * - rs16_update_device itself is unchanged: the same machine code
+ *   (scripts/isa_compare.py), this build's median inside the parent's spread
+ *   in 21 of 24 rows, 0.11 us slower to 5.8 us faster in the other three.
+ * Sizes in between are not measured. */
+int rs16_update_device_batch(rs16_update_plan* plan, size_t width, size_t nstripes,
+                             const void* d_delta, size_t delta_pitch, size_t delta_stride,
+                             void* d_recovery, size_t recovery_pitch, size_t recovery_stride,
+                             size_t recovery_pos, size_t recovery_n, void* stream, rs16_error* err);
 
 /* ---- Host-resident stripes, pipelined (full duplex) -----------------------
  * nstripes independent stripes in host memory (stripe i's originals at
@@ -1168,6 +1234,23 @@ uint64_t rs16_host_tower_sweep(const uint32_t* index, size_t n, int form, const 
  * 0, no multiple of 64 or too large, n = 0 or above RS16_UPDATE_MAX_SHARDS). */
 int rs16_host_update_consts(uint32_t rows, uint64_t shard_bytes, uint32_t n, uint32_t* quads_per_lane,
                             uint32_t* nslab, uint32_t* rows_per_wave, uint64_t* blocks);
+/* The same for rs16_update_device_batch: `rows` recovery rows of a window of
+ * `width` bytes, `n` deltas, `nstripes` stripes (one host function, which the
+ * batch launcher calls; no device needed).  out[0 .. 6) =
+ *   quads_per_lane, nslab, rows_per_wave   as above, of the window
+ *   stripes_per_wave  stripes a wave works on: above 1 is the packed form of
+ *                     windows of at most 128 bytes (lane l: quad l mod qrow of
+ *                     stripe l / qrow of the wave's group, qrow = width / 8)
+ *   waves             waves with work: wave w has slab w mod nslab of stripe
+ *                     group (w / nslab) mod ngroups of run w / (nslab ngroups),
+ *                     ngroups = ceil(nstripes / stripes_per_wave)
+ *   blocks            workgroups of four waves
+ * One stripe gives the quads_per_lane, nslab and rows_per_wave of
+ * rs16_host_update_consts.  Returns 1, or 0 where rs16_update_device_batch
+ * launches nothing or fails (rows = 0, nstripes = 0 or above 65535, a width
+ * that is 0, no multiple of 64 or 4 GiB and more, n = 0 or above
+ * RS16_UPDATE_MAX_SHARDS). */
+int rs16_host_update_batch_consts(uint32_t rows, uint64_t width, uint32_t n, uint32_t nstripes, uint32_t out[6]);
 /* The path rs16_repair_device takes, as the entry points decide it (one host
  * function; no device needed): 0 nothing to do, 1 = rs16_decode_device (no
  * recovery shard lost), 2 = encode + copy of the lost recovery rows (no

@@ -234,6 +234,18 @@ extern "C" int rs16_host_update_consts(uint32_t rows, uint64_t shard_bytes, uint
     if (blocks) *blocks = nb;
     return 1;
 }
+extern "C" int rs16_host_update_batch_consts(uint32_t rows, uint64_t width, uint32_t n, uint32_t nstripes,
+                                             uint32_t out[6]) {
+    // (the checks of rs16_update_device_batch)
+    if (width == 0 || (width & 63) != 0 || width > 0xFFFFFFFFu || nstripes > 65535 || !out) return 0;
+    UpdateBatchArgs a{};
+    a.qrow = (uint32_t)(width / 8), a.rows = rows, a.nstripes = nstripes;
+    uint64_t nb;
+    if (!update_batch_launch_consts(a, n, &nb)) return 0;  // (the function launch_update_batch calls)
+    out[0] = a.quads_per_lane, out[1] = a.nslab, out[2] = a.rows_per_wave, out[3] = a.stripes_per_wave;
+    out[4] = a.waves, out[5] = (uint32_t)nb;
+    return 1;
+}
 
 extern "C" int rs16_engine_set_profiling(rs16_engine* e, int enable, rs16_error* err) {
     if (int rc = e->activate(err)) return rc;

@@ -117,3 +117,46 @@ extern "C" int rs16_update_device(rs16_update_plan* p, size_t S, const void* d_d
     RS16_HIP(launch_update(a, (uint32_t)p->n, e->pick(stream)));
     return set_error(err, RS16_OK);
 }
+
+// (rows - 1) pitch + width <= stride, without overflow (rows >= 1, pitch >= width)
+static bool rows_fit(size_t rows, size_t pitch, size_t width, size_t stride) {
+    return stride >= width && (stride - width) / pitch >= rows - 1;
+}
+
+extern "C" int rs16_update_device_batch(rs16_update_plan* p, size_t width, size_t nstripes, const void* d_delta,
+                                        size_t delta_pitch, size_t delta_stride, void* d_recovery,
+                                        size_t recovery_pitch, size_t recovery_stride, size_t recovery_pos,
+                                        size_t recovery_n, void* stream, rs16_error* err) {
+    if (!p || !p->eng) return set_error(err, RS16_INVALID_ARGUMENT);
+    if (width == 0 || (width & 63) != 0) return set_error(err, RS16_INVALID_SHARD_SIZE, width);
+    if (recovery_pos > p->m || recovery_n > p->m - recovery_pos) return set_error(err, RS16_INVALID_ARGUMENT);
+    if (recovery_n == 0 || nstripes == 0) return set_error(err, RS16_OK);
+    if (!d_delta || !d_recovery || !shard_aligned(d_delta) || !shard_aligned(d_recovery))
+        return set_error(err, RS16_INVALID_ARGUMENT);
+    if ((delta_pitch & 63) != 0 || (recovery_pitch & 63) != 0 || delta_pitch < width || recovery_pitch < width)
+        return set_error(err, RS16_INVALID_ARGUMENT);
+    // (stripes that overlap would race: each is read and written by waves of its own)
+    if (nstripes > 1 && ((delta_stride & 63) != 0 || (recovery_stride & 63) != 0 ||
+                         !rows_fit(recovery_n, recovery_pitch, width, recovery_stride) ||
+                         !rows_fit(p->n, delta_pitch, width, delta_stride)))
+        return set_error(err, RS16_INVALID_ARGUMENT);
+    // (the heal's cap; a lane's offset inside a row is a 32-bit count)
+    if (nstripes > 65535 || width > 0xFFFFFFFFu || delta_pitch > 0xFFFFFFFFu || recovery_pitch > 0xFFFFFFFFu)
+        return set_error(err, RS16_INVALID_ARGUMENT);
+    rs16_engine* e = p->eng;
+    if (int rc = e->activate(err)) return rc;
+    UpdateBatchArgs a{};
+    a.rec = (uint8_t*)d_recovery;
+    a.delta = (const uint8_t*)d_delta;
+    a.idx = (const uint32_t*)p->dev.idx.p;
+    a.mul_tab = e->d_mul_tab.as<uint32_t>();
+    a.delta_pitch = delta_pitch, a.rec_pitch = recovery_pitch;
+    // (one stripe has no stride: whatever the caller passed is not used)
+    a.delta_stride = nstripes > 1 ? delta_stride : 0, a.rec_stride = nstripes > 1 ? recovery_stride : 0;
+    a.qrow = (uint32_t)(width / 8);
+    a.row0 = (uint32_t)recovery_pos;
+    a.rows = (uint32_t)recovery_n;
+    a.nstripes = (uint32_t)nstripes;
+    RS16_HIP(launch_update_batch(a, (uint32_t)p->n, e->pick(stream)));
+    return set_error(err, RS16_OK);
+}

@@ -620,6 +620,31 @@ struct UpdateArgs {
 bool update_launch_consts(UpdateArgs& a, uint32_t n, uint64_t* blocks);
 hipError_t launch_update(UpdateArgs a, uint32_t n, hipStream_t s);
 
+// The same update on a column window of a batch of stripes
+// (rs16_update_batch.hip): for every stripe i < nstripes,
+// rec_i[r] ^= sum over e < n of delta_i[e] * (table of entry idx[(row0 + r) n + e])
+// on the first 8 qrow bytes of the rows, with row r of stripe i at
+// rec + i rec_stride + r rec_pitch and delta e at delta + i delta_stride +
+// e delta_pitch.
+struct UpdateBatchArgs {
+    uint8_t* rec;            // the window's first byte of recovery row row0 of stripe 0
+    const uint8_t* delta;    // the window's first byte of delta 0 of stripe 0
+    const uint32_t* idx;     // the plan's recovery_count x n mul-table entries
+    const uint32_t* mul_tab;
+    uint64_t delta_pitch, delta_stride, rec_pitch, rec_stride;  // bytes
+    uint32_t qrow;           // quads per window row = width / 8
+    uint32_t row0, rows, nstripes;
+    // set by update_batch_launch_consts: stripes_per_wave > 1 is the packed
+    // form (one slab, one quad per lane), ngroups the stripe groups of
+    // stripes_per_wave, waves the waves with work
+    uint32_t quads_per_lane, nslab, rows_per_wave, stripes_per_wave, ngroups, waves;
+};
+// The shape of that launch, as update_launch_consts gives the single call's:
+// launch_update_batch calls it and rs16_host_update_batch_consts exports it.
+// One stripe gives the single call's quads per lane, slabs and rows per wave.
+bool update_batch_launch_consts(UpdateBatchArgs& a, uint32_t n, uint64_t* blocks);
+hipError_t launch_update_batch(UpdateBatchArgs a, uint32_t n, hipStream_t s);
+
 // FWHT / eval_poly.  `work` is a u32[65536] scratch.
 struct ErasureSpec {           // builds the erasure vector of rate_{high,low}.rs decode
     const uint8_t* flags_a;    // received flags of segment A

@@ -1133,6 +1133,21 @@ class UpdatePlan:
         _check(lib().rs16_update_device(self.h, shard_bytes, Engine._ptr(d_delta), Engine._ptr(d_recovery),
                                         recovery_pos, recovery_n, stream, C.byref(self._err)), self._err)
 
+    def apply_batch(self, width, nstripes, d_delta, delta_pitch, delta_stride, d_recovery, recovery_pitch,
+                    recovery_stride, recovery_pos=0, recovery_n=None, stream=None):
+        """rs16_update_device_batch: apply() on a window of `width` bytes of
+        every row, for `nstripes` stripes in one launch.  d_delta / d_recovery
+        point at the window's first byte (the column offset, a multiple of 64,
+        already added); delta e of stripe i lies at d_delta + i delta_stride +
+        e delta_pitch, recovery shard recovery_pos + r of stripe i at
+        d_recovery + i recovery_stride + r recovery_pitch.  Bytes outside the
+        window are neither read as data nor written.  Asynchronous on `stream`."""
+        if recovery_n is None:
+            recovery_n = max(self.recovery_count - recovery_pos, 0)
+        _check(lib().rs16_update_device_batch(self.h, width, nstripes, Engine._ptr(d_delta), delta_pitch,
+                                              delta_stride, Engine._ptr(d_recovery), recovery_pitch, recovery_stride,
+                                              recovery_pos, recovery_n, stream, C.byref(self._err)), self._err)
+
     def close(self):
         # Safe after the engine is gone: rs16_engine_free detaches its plans,
         # and freeing a detached one only frees host memory.

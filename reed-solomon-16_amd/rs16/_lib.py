@@ -160,6 +160,8 @@ SIGNATURES = {
     "rs16_update_plan_count": (_sz, [_p]),
     "rs16_update_plan_coefficients": (_i, [_p, C.POINTER(C.c_uint16), _e]),
     "rs16_update_device": (_i, [_p, _sz, _p, _p, _sz, _sz, _p, _e]),
+    "rs16_update_device_batch": (_i, [_p, _sz, _sz, _p, _sz, _sz, _p, _sz, _sz, _sz, _sz, _p, _e]),
+    "rs16_host_update_batch_consts": (_i, [_u32, _u64, _u32, _u32, C.POINTER(_u32)]),
     "rs16_encode_host_batch":(_i, [_p, _sz, _sz, _sz, _sz, _p, _sz, _p, _sz, _e]),
     "rs16_decode_host_batch": (_i, [_p, _sz, _sz, _sz, _sz, _p, _sz, _p, _sz, _p, _sz, _p, _sz, _e]),
     "rs16_decode_host_multi": (_i, [_p, _i, _sz, _sz, _sz, _p, _p, _p, _p, _e]),
